@@ -723,6 +723,37 @@ def _comm_report(sync, dev, step, iters=10):
     return rep
 
 
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, out, loss, model):
+    """--dump-outputs: what the last timed step handed its caller -- the model's output dict, the joint loss, and the
+    parameters and gradients after opt.step() (flattened and concatenated in named_parameters() order) -- as
+    out_dir/<name>.npy in float32.  Over the 64 MB budget, the largest arrays are cut to a fixed, seeded sample of their
+    flattened elements (same positions every run), smallest arrays kept whole first."""
+    import zlib
+    import numpy as np
+    params = [p for _, p in model.named_parameters()]
+    arrays = {'loss': loss.detach().reshape(1)}
+    arrays.update({k: v.detach() for k, v in out.items() if v is not None})
+    arrays['params'] = torch.cat([p.detach().reshape(-1).float() for p in params])
+    arrays['grads'] = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float()
+                                 for p in params])
+    arrays = {k: v.float().cpu().numpy() for k, v in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_BUDGET_BYTES // 4                    # float32 elements
+    names = sorted(arrays, key=lambda k: arrays[k].size)
+    for i, k in enumerate(names):
+        a = arrays[k]
+        n = min(a.size, left // (len(names) - i))
+        if n < a.size:
+            idx = np.sort(np.random.default_rng(zlib.crc32(k.encode())).choice(a.size, n, replace=False))
+            a = a.reshape(-1)[idx]
+        left -= a.size
+        np.save(os.path.join(out_dir, k + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
+    print(f'bench.py: wrote {len(names)} arrays of the last timed step to {out_dir}', file=sys.stderr, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -735,9 +766,14 @@ def main():
                     help='time the step only (the command profiles/r03_bench_kernel_stats.csv is taken from: its kernel times sum to the step)')
     ap.add_argument('--roofline-only', action='store_true',
                     help='run only the roofline kernel measurements (the command profiles/r02_roofline_kernel_stats.csv and the PMC passes are taken from)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed (model outputs, loss, updated '
+                         'parameters, gradients) as DIR/<name>.npy, float32, at most 64 MB in all (e.g. bench_out/)')
     ap.add_argument('--selftest-gloo', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--selftest-fail-rank', type=int, default=-1, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        _fail(f'--steps must be >= 1 (got {args.steps})')
     if args.roofline_only:
         dev = torch.device('cuda:0')
         _warm_clocks(dev)
@@ -788,7 +824,7 @@ def main():
         loss.backward()
         sync.finish()
         opt.step()
-        return loss
+        return loss, out
 
     for _ in range(args.warmup):
         step()
@@ -797,7 +833,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        loss, out = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -808,6 +844,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     final_loss = float(loss)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, loss, model)      # before _comm_report's extra steps move the parameters
     rccl_world = dist.get_world_size() if dist.is_initialized() else 0
     if world > 1 and rccl_world != args.gpus:
         _fail(f'the RCCL group has {rccl_world} ranks, --gpus says {args.gpus}')
