@@ -195,6 +195,16 @@ int rovit_vit_forward_prepare(const float* images, const float* const* params, v
  * probabilities per block, what explainability/attention_maps.py:18-105 means to roll out.  Inference workspace. */
 int rovit_vit_forward_taps(const float* images, const float* const* params, const void* prep, void* workspace, float* features,
                            void* const* attn_taps, float* const* prob_taps, int batch, int depth, rovit_stream_t stream);
+/* forward + attention rollout (explainability/attention_maps.py:40-95, ViTAttentionRollout.generate): rollout fp32 (B,197)
+ * receives row 0 of  A^_1 ... A^_depth,  A^_l = the block's head-fused softmax probabilities (head_fusion 0 mean, 1 max, 2 min)
+ * plus the identity, rows renormalised.  Computed behind every block's attention; no probability matrix is stored.
+ * Inference workspace; bf16 engine. */
+int rovit_vit_forward_rollout(const float* images, const float* const* params, const void* prep, void* workspace, float* features,
+                              float* rollout, int head_fusion, int batch, int depth, rovit_stream_t stream);
+/* the reference's map from a rollout (attention_maps.py:96-103): rollout[:, 1:] as 14x14, bilinear (half-pixel centres, edges
+ * clamped: cv2.resize INTER_LINEAR / F.interpolate align_corners=False) to 224x224, then (m - min) / (max - min + 1e-8) per
+ * image.  map224 fp32 (B,224,224). */
+int rovit_rollout_map(const float* rollout, float* map224, int batch, rovit_stream_t stream);
 /* images: the batch the forward ran on (read by the patch-embedding weight gradient, which gathers its pixels from it:
  * there is no im2col buffer); may be NULL for ranges with last_block > 0. */
 int rovit_vit_backward(const float* images, const float* d_features, const float* const* params, const void* prep, void* workspace,

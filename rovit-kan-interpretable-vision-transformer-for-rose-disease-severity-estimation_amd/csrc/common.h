@@ -208,6 +208,9 @@ void rovit_set_cu_budget(int cus);   // gemm.hip: CUs the weight-stationary GEMM
 hipStream_t rovit_side_stream_handle();
 int rovit_layernorm_fwd_rows(const float* x, void* xhat, float* rstd, int rows, int row_step, float eps, rovit_stream_t stream);
 int rovit_cls_norm_affine_grad(const float* dfeat, const float* xhat, float* dgamma, float* dbeta, int batch, rovit_stream_t stream);
+// rollout.hip: one block's attention-rollout update of v (B,197) from its saved qkv (first: v is e_0); partial: fp32 scratch of
+// batch x 13 x 197 floats.  Two launches (per-row-slice partials, fixed-order combine).
+int rovit_rollout_step(const void* qkv, float* v, float* partial, int head_fusion, int batch, int first, rovit_stream_t stream);
 // cls_tail.hip: the last block's post-attention half + the final norm on the class-token rows in one launch
 int rovit_cls_tail_fwd(const void* o, float* X, const void* wproj, const float* bproj, const void* wfc1, const float* bfc1, const void* wfc2,
                        const float* bfc2, const float* gamma, const float* beta, void* xhat2, float* rstd2, void* act, void* dact, float* feat,

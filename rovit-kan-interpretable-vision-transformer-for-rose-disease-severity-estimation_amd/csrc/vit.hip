@@ -260,7 +260,7 @@ namespace {
 // prepare: 0 = the weights in `prep` are current; 1 = prepare them from `params` first; 2 = ... and write the constant tables too
 int vit_forward_impl(const float* images, const float* const* params, const void* prep, void* workspace, float* features,
                      void* const* attn_taps, float* const* prob_taps, int batch, int depth, int training, int mlp_path,
-                     rovit_stream_t stream, int prepare = 0) {
+                     rovit_stream_t stream, int prepare = 0, float* rollout = nullptr, int head_fusion = 0) {
   ROVIT_CHECK_ARG(images && features, ROVIT_ERR_NULL, "vit_forward: null images/features");
   RUN(check_common(params, prep, workspace, batch, depth, mlp_path));
   const Prep P(depth);
@@ -270,10 +270,13 @@ int vit_forward_impl(const float* images, const float* const* params, const void
   float* X = (float*)(ws + L.X);
   const int M = (int)L.M;
   const float eps = 1e-6f;
+  // explainability outputs want every token of every block: one stream, no class-token shortcuts in the last block
+  const bool taps = attn_taps || prob_taps || rollout;
+  // (the rollout's partial sums, batch x 13 x 197 floats, sit in the dact slot: 52 bytes per token row of its 1536)
   // Weight preparation inside the forward (rovit_vit_forward_prepare): four launches, 41 us per training step when they stand in front
   // of the forward.  Only the patch-embedding weight is needed at once; the blocks' weights are prepared on the side stream BESIDE the
   // patch embedding (59 us, bound by the fp32 pixels it reads), and the caller's stream waits for them in front of block 0.
-  SideStream* ss_prep = (prepare && two_streams_enabled() && !attn_taps && !prob_taps && batch >= 16) ? side_stream() : nullptr;
+  SideStream* ss_prep = (prepare && two_streams_enabled() && !taps && batch >= 16) ? side_stream() : nullptr;
   hipEvent_t ev_prep = nullptr;
   if (prepare) {
     if (ss_prep) {
@@ -291,7 +294,7 @@ int vit_forward_impl(const float* images, const float* const* params, const void
   // chain on two HIP streams with no synchronisation until the final norm: every kernel here is a 20-50 us
   // persistent launch with ~6 us of ramp (dispatch, weight prologue, first tile, tail), which the other half's
   // kernels now cover.  Each half asks for half of the CUs (rovit_set_cu_budget) so the two chains co-reside.
-  SideStream* ss = (two_streams_enabled() && !attn_taps && !prob_taps && batch >= 16) ? side_stream() : nullptr;
+  SideStream* ss = (two_streams_enabled() && !taps && batch >= 16) ? side_stream() : nullptr;
   struct Half { int b0, nb; rovit_stream_t st; };
   Half halves[2] = {{0, ss ? (batch + 1) / 2 : batch, stream}, {(batch + 1) / 2, ss ? batch / 2 : 0, ss ? (rovit_stream_t)ss->stream : stream}};
   const int nh = ss ? 2 : 1;
@@ -302,7 +305,7 @@ int vit_forward_impl(const float* images, const float* const* params, const void
   }
   struct BudgetReset { bool on; ~BudgetReset() { if (on) rovit_set_cu_budget(256); } } budget_reset{ss != nullptr};
 #define EACH_HALF for (int hh = 0; hh < nh; ++hh)
-  const bool cls_fused = !attn_taps && !prob_taps;      // the last block's class-token rows: one launch (cls_tail.hip)
+  const bool cls_fused = !taps;      // the last block's class-token rows: one launch (cls_tail.hip)
   bool qkv_done = false;              // the previous block's tail launch has already written this block's qkv projection
   for (int i = 0; i < depth; ++i) {
     const float* const* bp = params + P_BLOCK0 + B_COUNT * i;
@@ -336,7 +339,7 @@ int vit_forward_impl(const float* images, const float* const* params, const void
       }
       // the last block: only the class token's attention output is consumed (the half behind it runs on those rows alone), and a query's
       // output needs no other query -- 197 scores per (image, head) instead of 197 x 197 (taps want every token's output: full kernel)
-      if (cls_only && !attn_taps && !prob_taps) {
+      if (cls_only && !taps) {
         RUN(rovit_attention_cls_fwd(ROWS(s + L.qkv, 3 * D, 2), ROWS(s + L.o, D, 2), (float*)(s + L.lse) + (size_t)h.b0 * H * T, h.nb, T, H, D / H,
                                     0.125f, h.st));
       } else {
@@ -352,6 +355,9 @@ int vit_forward_impl(const float* images, const float* const* params, const void
     // ... and, separately, the softmax probabilities (B,3,197,197) the reference's rollout code means to collect
     // (explainability/attention_maps.py:18-105)
     if (prob_taps && prob_taps[i]) RUN(rovit_attention_probs(s + L.qkv, prob_taps[i], batch, T, H, D / H, 0.125f, stream));
+    // ... and the attention rollout (rollout.hip), folded into a running (B,197) vector behind every block's attention (before the
+    // block tail overwrites qkv with the next block's); its partial sums use the dact slot, which an inference forward never writes
+    if (rollout) RUN(rovit_rollout_step(s + L.qkv, rollout, (float*)(s + L.dact), head_fusion, batch, i == 0, stream));
     // The last block: its post-attention half AND the final norm on the class-token rows in ONE launch (cls_tail.hip; six launches before).
     // (Taps want the attention module's output for every token: the launch-by-launch path below.)
     if (cls_only && cls_fused) {
@@ -448,6 +454,20 @@ extern "C" int rovit_vit_forward_taps(const float* images, const float* const* p
                                       rovit_stream_t stream) {
   ROVIT_CHECK_ARG(attn_taps || prob_taps, ROVIT_ERR_NULL, "vit_forward_taps: no tap array given");
   return vit_forward_impl(images, params, prep, workspace, features, attn_taps, prob_taps, batch, depth, 0, ROVIT_MLP_AUTO, stream);
+}
+
+// Same forward (inference workspace), additionally folding every block's attention into the attention rollout
+// (rollout.hip): rollout fp32 (B,197) receives row 0 of  A^_1 ... A^_depth,  A^_l = rownorm(fuse_heads(P_l) + I), the
+// vector the reference's ViTAttentionRollout.generate builds from hooked probabilities and 12 matrix products
+// (explainability/attention_maps.py:40-95).  head_fusion: 0 mean, 1 max, 2 min over the heads (attention_maps.py:63-70).
+// Like the taps, every query row of the last block is computed (no class-token shortcut).
+extern "C" int rovit_vit_forward_rollout(const float* images, const float* const* params, const void* prep, void* workspace,
+                                         float* features, float* rollout, int head_fusion, int batch, int depth, rovit_stream_t stream) {
+  ROVIT_CHECK_ARG(rollout, ROVIT_ERR_NULL, "vit_forward_rollout: null rollout");
+  ROVIT_CHECK_ARG(head_fusion >= 0 && head_fusion <= 2, ROVIT_ERR_SHAPE, "vit_forward_rollout: head_fusion must be 0 (mean), 1 (max) or 2 (min), got %d",
+                  head_fusion);
+  return vit_forward_impl(images, params, prep, workspace, features, nullptr, nullptr, batch, depth, 0, ROVIT_MLP_AUTO, stream, 0, rollout,
+                          head_fusion);
 }
 
 // Backward over blocks first_block, first_block-1, ..., last_block (inclusive).  first_block == depth-1 also

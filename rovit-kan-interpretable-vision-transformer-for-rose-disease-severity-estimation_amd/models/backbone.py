@@ -248,6 +248,12 @@ class DeiTTinyBackbone(nn.Module):
         from rovit_hip import taps
         return taps.attention_probabilities(self.model, x)
 
+    def attention_rollout(self, x: torch.Tensor, head_fusion: str = 'mean', upsample: bool = True):
+        """Extension (not in the reference): attention rollout of every image of the batch on the GPU, (B,224,224) maps when
+        ``upsample`` else the raw (B,14,14) rollout (rovit_hip.rollout.attention_rollout)."""
+        from rovit_hip import rollout
+        return rollout.attention_rollout(self.model, x, head_fusion, upsample)
+
 
 def freeze_backbone(model: nn.Module, freeze: bool = True):
     if not hasattr(model, 'backbone'):

@@ -182,6 +182,10 @@ class RoViTKAN(nn.Module):
     def get_attention_maps(self, x: torch.Tensor):
         return self.backbone.get_attention_maps(x)
 
+    def attention_rollout(self, x: torch.Tensor, head_fusion: str = 'mean', upsample: bool = True):
+        """Extension (not in the reference): DeiTTinyBackbone.attention_rollout of the backbone."""
+        return self.backbone.attention_rollout(x, head_fusion, upsample)
+
     def count_parameters(self) -> Dict[str, int]:
         def n(m):
             return sum(p.numel() for p in m.parameters() if p.requires_grad)
