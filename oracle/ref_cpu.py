@@ -399,8 +399,8 @@ def uncertainty_loss(mu, log_var, targets):
 
 
 def kan_regression_loss(pred, targets):
-    """training/losses.py:109-114."""
-    y = targets.unsqueeze(1).float() if targets.dim() == 1 else targets
+    """training/losses.py:109-114 (targets in the prediction's dtype: mse_loss needs one dtype, the fp64 oracle runs included)."""
+    y = targets.unsqueeze(1).to(pred.dtype) if targets.dim() == 1 else targets.to(pred.dtype)
     return F.mse_loss(pred, y)
 
 

@@ -196,10 +196,18 @@ class HeadPhaseFn(torch.autograd.Function):
     cfg: stage; masks (list of 3 scaled keep-masks / None entries) or None; drop_p, seed, offset (dropout drawn in the kernel
     when masks is None and drop_p > 0); kan_knots (list of knot buffers), kan_acts, kan_dims ([] = no KAN stack);
     grad_views: optional {param.data_ptr(): tensor} of flat-buffer views the parameter gradients may be written into directly.
-    outputs: cls, ord, mu, log_var, kan (the last KAN layer's output); inactive ones are zero-size placeholders."""
+    outputs: cls, ord, mu, log_var, kan (the last KAN layer's output); inactive ones are zero-size placeholders.
+
+    Parameter gradients go to a stream of their own (beside the backbone's backward, joined when the backward pass ends) only when
+    autograd is certain to take them without reading them before that join: the first HeadPhaseFn node of the pass for these
+    parameters, no parameter holding a .grad (AccumulateGrad steals the tensor instead of adding into .grad), and no tensor hook or
+    post-accumulate-grad hook on any of them.  Otherwise they are computed inline on the backward's stream, and a later node of the
+    same pass (two forwards of one model in one graph) also makes that stream wait for the earlier node's side-stream launch,
+    because autograd adds the two nodes' gradients as soon as the second one returns."""
 
     _streams = {}          # device index -> the stream the parameter-gradient launch runs on
     _pending = {}          # device index -> event recorded behind the most recent parameter-gradient launch (until waited for)
+    _claimed = {}          # device index -> (graph task id, data_ptrs of the parameters the pass's HeadPhaseFn nodes produced gradients for)
 
     @staticmethod
     def param_grad_stream(dev):
@@ -316,14 +324,24 @@ class HeadPhaseFn(torch.autograd.Function):
         for l in range(nl):
             d.kan_gz[l] = scratch.data_ptr() + 4 * off
             off += B * dims[l + 1]
-        # parameter gradients: written straight into the optimizer's flat gradient buffer when it offered views and nothing has been
-        # accumulated yet (autograd then installs the view as .grad without a copy); otherwise into fresh tensors
+        # parameter gradients: written straight into the optimizer's flat gradient buffer when it offered views and autograd will install
+        # them as .grad untouched (see `unread`); otherwise into fresh tensors
         live_h = [g_cls is not None] * 4 + [g_ord is not None] * 4 + [g_mu is not None] * 6
         live_k = [g_kan is not None] * (3 * nl)
         need = [ctx.needs_input_grad[2 + i] for i in range(14 + 3 * nl)]
-        want = any(n and l for n, l in zip(need, live_h + live_k))
+        out_ps = [p_ for p_, n, l in zip(params, need, live_h + live_k) if n and l]
+        want = bool(out_ps)
+        task = torch._C._current_graph_task_id()
+        claim = HeadPhaseFn._claimed.get(dev.index)
+        if claim is None or claim[0] != task:
+            claim = HeadPhaseFn._claimed[dev.index] = (task, set())
+        first = not any(p_.data_ptr() in claim[1] for p_ in out_ps)      # no earlier node of this pass produced gradients for them
+        claim[1].update(p_.data_ptr() for p_ in out_ps)
+        # nothing reads the gradients before the pass ends: AccumulateGrad steals them (no .grad yet, no second node to add them to)
+        # and no hook sees them
+        unread = first and all(p_.grad is None and not p_._backward_hooks and not p_._post_accumulate_grad_hooks for p_ in out_ps)
         views = cfg.get('grad_views')
-        direct = bool(views) and all(p_.grad is None for p_ in params)
+        direct = bool(views) and unread
         grads = [None] * (14 + 3 * nl)
         if want:
             for i, (p_, l) in enumerate(zip(params, live_h + live_k)):
@@ -335,8 +353,10 @@ class HeadPhaseFn(torch.autograd.Function):
                 d.head_grads[i] = ptr(grads[i])
             for l in range(nl):
                 d.kan_dw[l], d.kan_dlw[l], d.kan_dlb[l] = (ptr(grads[14 + 3 * l + q]) for q in range(3))
-        side = HeadPhaseFn.param_grad_stream(dev) if (want and cfg.get('dw_side_stream', True)) else None
+        side = HeadPhaseFn.param_grad_stream(dev) if (want and unread and cfg.get('dw_side_stream', True)) else None
         d.want_param_grads = int(want and side is None)
+        if not first:                  # autograd adds this node's gradients to an earlier node's, which may still be on the side stream
+            HeadPhaseFn.wait_param_grads(dev, torch.cuda.current_stream(dev))
         call('rovit_head_phase_bwd', C.byref(d), stream_ptr())
         if side is not None:
             # The parameter gradients are sample sums nobody waits for before the optimizer (or the data-parallel bucket): their launch

@@ -9,8 +9,9 @@ Every parameter is re-homed into a flat fp32 buffer (each nn.Parameter keeps its
   starting on a 16-byte boundary (the head / KAN kernels read them with 16-byte loads and check the alignment; the
   padding floats stay zero in the parameter, gradient and moment buffers, so norms and AdamW are unchanged); their
   gradients (separate autograd tensors) are packed by one multi-tensor copy per step.
-The whole step is then: squared norms (rovit_sq_norm_accum per buffer) -> clip coefficient on the device
-(rovit_clip_coef) -> fused clip-scale + decoupled weight decay + Adam (rovit_adamw_flat per buffer / active segment).
+The whole step is then: squared norm and clip coefficient on the device in one launch (rovit_sq_norm_clip over up to four
+gradient runs; with more disjoint runs one rovit_sq_norm_accum per run + rovit_clip_coef; block partials summed in a fixed order
+either way, so the norm is bit-reproducible) -> fused clip-scale + decoupled weight decay + Adam (rovit_adamw_flat_multi).
 A module whose parameters received no gradient this step (curriculum stage gating) is skipped entirely, like
 torch.optim.AdamW skips parameters with ``grad is None``; its bias-correction step count does not advance.
 
@@ -118,6 +119,9 @@ class RoViTAdamW(torch.optim.Optimizer):
         self._sq = torch.zeros((), dtype=torch.float32, device=dev)
         # ticket + fixed-order block partials of rovit_sq_norm_clip (one per 4096 gradient floats; bit-reproducible norm)
         self._sq_scratch = torch.zeros(16 + (self._bb_total + 4095) // 4096 + (self._o_total + 4095) // 4096 + 8, dtype=torch.float32, device=dev)
+        # ticket + block partials of rovit_sq_norm_accum (at most 512 blocks), for the many-run branch of step(); not shared with
+        # _sq_scratch, whose ticket and partial count rovit_sq_norm_clip owns
+        self._accum_scratch = torch.zeros(8 + 512, dtype=torch.float32, device=dev)
         self._coef = torch.ones((), dtype=torch.float32, device=dev)
         self._norm = torch.zeros((), dtype=torch.float32, device=dev)
         self.engine._prep_key = None
@@ -213,10 +217,10 @@ class RoViTAdamW(torch.optim.Optimizer):
                 cnt = (C.c_size_t * len(bufs))(*[n for _, n in bufs])
                 call('rovit_sq_norm_clip', arr, cnt, len(bufs), float(self.max_grad_norm), ptr(self._coef), ptr(self._norm),
                      ptr(self._sq_scratch), self._sq_scratch.numel(), sp)
-            elif bufs:                                    # many disjoint runs (a model with many gated modules): one launch per run
-                self._sq.zero_()
+            elif bufs:                                    # many disjoint runs (a model with many gated modules): one launch per run,
+                self._sq.zero_()                          # each adding its fixed-order block sum to the norm in run order (bit-reproducible)
                 for b, n in bufs:
-                    call('rovit_sq_norm_accum', ptr(b), n, ptr(self._sq), None, sp)
+                    call('rovit_sq_norm_accum', ptr(b), n, ptr(self._sq), ptr(self._accum_scratch), sp)
                 call('rovit_clip_coef', ptr(self._sq), float(self.max_grad_norm), ptr(self._coef), ptr(self._norm), sp)
             if bufs:
                 self.last_grad_norm = self._norm

@@ -206,10 +206,21 @@ def test_training_step_uses_the_fused_phase_and_writes_gradients_into_the_optimi
     x = torch.randn(4, 3, 224, 224, device=dev())
     y = torch.randint(0, 4, (4,), device=dev())
     views = m._head_grad_views
-    loss_fn(m(x), y, y, 4)['total_loss'].backward()
+    out = m(x)
+    loss_fn(out, y, y, 4)['total_loss'].backward()
     others = [p for n, p in m.named_parameters() if not n.startswith('backbone.')]
     assert len(others) == 23 and all(p.grad is not None and p.grad.data_ptr() == views[p.data_ptr()].data_ptr() for p in others)
     g1 = [p.grad.clone() for p in others]
+    # fp64 oracle of the heads / KAN at the features the backbone produced
+    names = [n for n, p in m.named_parameters() if not n.startswith('backbone.')]
+    sd = {k: v.detach().cpu().double() for k, v in m.state_dict().items() if not k.startswith('backbone.')}
+    for n in names:
+        sd[n].requires_grad_(True)
+    ref = _oracle(out['features'].detach().cpu().double(), sd, 4)
+    ref['kan_severity'] = ref.pop('kan')
+    ref_cpu.joint_loss(ref, y.cpu(), y.cpu(), 4)['total_loss'].backward()
+    for n, g in zip(names, g1):
+        assert float((g.cpu().double() - sd[n].grad).abs().max()) <= 1e-4 * float(sd[n].grad.abs().max()), n
     loss_fn(m(x), y, y, 4)['total_loss'].backward()                     # accumulation: not the direct path, grads double
     for p, g in zip(others, g1):
         assert float((p.grad - 2 * g).abs().max()) <= 1e-5 * float(g.abs().max()) + 1e-9
