@@ -205,6 +205,26 @@ int rovit_vit_forward_rollout(const float* images, const float* const* params, c
  * clamped: cv2.resize INTER_LINEAR / F.interpolate align_corners=False) to 224x224, then (m - min) / (max - min + 1e-8) per
  * image.  map224 fp32 (B,224,224). */
 int rovit_rollout_map(const float* rollout, float* map224, int batch, rovit_stream_t stream);
+/* Grad-CAM++ at blocks[depth-1].norm1 (explainability/gradcam.py:34-104, GradCAMPlusPlus.compute), batched, bf16 engine, eval
+ * semantics (no dropout).  Workspace: rovit_vit_gradcam_workspace_bytes(batch, depth) bytes (the inference workspace plus the last
+ * block's class-token backward temporaries; 0 for a bad batch / depth).  rovit_vit_forward_gradcam = the inference forward, keeping
+ * what the last block's class-token backward reads. */
+size_t rovit_vit_gradcam_workspace_bytes(int batch, int depth);
+int rovit_vit_forward_gradcam(const float* images, const float* const* params, const void* prep, void* workspace, float* features,
+                              int batch, int depth, rovit_stream_t stream);
+/* ... then, on the same workspace and features: the classification head (head_w1 (hidden,192), head_b1, head_w2 (classes,hidden),
+ * head_b2; fp32; hidden and classes in [1, 2048]) -> logits fp32 (B,classes); the target of image b is targets[b] (int32; NULL: the
+ * first argmax of its logits), written to chosen (int32 (B), may be NULL); an out-of-range target gives a NaN cam for that image.
+ * With a = the norm1 output and g = d logits[b, c_b] / d a: cam fp32 (B,196) = relu(w[n] * sum_d a[n,d]) for the 196 patch tokens,
+ * w[n] = sum_d g^2 / (2 g^2 + sum_n' a g^3) * relu(g).  act / grad: fp32 (B,197,192) copies of a and g, each may be NULL.
+ * Writes no parameter gradient and leaves the backward's stream state alone; may run more than once on one forward. */
+int rovit_vit_gradcam(const float* const* params, const void* prep, void* workspace, const float* features, const float* head_w1,
+                      const float* head_b1, const float* head_w2, const float* head_b2, int hidden, int classes, const int* targets,
+                      float* logits, int* chosen, float* cam, float* act, float* grad, int batch, int depth, rovit_stream_t stream);
+/* the reference's map from a raw cam (gradcam.py:89-101): bilinear 14x14 -> 224x224 as rovit_rollout_map, then (m - min) / (max - min)
+ * when max > 0 -- no epsilon: an all-equal positive map gives 0/0 = NaN, as the reference's numpy division does -- else m unchanged.
+ * map224 fp32 (B,224,224). */
+int rovit_gradcam_map(const float* cam, float* map224, int batch, rovit_stream_t stream);
 /* images: the batch the forward ran on (read by the patch-embedding weight gradient, which gathers its pixels from it:
  * there is no im2col buffer); may be NULL for ranges with last_block > 0. */
 int rovit_vit_backward(const float* images, const float* d_features, const float* const* params, const void* prep, void* workspace,

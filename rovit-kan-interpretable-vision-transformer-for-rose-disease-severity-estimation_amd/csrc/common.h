@@ -67,6 +67,7 @@ enum RovitKnob {
   ROVIT_KNOB_TAIL_WAVES = 18,    // waves per workgroup of the forward block tail: 8 (two row tiles per wave) or 16 (one; four waves per SIMD)
   ROVIT_KNOB_FWD_STAGGER = 19,   // 1: the forward's second half-batch starts one attention launch behind the first
   ROVIT_KNOB_ATTN_FWD3 = 20,     // 1: attention forward with three workgroups per CU (attn_fwd3_kernel)
+  ROVIT_KNOB_GRADCAM_RECOMPUTE = 21, // 1: Grad-CAM++'s second pass recomputes g = dqkv . Wqkv instead of reading the fp32 scratch (gradcam.hip)
   ROVIT_KNOB_SKIP_WGRAD_REDUCE = 14,  // 1: the slab-reduce / affine-finalize launches are not issued (gradients WRONG): upper bound of what folding them away could gain
   ROVIT_KNOB_COUNT = 32
 };
@@ -211,6 +212,15 @@ int rovit_cls_norm_affine_grad(const float* dfeat, const float* xhat, float* dga
 // rollout.hip: one block's attention-rollout update of v (B,197) from its saved qkv (first: v is e_0); partial: fp32 scratch of
 // batch x 13 x 197 floats.  Two launches (per-row-slice partials, fixed-order combine).
 int rovit_rollout_step(const void* qkv, float* v, float* partial, int head_fusion, int batch, int first, rovit_stream_t stream);
+// gradcam.hip (rovit_vit_gradcam in vit.hip): the head seed -- classification head, target (targets NULL: first argmax), d_features -- plus
+// the bf16 transposed copy wt (192, 576) of the unfolded qkv weight; then g = dqkv . Wqkv, S, w and the raw relu'd cam (B,196) in two
+// launches.  g: fp32 scratch (B*197, 192); spart: fp64 scratch (B, ROVIT_GRADCAM_SPLITS, 192); act / grad: optional (B,197,192) taps.
+constexpr int ROVIT_GRADCAM_SPLITS = 13, ROVIT_GRADCAM_MAX_HIDDEN = 2048, ROVIT_GRADCAM_MAX_CLASSES = 2048;
+int rovit_gradcam_seed(const float* feat, const float* w1, const float* b1, const float* w2, const float* b2, int hidden, int classes,
+                       const int* targets, float* logits, int* chosen, float* dfeat, const float* wqkv, void* wt, int batch,
+                       rovit_stream_t stream);
+int rovit_gradcam_cam(const void* dqkv, const void* wt, const void* xhat1, const float* gamma, const float* beta, float* g, double* spart,
+                      float* act, float* grad, float* cam, int batch, rovit_stream_t stream);
 // cls_tail.hip: the last block's post-attention half + the final norm on the class-token rows in one launch
 int rovit_cls_tail_fwd(const void* o, float* X, const void* wproj, const float* bproj, const void* wfc1, const float* bfc1, const void* wfc2,
                        const float* bfc2, const float* gamma, const float* beta, void* xhat2, float* rstd2, void* act, void* dact, float* feat,

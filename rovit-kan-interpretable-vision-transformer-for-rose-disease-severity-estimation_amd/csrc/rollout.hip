@@ -25,6 +25,7 @@
 // of F.interpolate(mode='bilinear', align_corners=False), which is what cv2.resize INTER_LINEAR does on a float image), then
 // (m - min) / (max - min + 1e-8) over the image.  Two passes over the 50176 outputs (min/max, then write); no intermediate buffer.
 #include "common.h"
+#include "map224.h"
 
 namespace {
 
@@ -140,20 +141,6 @@ __global__ __launch_bounds__(256) void rollout_combine_kernel(const float* __res
   float s = 0.f;
   for (int k = 0; k < splits; ++k) s += p[(size_t)k * RT];
   v[(size_t)b * RT + j] = s;
-}
-
-constexpr int GRID = 14, MAP = 224;
-
-// F.interpolate(bilinear, align_corners=False) on a 14x14 grid, output pixel (y, x)
-__device__ __forceinline__ float bilinear14(const float* g, int y, int x) {
-  const float sc = (float)GRID / MAP;
-  const float sy = fmaxf(sc * (y + 0.5f) - 0.5f, 0.f), sx = fmaxf(sc * (x + 0.5f) - 0.5f, 0.f);
-  const int y0 = (int)sy, x0 = (int)sx;
-  const int yp = y0 < GRID - 1 ? 1 : 0, xp = x0 < GRID - 1 ? 1 : 0;
-  const float ly1 = sy - y0, ly0 = 1.f - ly1, lx1 = sx - x0, lx0 = 1.f - lx1;
-  const float* r0 = g + y0 * GRID + x0;
-  const float* r1 = r0 + yp * GRID;
-  return ly0 * (lx0 * r0[0] + lx1 * r0[xp]) + ly1 * (lx0 * r1[0] + lx1 * r1[xp]);
 }
 
 __global__ __launch_bounds__(256) void rollout_map_kernel(const float* __restrict__ rollout, float* __restrict__ map) {

@@ -124,6 +124,30 @@ struct Plan {          // byte offsets into the workspace
   }
 };
 
+// Grad-CAM++ workspace (rovit_vit_forward_gradcam / rovit_vit_gradcam): the inference plan, whose one shared block buffer holds the last
+// block's xhat1 / qkv / o / lse at the end of the forward (and, in this mode, its class-token xhat2 / rstd2 / act / dact), plus what the
+// last block's class-token backward and the CAM need.  Buffers that are dead by then are reused: the gradients entering the block and
+// the mid-block one (class-token rows; never read here) go into the fp32 residual stream X, whose 4 bytes per element hold both bf16
+// buffers; dpre and then dqkv into the act slot, which nothing reads after the forward.  Nothing the backward reads is overwritten,
+// so rovit_vit_gradcam may run more than once on one forward.
+struct GradcamPlan {
+  Plan L;
+  size_t xin, xmid, dpre, dqkv;        // aliases (see above)
+  size_t dO, g, wt, dfeat, spart, total;
+  GradcamPlan(int batch, int depth) : L(batch, depth, 0) {
+    const size_t M = L.M;
+    xin = L.X; xmid = L.X + M * D * 2;
+    dpre = dqkv = L.blk0 + L.act;
+    size_t o = L.total;
+    dO = o; o = al(o + M * D * 2);
+    g = o; o = al(o + M * D * 4);
+    wt = o; o = al(o + (size_t)3 * D * D * 2);
+    dfeat = o; o = al(o + (size_t)batch * D * 4);
+    spart = o; o = al(o + (size_t)batch * ROVIT_GRADCAM_SPLITS * D * 8);
+    total = o;
+  }
+};
+
 #define RUN(call) do { int rc__ = (call); if (rc__ != ROVIT_OK) return rc__; } while (0)
 
 // ---- second stream for the weight-gradient kernels of the backward pass -------------------------------------
@@ -198,6 +222,9 @@ hipStream_t rovit_side_stream_handle() {
 
 extern "C" size_t rovit_vit_prep_bytes(int depth) { return Prep(depth).total; }
 extern "C" size_t rovit_vit_workspace_bytes(int batch, int depth, int training) { return Plan(batch, depth, training).total; }
+extern "C" size_t rovit_vit_gradcam_workspace_bytes(int batch, int depth) {
+  return batch > 0 && depth > 0 && depth <= 64 ? GradcamPlan(batch, depth).total : 0;
+}
 extern "C" int rovit_vit_num_params(int depth) { return P_BLOCK0 + B_COUNT * depth; }
 
 extern "C" int rovit_vit_workspace_field(int batch, int depth, int field, int block, size_t* offset, size_t* bytes) {
@@ -260,7 +287,7 @@ namespace {
 // prepare: 0 = the weights in `prep` are current; 1 = prepare them from `params` first; 2 = ... and write the constant tables too
 int vit_forward_impl(const float* images, const float* const* params, const void* prep, void* workspace, float* features,
                      void* const* attn_taps, float* const* prob_taps, int batch, int depth, int training, int mlp_path,
-                     rovit_stream_t stream, int prepare = 0, float* rollout = nullptr, int head_fusion = 0) {
+                     rovit_stream_t stream, int prepare = 0, float* rollout = nullptr, int head_fusion = 0, bool gradcam = false) {
   ROVIT_CHECK_ARG(images && features, ROVIT_ERR_NULL, "vit_forward: null images/features");
   RUN(check_common(params, prep, workspace, batch, depth, mlp_path));
   const Prep P(depth);
@@ -363,10 +390,12 @@ int vit_forward_impl(const float* images, const float* const* params, const void
     if (cls_only && cls_fused) {
       EACH_HALF {
         const Half& h = halves[hh];
+        // (training, and the Grad-CAM++ forward: keep what the class-token backward reads)
+        const bool keep = training || gradcam;
         RUN(rovit_cls_tail_fwd(ROWS(s + L.o, D, 2), X + (size_t)h.b0 * T * D, q + P.wproj, bp[B_PROJB], q + P.wfc1, (const float*)(q + P.bfc1),
-                               q + P.wfc2, bp[B_FC2B], params[P_NORM_W], params[P_NORM_B], training ? ROWS(s + L.xhat2, D, 2) : nullptr,
-                               training ? (float*)ROWS(s + L.rstd2, 1, 4) : nullptr, training ? ROWS(s + L.act, MLP, 2) : nullptr,
-                               training ? ROWS(s + L.dact, MLP, 2) : nullptr, features + (size_t)h.b0 * D,
+                               q + P.wfc2, bp[B_FC2B], params[P_NORM_W], params[P_NORM_B], keep ? ROWS(s + L.xhat2, D, 2) : nullptr,
+                               keep ? (float*)ROWS(s + L.rstd2, 1, 4) : nullptr, keep ? ROWS(s + L.act, MLP, 2) : nullptr,
+                               keep ? ROWS(s + L.dact, MLP, 2) : nullptr, features + (size_t)h.b0 * D,
                                (float*)(ws + L.xhat_cls) + (size_t)h.b0 * D, (float*)(ws + L.rstd_cls) + h.b0, h.nb, T, eps, h.st));
       }
       continue;
@@ -468,6 +497,49 @@ extern "C" int rovit_vit_forward_rollout(const float* images, const float* const
                   head_fusion);
   return vit_forward_impl(images, params, prep, workspace, features, nullptr, nullptr, batch, depth, 0, ROVIT_MLP_AUTO, stream, 0, rollout,
                           head_fusion);
+}
+
+// Same forward as rovit_vit_forward's inference mode (blocks 0..depth-2 and the last block's attention identical; workspace of
+// rovit_vit_gradcam_workspace_bytes), except that the last block's class-token tail also keeps xhat2 / rstd2 / act / gelu' for
+// rovit_vit_gradcam, as the training forward does.
+extern "C" int rovit_vit_forward_gradcam(const float* images, const float* const* params, const void* prep, void* workspace,
+                                         float* features, int batch, int depth, rovit_stream_t stream) {
+  return vit_forward_impl(images, params, prep, workspace, features, nullptr, nullptr, batch, depth, 0, ROVIT_MLP_AUTO, stream, 0, nullptr, 0,
+                          true);
+}
+
+// Grad-CAM++ at blocks[depth-1].norm1 (explainability/gradcam.py:34-104) for every image of the forward above: the head seed, the
+// last block's class-token backward down to dqkv -- no norm1 backward, no weight gradient, no side stream: the backward's stream
+// state is not touched -- and the CAM (gradcam.hip).  All on `stream`, no host synchronisation.
+extern "C" int rovit_vit_gradcam(const float* const* params, const void* prep, void* workspace, const float* features, const float* head_w1,
+                                 const float* head_b1, const float* head_w2, const float* head_b2, int hidden, int classes, const int* targets,
+                                 float* logits, int* chosen, float* cam, float* act, float* grad, int batch, int depth, rovit_stream_t stream) {
+  RUN(check_common(params, prep, workspace, batch, depth));
+  ROVIT_CHECK_ARG(features && head_w1 && head_b1 && head_w2 && head_b2 && logits && cam, ROVIT_ERR_NULL,
+                  "vit_gradcam: null features / head parameter / logits / cam");
+  ROVIT_CHECK_ARG(hidden > 0 && hidden <= ROVIT_GRADCAM_MAX_HIDDEN, ROVIT_ERR_SHAPE, "vit_gradcam: hidden must be in [1, %d], got %d",
+                  ROVIT_GRADCAM_MAX_HIDDEN, hidden);
+  ROVIT_CHECK_ARG(classes > 0 && classes <= ROVIT_GRADCAM_MAX_CLASSES, ROVIT_ERR_SHAPE, "vit_gradcam: classes must be in [1, %d], got %d",
+                  ROVIT_GRADCAM_MAX_CLASSES, classes);
+  const int i = depth - 1;
+  const float* const* bp = params + P_BLOCK0 + B_COUNT * i;
+  ROVIT_CHECK_ARG(params[P_NORM_W] && bp[B_N1W] && bp[B_N1B] && bp[B_QKVW], ROVIT_ERR_NULL, "vit_gradcam: null backbone parameter");
+  const Prep P(depth);
+  const GradcamPlan G(batch, depth);
+  const Plan& L = G.L;
+  const char* q = (const char*)prep + P.blk0 + (size_t)i * P.blk_stride;
+  char* ws = (char*)workspace;
+  char* s = ws + L.blk0;
+  float* dfeat = (float*)(ws + G.dfeat);
+  RUN(rovit_gradcam_seed(features, head_w1, head_b1, head_w2, head_b2, hidden, classes, targets, logits, chosen, dfeat, bp[B_QKVW],
+                         ws + G.wt, batch, stream));
+  // the final-norm backward and the class-token tail (cls_tail.hip), then the rank-one attention backward: dqkv of every token
+  RUN(rovit_cls_tail_bwd(dfeat, (const float*)(ws + L.xhat_cls), (const float*)(ws + L.rstd_cls), params[P_NORM_W], q + P.wfc2, q + P.wfc1,
+                         q + P.wproj, s + L.dact, s + L.xhat2, (const float*)(s + L.rstd2), ws + G.xin, ws + G.dpre, ws + G.xmid, ws + G.dO,
+                         batch, T, stream));
+  RUN(rovit_attention_cls_bwd(s + L.qkv, s + L.o, (const float*)(s + L.lse), ws + G.dO, ws + G.dqkv, batch, T, H, D / H, 0.125f, stream));
+  return rovit_gradcam_cam(ws + G.dqkv, ws + G.wt, s + L.xhat1, bp[B_N1W], bp[B_N1B], (float*)(ws + G.g), (double*)(ws + G.spart), act, grad,
+                           cam, batch, stream);
 }
 
 // Backward over blocks first_block, first_block-1, ..., last_block (inclusive).  first_block == depth-1 also

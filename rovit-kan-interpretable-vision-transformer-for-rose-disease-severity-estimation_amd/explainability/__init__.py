@@ -1,2 +1,3 @@
-"""Drop-in for the reference's ``explainability`` package: attention rollout computed on the GPU."""
+"""Drop-in for the reference's ``explainability`` package: attention rollout and Grad-CAM++ computed on the GPU."""
 from .attention_maps import ViTAttentionRollout  # noqa: F401
+from .gradcam import GradCAMPlusPlus  # noqa: F401

@@ -496,6 +496,15 @@ class VitEngine:
         if len(pool) < 2:
             pool.append(ws)
 
+    def take_gradcam_ws(self, batch: int, dev) -> torch.Tensor:
+        """Workspace of rovit_vit_forward_gradcam / rovit_vit_gradcam (the inference plan plus the last block's backward temporaries),
+        pooled like the others; give it back with give_ws(batch, 'gradcam', ws)."""
+        pool = self._ws_pool.setdefault((batch, 'gradcam', str(dev)), [])
+        if pool:
+            return pool.pop()
+        nbytes = native.load().rovit_vit_gradcam_workspace_bytes(batch, self.depth)
+        return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
     # -- flat gradients -----------------------------------------------------------------------
     def ensure_grads(self, params: Sequence[torch.Tensor]):
         dev = params[0].device

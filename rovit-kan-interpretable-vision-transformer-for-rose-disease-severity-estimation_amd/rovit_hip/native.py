@@ -15,7 +15,7 @@ _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get('ROVIT_HIP_LIB') or os.path.join(_PKG_ROOT, 'lib', 'librovit_hip.so')   # env override: developer A/B builds
 
 _lib: Optional[C.CDLL] = None
-ABI_VERSION = 420          # rovit_version() this binding matches (csrc/api.hip)
+ABI_VERSION = 430          # rovit_version() this binding matches (csrc/api.hip)
 
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 
@@ -56,6 +56,10 @@ SIGNATURES = {
     'rovit_vit_forward_taps': (_i, [_vp] * 7 + [_i, _i, _vp]),
     'rovit_vit_forward_rollout': (_i, [_vp] * 6 + [_i, _i, _i, _vp]),
     'rovit_rollout_map': (_i, [_vp, _vp, _i, _vp]),
+    'rovit_vit_gradcam_workspace_bytes': (_sz, [_i, _i]),
+    'rovit_vit_forward_gradcam': (_i, [_vp] * 5 + [_i, _i, _vp]),
+    'rovit_vit_gradcam': (_i, [_vp] * 8 + [_i, _i] + [_vp] * 6 + [_i, _i, _vp]),
+    'rovit_gradcam_map': (_i, [_vp, _vp, _i, _vp]),
     'rovit_attention_probs': (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp]),
     'rovit_vit_backward': (_i, [_vp] * 6 + [_i] * 5 + [_vp]),
     'rovit_vit_backward_notify': (_i, [_vp] * 6 + [_i] * 5 + [_vp] + [_vp]),
