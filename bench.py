@@ -6,9 +6,14 @@
         bench.py --gpus N --steps K --warmup W
 
 Prints ONE JSON line on rank 0.  `value` = whole-job images/sec (inputs resident in HBM before the timed region).
-`roofline` is measured live (device events on the launch stream) for the dominant kernel class, the bf16 MFMA GEMM
-of the attention/MLP linears; `cpu_baseline` times the CPU oracle (a port of the reference's algorithm) on a
-bounded sample on this box's host cores, rank 0 at N=1 only.
+A plain run sets up, warms up, times the steps, writes --dump-outputs if given and prints that line, nothing more.
+
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
+
+adds everything else the benchmark measures, after the timed steps (about a minute more at N=1): `roofline*` are
+measured live (device events on the launch stream) for the step's kernel classes, `fp32_mode` and `backbone_only`
+time other precisions and configurations, `cpu_baseline` times the CPU oracle (a port of the reference's algorithm)
+on a bounded sample on the host's cores (rank 0 at N=1 only), and at N>1 `config.allreduce` reports the exchange.
 """
 import argparse
 import json
@@ -761,9 +766,12 @@ def main():
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--batch', type=int, default=256)
     ap.add_argument('--buckets', type=int, default=2)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also run what the headline figure does not need: the roofline, fp32-mode and '
+                         'backbone-only sections and the CPU baseline at N=1, the all-reduce report at N>1 (off by default)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--no-roofline', action='store_true',
-                    help='time the step only (the command profiles/r03_bench_kernel_stats.csv is taken from: its kernel times sum to the step)')
+                    help='with --full: skip the roofline, fp32-mode and backbone-only sections (a plain run skips them too)')
     ap.add_argument('--roofline-only', action='store_true',
                     help='run only the roofline kernel measurements (the command profiles/r02_roofline_kernel_stats.csv and the PMC passes are taken from)')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
@@ -849,7 +857,7 @@ def main():
     rccl_world = dist.get_world_size() if dist.is_initialized() else 0
     if world > 1 and rccl_world != args.gpus:
         _fail(f'the RCCL group has {rccl_world} ranks, --gpus says {args.gpus}')
-    comm = _comm_report(sync, dev, step) if (world > 1 or force_dist) else None
+    comm = _comm_report(sync, dev, step) if args.full and (world > 1 or force_dist) else None
 
     if rank == 0:
         ips = world * args.batch * args.steps / dt
@@ -866,15 +874,16 @@ def main():
                        'backbone_mfma_frac_of_step': round(ips / world * TRAIN_FLOP_PER_IMG / 1e12 / MFMA_BF16_PEAK_TFLOPS, 4)},
             'final_loss': round(final_loss, 5),
         }
+        if world > 1 or force_dist:
+            res['config']['allreduce_op'] = sync.reducer.op_name
         if comm is not None:
             res['config']['allreduce'] = comm
-            res['config']['allreduce_op'] = sync.reducer.op_name
     if world > 1 or force_dist:
         dist.barrier()
         dist.destroy_process_group()       # the other ranks are done: rank 0 measures its kernels alone
     if rank == 0:
         # N > 1 lines carry the step and the exchange only (the kernels are the same as at N = 1; eight-rank runs stay short)
-        if not args.no_roofline and world == 1:
+        if args.full and not args.no_roofline and world == 1:
             res['roofline'] = wgrad_roofline(dev)
             res['roofline_attn'] = attn_roofline(dev)
             res['roofline_mlp'] = mlp_roofline(dev)
@@ -888,7 +897,7 @@ def main():
             # handle 256 images; their HBM-roofline time on algorithmic bytes against their measured time
             res['config']['attention_half_us_per_block'] = round(attn_us, 1)
             res['config']['attention_half_frac_of_hbm_roofline'] = round(attn_floor_us / attn_us, 4)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res['cpu_baseline'] = cpu_baseline()
         print(json.dumps(res), flush=True)
 
