@@ -163,6 +163,33 @@ int rovit_head_phase_bwd(const rovit_head_phase* p, rovit_stream_t stream);
 int rovit_head_phase_bwd_params(const rovit_head_phase* p, rovit_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Monte-Carlo dropout over the heads in ONE launch (csrc/mc_dropout.hip): what the reference's recipe -- the
+ * heads' nn.Dropout modules in training mode (experiments/baselines.py:48-52), T forwards -- gives, from the
+ * backbone features of ONE forward (DeiT-Tiny has no dropout).  Per image: each active head's relu(fc1(x))
+ * once; per sample t < num_samples the masks (Philox4x32-10, key = seed, counter (image * hid + unit, t,
+ * offset lo, offset hi), words x / y / z -> heads 0 / 1 / 2, kept iff (word >> 8) * 2^-24 < 1 - drop_p, kept
+ * units scaled by 1 / (1 - drop_p): sample 0 is rovit_head_phase_fwd's draw), the output linears (log_var
+ * clamped to +-10), and the per-image statistics over the samples (variances divided by T).
+ *   Limits: those of rovit_head_phase (embed <= 768, hid <= 256, both multiples of 4; 2 <= num_classes <= 8)
+ *   and 1 <= num_samples <= 4096.  Outputs (fp32, device): class_probs / class_probs_std (B, C), pred_entropy /
+ *   exp_entropy / mutual_info (B); stage >= 2: ord_probs (B, C), ord_severity / ord_severity_std (B); stage
+ *   >= 3: unc_mu, epistemic_var (variance of mu), aleatoric_var (mean of exp(log_var)), unc_std (B).
+ *   s_cls (T, B, C), s_ord (T, B, C - 1), s_mu / s_lv (T, B): optional per-sample outputs (NULL: not written).
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct rovit_head_mc {
+  int batch, embed, hid, num_classes, stage, num_samples;
+  float drop_p;
+  unsigned long long seed, offset;
+  const float* features;          /* (B, embed) */
+  const float* head_params[14];   /* order of rovit_heads_fwd */
+  float* class_probs; float* class_probs_std; float* pred_entropy; float* exp_entropy; float* mutual_info;
+  float* ord_probs; float* ord_severity; float* ord_severity_std;
+  float* unc_mu; float* epistemic_var; float* aleatoric_var; float* unc_std;
+  float* s_cls; float* s_ord; float* s_mu; float* s_lv;
+} rovit_head_mc;
+int rovit_head_mc_fwd(const rovit_head_mc* p, rovit_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * DeiT-Tiny backbone (models/backbone.py:23-25 -> timm VisionTransformer.forward).
  * params / grads: HOST arrays of rovit_vit_num_params(depth) device pointers (fp32, timm layouts):
  *   [0] cls_token (192) [1] pos_embed (197,192) [2] patch_embed.proj.weight (192,768) [3] .bias [4] norm.weight

@@ -18,7 +18,8 @@ void rovit_set_error(const char* fmt, ...) {
 // 410: round 4 -- rovit_joint_loss takes int64 severity labels (severity_is_int64); rovit_head_phase_*, rovit_sq_norm_clip, rovit_adamw_flat_multi added.
 // 420: rovit_vit_forward_rollout and rovit_rollout_map added (attention rollout, rollout.hip).
 // 430: rovit_vit_gradcam_workspace_bytes, rovit_vit_forward_gradcam, rovit_vit_gradcam and rovit_gradcam_map added (Grad-CAM++, gradcam.hip).
-extern "C" int rovit_version(void) { return 430; }
+// 440: rovit_head_mc_fwd added (Monte-Carlo dropout over the heads, mc_dropout.hip).
+extern "C" int rovit_version(void) { return 440; }
 extern "C" const char* rovit_last_error_string(void) { return g_err; }
 
 #include <mutex>

@@ -10,6 +10,13 @@ from rovit_hip.functions import MLPHeadFn
 LIN_CLAMP10 = 2
 
 
+def dropout_active(drop: nn.Dropout) -> bool:
+    """A head's dropout is applied iff ITS nn.Dropout module is in training mode with p > 0 -- the flag torch.nn.Dropout itself
+    obeys, so the reference's MC-dropout recipe (eval(), then the Dropout modules back to train()) works.  Under plain
+    model.train() / model.eval() this is the model's own flag."""
+    return drop.training and drop.p > 0.0
+
+
 def dropout_mask(drop: nn.Dropout, training: bool, shape, device) -> Optional[torch.Tensor]:
     """Scaled keep-mask for the fused Linear+ReLU+Dropout kernel (None in eval mode / p == 0)."""
     if not training or drop.p <= 0.0:
@@ -20,7 +27,7 @@ def dropout_mask(drop: nn.Dropout, training: bool, shape, device) -> Optional[to
 
 class _Head(nn.Module):
     def _hidden_mask(self, x):
-        return dropout_mask(self.dropout, self.training, (x.shape[0], self.fc1.out_features), x.device)
+        return dropout_mask(self.dropout, self.dropout.training, (x.shape[0], self.fc1.out_features), x.device)
 
 
 class ClassificationHead(_Head):

@@ -9,7 +9,7 @@ import torch.nn as nn
 from rovit_hip.functions import ACT_RELU, ACT_SIGMOID3, HeadPhaseFn, HeadsFn
 
 from .backbone import DeiTTinyBackbone
-from .heads import ClassificationHead, OrdinalHead, UncertaintyHead, dropout_mask
+from .heads import ClassificationHead, OrdinalHead, UncertaintyHead, dropout_active, dropout_mask
 from .kan import KANSeverityModule
 
 
@@ -60,9 +60,9 @@ class RoViTKAN(nn.Module):
             return self._forward_head_phase(features, stage)
         B, hid = features.shape[0], self.classification_head.fc1.out_features
         masks = None
-        if self.training:
-            heads = ((self.classification_head, 1), (self.ordinal_head, 2), (self.uncertainty_head, 3))
-            live = [stage >= need and h.dropout.p > 0.0 for h, need in heads]
+        heads = ((self.classification_head, 1), (self.ordinal_head, 2), (self.uncertainty_head, 3))
+        live = [stage >= need and dropout_active(h.dropout) for h, need in heads]      # each head's own Dropout flag
+        if any(live):
             ps = {h.dropout.p for (h, _), a in zip(heads, live) if a}
             if len(ps) == 1:                      # one random draw for all active heads (3 launches instead of 9-12)
                 keep = 1.0 - ps.pop()
@@ -103,13 +103,19 @@ class RoViTKAN(nn.Module):
             # (num_knots 5 / 6: dense basis rows; any other grid: one 16-byte load of the four live weights per (input, output) pair --
             # BASELINE configs[4], num_knots 32 at batch 512: 50 us forward against 54 for the three per-layer launches, backward 144 against 126)
             return False
-        if self.training and len({h.dropout.p for h in (c, o, u)}) != 1:
+        if len({self._drop_p(h) for h in (c, o, u)}) != 1:      # the kernel draws one p for every head, or none
             return False
         for top in (c, o, u, k):
             for m in top.modules():
                 if m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or getattr(m, '_backward_pre_hooks', None):
                     return False
         return True
+
+    @staticmethod
+    def _drop_p(head) -> float:
+        """The dropout probability a forward applies to this head's hidden layer: its Dropout's p if that module is in training
+        mode, else 0."""
+        return float(head.dropout.p) if dropout_active(head.dropout) else 0.0
 
     def _kan_params(self):
         out = []
@@ -125,8 +131,8 @@ class RoViTKAN(nn.Module):
                'kan_knots': [l.knots for l in k.kan_layers] if stage >= 4 else [],
                'kan_acts': [ACT_SIGMOID3 if i == nl - 1 else ACT_RELU for i in range(nl)],
                'grad_views': getattr(self, '_head_grad_views', None)}
-        p = self.classification_head.dropout.p
-        if self.training and p > 0.0:
+        p = self._drop_p(self.classification_head)          # every head's (_head_phase_fusable)
+        if p > 0.0:
             # dropout drawn inside the kernel (Philox keyed by the device generator's seed, counter advanced like torch's own kernels do)
             gen = torch.cuda.default_generators[features.device.index]
             n = features.shape[0] * self.classification_head.fc1.out_features
@@ -172,6 +178,26 @@ class RoViTKAN(nn.Module):
             if out['kan_severity'] is not None:
                 pred['kan_severity'] = out['kan_severity']
             return pred
+
+    def predict_mc(self, x: torch.Tensor, num_samples: int = 30, seed=None, return_samples: bool = False) -> Dict[str, torch.Tensor]:
+        """Extension (not in the reference): Monte-Carlo dropout over the heads -- one backbone forward and one launch for every
+        sample (rovit_hip.mc_dropout.mc_dropout_predict).  Unlike predict(), leaves every module's training flag as it found it."""
+        from rovit_hip import mc_dropout
+        return mc_dropout.mc_dropout_predict(self, x, num_samples, seed, return_samples)
+
+    def _head_dropouts(self):
+        return (self.classification_head.dropout, self.ordinal_head.dropout, self.uncertainty_head.dropout)
+
+    def enable_dropout(self):
+        """The interface the reference's BaselineModel declares (experiments/baselines.py:48-52, empty there), for MC dropout: the
+        three heads' Dropout modules to training mode (the only dropout with p > 0; the backbone's is 0), the rest as it is."""
+        for d in self._head_dropouts():
+            d.train()
+
+    def disable_dropout(self):
+        """BaselineModel.disable_dropout's slot (experiments/baselines.py:51-52): the heads' Dropout modules back to eval mode."""
+        for d in self._head_dropouts():
+            d.eval()
 
     def freeze_backbone(self):
         self.backbone.freeze()

@@ -15,7 +15,7 @@ _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get('ROVIT_HIP_LIB') or os.path.join(_PKG_ROOT, 'lib', 'librovit_hip.so')   # env override: developer A/B builds
 
 _lib: Optional[C.CDLL] = None
-ABI_VERSION = 430          # rovit_version() this binding matches (csrc/api.hip)
+ABI_VERSION = 440          # rovit_version() this binding matches (csrc/api.hip)
 
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 
@@ -44,6 +44,7 @@ SIGNATURES = {
     'rovit_head_phase_fwd': (_i, [_vp, _vp]),
     'rovit_head_phase_bwd': (_i, [_vp, _vp]),
     'rovit_head_phase_bwd_params': (_i, [_vp, _vp]),
+    'rovit_head_mc_fwd': (_i, [_vp, _vp]),
     'rovit_vit_num_params': (_i, [_i]),
     'rovit_vit_prep_bytes': (_sz, [_i]),
     'rovit_vit_workspace_bytes': (_sz, [_i, _i, _i]),
@@ -114,6 +115,16 @@ class HeadPhase(C.Structure):
                 ('g_cls', _vp), ('g_ord', _vp), ('g_mu', _vp), ('g_lv', _vp), ('g_kan', _vp),
                 ('d_features', _vp), ('dpre', _vp), ('kan_gz', _vp * 4), ('head_grads', _vp * 14), ('kan_dw', _vp * 4),
                 ('kan_dlw', _vp * 4), ('kan_dlb', _vp * 4), ('want_param_grads', _i)]
+
+
+class HeadMC(C.Structure):
+    """``rovit_head_mc`` of include/rovit_hip.h, field for field."""
+    _fields_ = [('batch', _i), ('embed', _i), ('hid', _i), ('num_classes', _i), ('stage', _i), ('num_samples', _i), ('drop_p', _f),
+                ('seed', C.c_ulonglong), ('offset', C.c_ulonglong), ('features', _vp), ('head_params', _vp * 14),
+                ('class_probs', _vp), ('class_probs_std', _vp), ('pred_entropy', _vp), ('exp_entropy', _vp), ('mutual_info', _vp),
+                ('ord_probs', _vp), ('ord_severity', _vp), ('ord_severity_std', _vp),
+                ('unc_mu', _vp), ('epistemic_var', _vp), ('aleatoric_var', _vp), ('unc_std', _vp),
+                ('s_cls', _vp), ('s_ord', _vp), ('s_mu', _vp), ('s_lv', _vp)]
 
 
 # entry points only the developer library exports (round-2 / round-3 experiments that lost; tools/ A/B them)
