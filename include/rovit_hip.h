@@ -248,6 +248,22 @@ int rovit_vit_forward_gradcam(const float* images, const float* const* params, c
 int rovit_vit_gradcam(const float* const* params, const void* prep, void* workspace, const float* features, const float* head_w1,
                       const float* head_b1, const float* head_w2, const float* head_b2, int hidden, int classes, const int* targets,
                       float* logits, int* chosen, float* cam, float* act, float* grad, int batch, int depth, rovit_stream_t stream);
+/* Grad-CAM++ of the severity and uncertainty outputs.  rovit_explain_seed: the targets' scalar per image and d target / d features,
+ * from the backbone features and the heads / KAN parameters of a rovit_head_phase descriptor (batch, embed = 192, hid, num_classes,
+ * stage, kan_*, features, head_params; the forward / backward buffers and the dropout fields are not read: eval semantics).  kinds:
+ * HOST array of n_targets (1..4) distinct ROVIT_TARGET_* other than CLASS (whose seed is rovit_vit_gradcam's), each produced at the
+ * descriptor's stage (ordinal_severity from 2, mu / log_var from 3, kan_severity at 4 with a one-output KAN stack).  Targets:
+ *   ORDINAL_SEVERITY  sum_k k P(y = k) from the cumulative sigmoids (models/heads.py:45-77); gradient -sum_k sigma'(z_k) dz_k
+ *   MU, LOG_VAR       the uncertainty head's mu, clamp(log_var, -10, 10) (gradient where -10 <= pre-clamp value <= 10)
+ *   KAN_SEVERITY      KANSeverityModule's output (models/kan.py:138-149), gradient as rovit_head_phase_bwd computes it
+ * values fp32 (n_targets, B), seeds fp32 (n_targets, B, 192).  Limits: those of rovit_head_phase.  fp32, no atomics, deterministic. */
+enum { ROVIT_TARGET_CLASS = 0, ROVIT_TARGET_ORDINAL_SEVERITY = 1, ROVIT_TARGET_MU = 2, ROVIT_TARGET_LOG_VAR = 3, ROVIT_TARGET_KAN_SEVERITY = 4 };
+int rovit_explain_seed(const rovit_head_phase* p, const int* kinds, int n_targets, float* values, float* seeds, rovit_stream_t stream);
+/* rovit_vit_gradcam with the caller's d_features (B,192) fp32 (16-byte aligned; e.g. a target's rows of rovit_explain_seed's seeds)
+ * instead of the classification head's seed: cam / act / grad as there.  Runs on the workspace of rovit_vit_forward_gradcam and may
+ * run once per target on one forward; writes no parameter gradient. */
+int rovit_vit_gradcam_seeded(const float* const* params, const void* prep, void* workspace, const float* d_features, float* cam, float* act,
+                             float* grad, int batch, int depth, rovit_stream_t stream);
 /* the reference's map from a raw cam (gradcam.py:89-101): bilinear 14x14 -> 224x224 as rovit_rollout_map, then (m - min) / (max - min)
  * when max > 0 -- no epsilon: an all-equal positive map gives 0/0 = NaN, as the reference's numpy division does -- else m unchanged.
  * map224 fp32 (B,224,224). */

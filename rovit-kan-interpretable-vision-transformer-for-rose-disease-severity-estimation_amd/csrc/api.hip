@@ -19,6 +19,8 @@ void rovit_set_error(const char* fmt, ...) {
 // 420: rovit_vit_forward_rollout and rovit_rollout_map added (attention rollout, rollout.hip).
 // 430: rovit_vit_gradcam_workspace_bytes, rovit_vit_forward_gradcam, rovit_vit_gradcam and rovit_gradcam_map added (Grad-CAM++, gradcam.hip).
 // 440: rovit_head_mc_fwd added (Monte-Carlo dropout over the heads, mc_dropout.hip).
+// (rovit_explain_seed and rovit_vit_gradcam_seeded were added at 440: new entries only, no argument list changed, and the binding
+// resolves every symbol it declares at load time.)
 extern "C" int rovit_version(void) { return 440; }
 extern "C" const char* rovit_last_error_string(void) { return g_err; }
 

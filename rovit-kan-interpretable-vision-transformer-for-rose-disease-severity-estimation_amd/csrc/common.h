@@ -221,6 +221,8 @@ int rovit_gradcam_seed(const float* feat, const float* w1, const float* b1, cons
                        rovit_stream_t stream);
 int rovit_gradcam_cam(const void* dqkv, const void* wt, const void* xhat1, const float* gamma, const float* beta, float* g, double* spart,
                       float* act, float* grad, float* cam, int batch, rovit_stream_t stream);
+// explain.hip: the same bf16 transposed qkv-weight copy on its own (rovit_vit_gradcam_seeded has no head seed to launch it beside)
+int rovit_gradcam_wt(const float* wqkv, void* wt, rovit_stream_t stream);
 // cls_tail.hip: the last block's post-attention half + the final norm on the class-token rows in one launch
 int rovit_cls_tail_fwd(const void* o, float* X, const void* wproj, const float* bproj, const void* wfc1, const float* bfc1, const void* wfc2,
                        const float* bfc2, const float* gamma, const float* beta, void* xhat2, float* rstd2, void* act, void* dact, float* feat,

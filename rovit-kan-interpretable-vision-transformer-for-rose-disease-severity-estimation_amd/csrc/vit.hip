@@ -542,6 +542,32 @@ extern "C" int rovit_vit_gradcam(const float* const* params, const void* prep, v
                            cam, batch, stream);
 }
 
+// rovit_vit_gradcam with the caller's d_features in place of the classification head's seed (explain.hip's rovit_explain_seed writes
+// those of the severity and uncertainty outputs): the bf16 transposed qkv-weight copy, the class-token backward and the CAM.  Reads
+// the forward's workspace only, so it may run once per target on one rovit_vit_forward_gradcam.
+extern "C" int rovit_vit_gradcam_seeded(const float* const* params, const void* prep, void* workspace, const float* d_features, float* cam,
+                                        float* act, float* grad, int batch, int depth, rovit_stream_t stream) {
+  RUN(check_common(params, prep, workspace, batch, depth));
+  ROVIT_CHECK_ARG(d_features && cam, ROVIT_ERR_NULL, "vit_gradcam_seeded: null d_features / cam");
+  ROVIT_CHECK_ARG(rovit_aligned16(d_features), ROVIT_ERR_ALIGN, "vit_gradcam_seeded: d_features must be 16-byte aligned");
+  const int i = depth - 1;
+  const float* const* bp = params + P_BLOCK0 + B_COUNT * i;
+  ROVIT_CHECK_ARG(params[P_NORM_W] && bp[B_N1W] && bp[B_N1B] && bp[B_QKVW], ROVIT_ERR_NULL, "vit_gradcam_seeded: null backbone parameter");
+  const Prep P(depth);
+  const GradcamPlan G(batch, depth);
+  const Plan& L = G.L;
+  const char* q = (const char*)prep + P.blk0 + (size_t)i * P.blk_stride;
+  char* ws = (char*)workspace;
+  char* s = ws + L.blk0;
+  RUN(rovit_gradcam_wt(bp[B_QKVW], ws + G.wt, stream));
+  RUN(rovit_cls_tail_bwd(d_features, (const float*)(ws + L.xhat_cls), (const float*)(ws + L.rstd_cls), params[P_NORM_W], q + P.wfc2,
+                         q + P.wfc1, q + P.wproj, s + L.dact, s + L.xhat2, (const float*)(s + L.rstd2), ws + G.xin, ws + G.dpre, ws + G.xmid,
+                         ws + G.dO, batch, T, stream));
+  RUN(rovit_attention_cls_bwd(s + L.qkv, s + L.o, (const float*)(s + L.lse), ws + G.dO, ws + G.dqkv, batch, T, H, D / H, 0.125f, stream));
+  return rovit_gradcam_cam(ws + G.dqkv, ws + G.wt, s + L.xhat1, bp[B_N1W], bp[B_N1B], (float*)(ws + G.g), (double*)(ws + G.spart), act, grad,
+                           cam, batch, stream);
+}
+
 // Backward over blocks first_block, first_block-1, ..., last_block (inclusive).  first_block == depth-1 also
 // runs the final-norm backward from d_features; last_block == 0 also produces the patch-embed / pos / cls
 // gradients.  Splitting the range lets the caller start a gradient all-reduce between calls.

@@ -20,15 +20,21 @@ class GradCAMPlusPlus:
         self.model = model
         self.device = device
 
-    def compute_batch(self, images: torch.Tensor, class_idx=None) -> torch.Tensor:
-        """(B,224,224) fp32 maps on the device, one per image; ``class_idx``: None (each image's argmax), an int or a (B,) tensor."""
+    def compute_batch(self, images: torch.Tensor, class_idx=None, target='class'):
+        """(B,224,224) fp32 maps on the device, one per image; ``class_idx``: None (each image's argmax), an int or a (B,) tensor.
+        ``target`` (extension): the output explained -- 'class', 'ordinal_severity', 'mu', 'log_var' or 'kan_severity' -- or a list of
+        them, which gives a dict name -> maps from one forward (rovit_hip.gradcam.grad_cam_pp)."""
         self.model.eval()
-        return grad_cam_pp(self.model, images.to(self.device), class_idx, upsample=True)
+        return grad_cam_pp(self.model, images.to(self.device), class_idx, upsample=True, target=target)
 
-    def compute(self, image_tensor: torch.Tensor, class_idx: int = None) -> np.ndarray:
-        """The reference's contract (gradcam.py:34-104): the (224,224) map of item 0 as numpy, for ``class_idx`` or item 0's argmax.
-        The caller's tensor is not modified (the reference sets its requires_grad; nothing here needs it)."""
-        return self.compute_batch(image_tensor, class_idx)[0].cpu().numpy()
+    def compute(self, image_tensor: torch.Tensor, class_idx: int = None, target='class'):
+        """The reference's contract (gradcam.py:34-104): the (224,224) map of item 0 as numpy, for ``class_idx`` or item 0's argmax
+        (a dict name -> map for a list of targets).  The caller's tensor is not modified (the reference sets its requires_grad; nothing
+        here needs it)."""
+        maps = self.compute_batch(image_tensor, class_idx, target)
+        if isinstance(maps, dict):
+            return {n: m[0].cpu().numpy() for n, m in maps.items()}
+        return maps[0].cpu().numpy()
 
     def overlay_on_image(self, image, cam, alpha=0.5, colormap=None):
         raise NotImplementedError(_PLOTS.format('overlay_on_image'))

@@ -212,11 +212,12 @@ class RoViTKAN(nn.Module):
         """Extension (not in the reference): DeiTTinyBackbone.attention_rollout of the backbone."""
         return self.backbone.attention_rollout(x, head_fusion, upsample)
 
-    def grad_cam_pp(self, x: torch.Tensor, class_idx=None, upsample: bool = True, return_taps: bool = False):
-        """Extension (not in the reference): Grad-CAM++ of cls_logits at blocks[-1].norm1 for every image of the batch on the GPU
+    def grad_cam_pp(self, x: torch.Tensor, class_idx=None, upsample: bool = True, return_taps: bool = False, target='class'):
+        """Extension (not in the reference): Grad-CAM++ at blocks[-1].norm1 for every image of the batch on the GPU, of cls_logits or,
+        with ``target=``, of ordinal_severity / mu / log_var / kan_severity, or of several of them from one forward
         (rovit_hip.gradcam.grad_cam_pp)."""
         from rovit_hip import gradcam
-        return gradcam.grad_cam_pp(self, x, class_idx, upsample, return_taps)
+        return gradcam.grad_cam_pp(self, x, class_idx, upsample, return_taps, target)
 
     def count_parameters(self) -> Dict[str, int]:
         def n(m):

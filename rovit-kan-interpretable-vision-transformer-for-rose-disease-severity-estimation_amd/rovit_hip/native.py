@@ -61,6 +61,8 @@ SIGNATURES = {
     'rovit_vit_forward_gradcam': (_i, [_vp] * 5 + [_i, _i, _vp]),
     'rovit_vit_gradcam': (_i, [_vp] * 8 + [_i, _i] + [_vp] * 6 + [_i, _i, _vp]),
     'rovit_gradcam_map': (_i, [_vp, _vp, _i, _vp]),
+    'rovit_explain_seed': (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
+    'rovit_vit_gradcam_seeded': (_i, [_vp] * 7 + [_i, _i, _vp]),
     'rovit_attention_probs': (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp]),
     'rovit_vit_backward': (_i, [_vp] * 6 + [_i] * 5 + [_vp]),
     'rovit_vit_backward_notify': (_i, [_vp] * 6 + [_i] * 5 + [_vp] + [_vp]),
