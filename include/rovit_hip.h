@@ -299,6 +299,17 @@ int rovit_vit_workspace_field(int batch, int depth, int field, int block, size_t
 int rovit_vit_backward_notify(const float* images, const float* d_features, const float* const* params, const void* prep,
                               void* workspace, float* const* grads, int batch, int depth, int first_block, int last_block,
                               int mlp_path, rovit_stream_t stream, rovit_stream_t notify_stream);
+/* rovit_vit_backward that can also produce the gradient with respect to the input images, and can skip the weight gradients.
+ *   d_images: NULL = no image gradient; else fp32 (batch/copies,3,224,224), written by the range that ends at block 0
+ *             (rovit_patch_embed_dgrad with `copies`, `scale`, `accumulate`: batch must be a multiple of copies, image b's copies being
+ *             batch rows s*(batch/copies) + b).  Ranges with last_block > 0 must pass NULL.
+ *   grads:    NULL = the dgrad chain only: no weight-gradient launch, no write to any gradient or slab buffer, and neither the library's
+ *             side stream nor its event state is used, so a pending data-parallel range sequence of another backward is left intact.
+ *             The dgrad chain's launches are those of the full backward, so its d_images are bit-identical to a full backward's.
+ * With grads != NULL and d_images == NULL this is rovit_vit_backward. */
+int rovit_vit_backward_input(const float* images, const float* d_features, const float* const* params, const void* prep, void* workspace,
+                             float* const* grads, int batch, int depth, int first_block, int last_block, int mlp_path, rovit_stream_t stream,
+                             float* d_images, int copies, float scale, int accumulate);
 
 /* ---- the individual backbone kernels (used by rovit_vit_* and exposed for unit tests / profiling) ---------- */
 /* C = A(M,K) W(N,K)^T + bias with a fused epilogue:
@@ -402,6 +413,13 @@ int rovit_im2col(const float* x, void* col, int batch, rovit_stream_t stream);
 int rovit_patch_embed_fwd(const float* images, const void* W, const float* bias, const float* pos, float* X, int batch, int tokens,
                           rovit_stream_t stream);
 int rovit_patch_embed_wgrad(const void* dY, int ldy, const float* images, int batch, int tokens, int N, int splits, float* ws,
+                            rovit_stream_t stream);
+/* the patch embedding's data gradient, the transpose of rovit_patch_embed_fwd (input_grad.hip):
+ *   d_images[b,c,16py+ky,16px+kx] (+)= scale * sum_{s<copies} sum_n dY[(s*b_out + b)*197 + 1 + 14py + px][n] W[n][c*256 + ky*16 + kx]
+ * dY bf16 (copies*b_out*197, ldy) token rows (class-token rows not read); W the prepared bf16 (192,768) patch weight; d_images fp32 NCHW
+ * (b_out,3,224,224), each element written once: scale * sum when accumulate == 0, added to what it holds otherwise.  The copies are
+ * summed in the fp32 accumulators in the order s = 0, 1, ... before the scale.  bf16 MFMA, fp32 accumulation; no atomics. */
+int rovit_patch_embed_dgrad(const void* dY, int ldy, const void* W, float* d_images, int b_out, int copies, float scale, int accumulate,
                             rovit_stream_t stream);
 int rovit_cls_rows(const float* cls, const float* pos, float* X, int batch, int tokens, rovit_stream_t stream);
 int rovit_cls_norm_fwd(const float* X, const float* gamma, const float* beta, float* feat, float* xhat, float* rstd, int batch,

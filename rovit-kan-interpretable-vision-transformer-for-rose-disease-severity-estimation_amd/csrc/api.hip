@@ -21,6 +21,8 @@ void rovit_set_error(const char* fmt, ...) {
 // 440: rovit_head_mc_fwd added (Monte-Carlo dropout over the heads, mc_dropout.hip).
 // (rovit_explain_seed and rovit_vit_gradcam_seeded were added at 440: new entries only, no argument list changed, and the binding
 // resolves every symbol it declares at load time.)
+// (rovit_patch_embed_dgrad and rovit_vit_backward_input were added at 440 the same way: image gradients, input_grad.hip; the argument
+// lists of rovit_vit_backward and rovit_vit_backward_notify did not change.)
 extern "C" int rovit_version(void) { return 440; }
 extern "C" const char* rovit_last_error_string(void) { return g_err; }
 

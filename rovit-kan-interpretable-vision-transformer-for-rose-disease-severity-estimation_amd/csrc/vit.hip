@@ -572,14 +572,31 @@ extern "C" int rovit_vit_gradcam_seeded(const float* const* params, const void* 
 // runs the final-norm backward from d_features; last_block == 0 also produces the patch-embed / pos / cls
 // gradients.  Splitting the range lets the caller start a gradient all-reduce between calls.
 // grads[] mirrors params[]; every entry of the processed range is overwritten.
+// InputGrad (rovit_vit_backward_input): the image gradient of the range ending at block 0, and/or grads == NULL for the dgrad chain alone.
 namespace {
+struct InputGrad {
+  float* d_images;
+  int copies;
+  float scale;
+  int accumulate;
+};
 int vit_backward_impl(const float* images, const float* d_features, const float* const* params, const void* prep, void* workspace,
                       float* const* grads, int batch, int depth, int first_block, int last_block, int mlp_path, rovit_stream_t stream,
-                      bool defer_join, hipStream_t notify) {
+                      bool defer_join, hipStream_t notify, const InputGrad* ig = nullptr) {
   RUN(check_common(params, prep, workspace, batch, depth, mlp_path));
-  ROVIT_CHECK_ARG(grads, ROVIT_ERR_NULL, "vit_backward: null grads");
+  ROVIT_CHECK_ARG(grads || ig, ROVIT_ERR_NULL, "vit_backward: null grads");
   ROVIT_CHECK_ARG(first_block < depth && last_block >= 0 && first_block >= last_block, ROVIT_ERR_SHAPE,
                   "vit_backward: bad block range [%d..%d] for depth %d", first_block, last_block, depth);
+  // the weight gradients and everything that serves them (the side stream, its events, the slabs) only when there are gradients to write
+  const bool wgrad = grads != nullptr;
+  float* const d_images = ig ? ig->d_images : nullptr;
+  if (d_images) {
+    ROVIT_CHECK_ARG(last_block == 0, ROVIT_ERR_SHAPE, "vit_backward_input: d_images needs the block range that ends at block 0 (got %d)",
+                    last_block);
+    ROVIT_CHECK_ARG(ig->copies > 0 && batch % ig->copies == 0, ROVIT_ERR_SHAPE,
+                    "vit_backward_input: batch %d is not a multiple of copies %d", batch, ig->copies);
+    ROVIT_CHECK_ARG(rovit_aligned16(d_images), ROVIT_ERR_ALIGN, "vit_backward_input: d_images must be 16-byte aligned");
+  }
   const Prep P(depth);
   const Plan L(batch, depth, 1);
   const char* pb = (const char*)prep;
@@ -610,7 +627,7 @@ int vit_backward_impl(const float* images, const float* d_features, const float*
   // block i was last read by B in block i+2 (x1, dpre, dqkv: parity pairs) or i+3 (x0: three buffers, A5 of block i overwrites what
   // the fc2 weight gradient of block i+2 read).
   hipStream_t sA = (hipStream_t)stream;
-  SideStream* ss = two_streams_enabled() ? side_stream() : nullptr;
+  SideStream* ss = (wgrad && two_streams_enabled()) ? side_stream() : nullptr;
   hipStream_t sB = ss ? ss->stream : sA;
   static hipEvent_t no_events[64];
   if (ss && !(ss->carry && first_block != depth - 1)) {      // a new backward pass, or the previous range was joined
@@ -689,8 +706,8 @@ int vit_backward_impl(const float* images, const float* d_features, const float*
       // qkv dgrad below are told so and treat the other rows as zeros without reading them)
       if (ss && !hand_over(ss, sA, sB)) EVFAIL("event hand-over");
       // the final norm's dgamma / dbeta: sample sums off the dgrad chain -> the weight-gradient stream
-      RUN(rovit_cls_norm_affine_grad(d_features, (const float*)(ws + L.xhat_cls), grads[P_NORM_W], grads[P_NORM_B], batch, sB));
-      {
+      if (wgrad) RUN(rovit_cls_norm_affine_grad(d_features, (const float*)(ws + L.xhat_cls), grads[P_NORM_W], grads[P_NORM_B], batch, sB));
+      if (wgrad) {
         const float* const* bpp = params + P_BLOCK0 + B_COUNT * i;
         float* const* bg = grads + P_BLOCK0 + B_COUNT * i;
         const int sc = std::min(std::min(4, L.s_fc2c), std::min(L.s_fc1c, L.s_projc));
@@ -730,7 +747,7 @@ int vit_backward_impl(const float* images, const float* d_features, const float*
       RUN(rovit_gemm_ln_bwd(dp, MLP, q + P.wfc1T, MLP, M, MLP, s + L.xhat2, (const float*)(s + L.rstd2), nullptr, xin, xmid, sA));   // A2
     }
     if (ss && !hand_over(ss, sA, sB)) EVFAIL("event hand-over");                                                   // E_i
-    RUN(issue_merged(i, pending, xin, dp, xmid));
+    if (wgrad) RUN(issue_merged(i, pending, xin, dp, xmid));
     {
       const int cus = ROVIT_KNOB(ROVIT_KNOB_PROJ_DGRAD_CUS, 256);
       if (cus != 256) rovit_set_cu_budget(cus);
@@ -752,13 +769,17 @@ int vit_backward_impl(const float* images, const float* d_features, const float*
     RUN(rovit_pos_grad(nullptr, x0v(-1), grads[P_POS], grads[P_CLS], batch, T, stream));
     return ROVIT_OK;
   };
+  auto pixel_grads = [&]() -> int {          // d_images: the patch embedding's data gradient, from the same bf16 rows (input_grad.hip)
+    if (!d_images) return ROVIT_OK;
+    return rovit_patch_embed_dgrad(x0v(-1), D, pb + P.wpe, d_images, batch / ig->copies, ig->copies, ig->scale, ig->accumulate, stream);
+  };
   bool patch_done = false;
-  if (pending >= 0) {
+  if (pending >= 0 && wgrad) {
     if (ss && !hand_over(ss, sA, sB)) EVFAIL("event hand-over");
     RUN(issue_qkv(pending));
     // the patch-embedding weight gradient (58 us, needs only the dgrad chain's final dX) runs on the caller's stream BESIDE block 0's
     // last weight gradients on the side stream instead of behind the join
-    if (ss && last_block == 0) { RUN(patch_grads()); patch_done = true; }
+    if (ss && last_block == 0) { RUN(patch_grads()); RUN(pixel_grads()); patch_done = true; }
     if (ss && defer_join && last_block > 0) {
       // the gradients of this range are final once B drains: tell the caller's reduction stream, do not stall A
       if (!hand_over(ss, sB, notify)) EVFAIL("event hand-over");
@@ -768,7 +789,10 @@ int vit_backward_impl(const float* images, const float* d_features, const float*
     }
   }
 #undef EVFAIL
-  if (last_block == 0 && !patch_done) RUN(patch_grads());
+  if (last_block == 0 && !patch_done) {
+    if (wgrad) RUN(patch_grads());
+    RUN(pixel_grads());
+  }
   return ROVIT_OK;
 }
 }  // namespace
@@ -789,4 +813,13 @@ extern "C" int rovit_vit_backward_notify(const float* images, const float* d_fea
                                          int last_block, int mlp_path, rovit_stream_t stream, rovit_stream_t notify_stream) {
   return vit_backward_impl(images, d_features, params, prep, workspace, grads, batch, depth, first_block, last_block, mlp_path, stream, true,
                            (hipStream_t)notify_stream);
+}
+
+// rovit_vit_backward plus the image gradient (d_images != NULL) and/or without the weight gradients (grads == NULL): include/rovit_hip.h
+extern "C" int rovit_vit_backward_input(const float* images, const float* d_features, const float* const* params, const void* prep,
+                                        void* workspace, float* const* grads, int batch, int depth, int first_block, int last_block,
+                                        int mlp_path, rovit_stream_t stream, float* d_images, int copies, float scale, int accumulate) {
+  const InputGrad ig{d_images, copies, scale, accumulate};
+  return vit_backward_impl(images, d_features, params, prep, workspace, grads, batch, depth, first_block, last_block, mlp_path, stream, false,
+                           nullptr, &ig);
 }

@@ -141,6 +141,9 @@ class DeiTTiny(nn.Module):
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             raise native.RovitHipError("precision='fp32' is an inference-only parity mode: call it under torch.no_grad() "
                                        '(training runs on the bf16 MFMA path)')
+        if torch.is_grad_enabled() and isinstance(x, torch.Tensor) and x.requires_grad:
+            raise native.RovitHipError("precision='fp32' gives no gradient with respect to the images: use the default "
+                                       "precision='bf16' for input gradients (or rovit_hip.input_grad.input_gradients)")
         x = x.detach().float().contiguous()
         if x.dim() != 4 or tuple(x.shape[1:]) != (3, IMG, IMG):
             raise native.RovitHipError(f'backbone expects (B,3,224,224) images, got {tuple(x.shape)}')
@@ -178,9 +181,9 @@ class DeiTTiny(nn.Module):
             for i in attn_hooked:
                 fire(self.blocks[i].attn, self.blocks[i].attn._forward_hooks, (None,), outs[i])
         eng = self.engine
-        if (norm_fwd or norm_bwd) and not (training and any(p.requires_grad for p in self.parameters())):
-            raise native.RovitHipError('hooks on blocks[i].norm1 read the training workspace: call the model with grad enabled '
-                                       'and trainable backbone parameters (as explainability/gradcam.py does)')
+        if (norm_fwd or norm_bwd) and not (training and (x.requires_grad or any(p.requires_grad for p in self.parameters()))):
+            raise native.RovitHipError('hooks on blocks[i].norm1 read the training workspace: call the model with grad enabled and '
+                                       'images that require grad or trainable backbone parameters (as explainability/gradcam.py does)')
         eng.grad_taps = {i: self._fire_norm1_backward for i in norm_bwd}
         try:
             feats = VitFn.apply(x, eng, training, *self.ordered_parameters())

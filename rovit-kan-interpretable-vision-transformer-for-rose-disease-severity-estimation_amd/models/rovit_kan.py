@@ -219,6 +219,13 @@ class RoViTKAN(nn.Module):
         from rovit_hip import gradcam
         return gradcam.grad_cam_pp(self, x, class_idx, upsample, return_taps, target)
 
+    def input_gradients(self, x: torch.Tensor, target='class', class_idx=None, steps: int = 0, baseline=None, chunk: int = 256,
+                        return_values: bool = False):
+        """Extension (not in the reference): d target / d images of cls_logits, ordinal_severity, mu, log_var or kan_severity for every
+        image of the batch on the GPU, or with ``steps >= 1`` their integrated gradients from ``baseline`` (rovit_hip.input_grad)."""
+        from rovit_hip import input_grad
+        return input_grad.input_gradients(self, x, target, class_idx, steps, baseline, chunk, return_values)
+
     def count_parameters(self) -> Dict[str, int]:
         def n(m):
             return sum(p.numel() for p in m.parameters() if p.requires_grad)

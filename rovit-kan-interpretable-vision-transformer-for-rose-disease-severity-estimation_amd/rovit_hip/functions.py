@@ -524,10 +524,15 @@ class VitEngine:
 class VitFn(torch.autograd.Function):
     """features = backbone(images).  Parameter gradients are written by the HIP backward into the engine's
     flat buffer and installed as ``param.grad`` directly (autograd's per-tensor accumulation would cost ~150
-    tiny copy kernels); accumulation semantics are preserved (grad += new when a grad already exists)."""
+    tiny copy kernels); accumulation semantics are preserved (grad += new when a grad already exists).
+
+    When the images require grad, the backward also returns d features / d images (rovit_vit_backward_input: the patch embedding's data
+    gradient from the dgrad chain's bf16 rows), fp32 computed and cast to the images' dtype.  When no parameter requires grad it runs the
+    dgrad chain alone: no weight gradient, no ``.grad`` installed, the flat gradient buffers and the data-parallel hooks untouched."""
 
     @staticmethod
     def forward(ctx, images, engine: VitEngine, training: bool, *params):
+        ctx.in_dtype = images.dtype
         images = _f32c(images)
         if images.dim() != 4 or tuple(images.shape[1:]) != (3, 224, 224):
             raise native.RovitHipError(f'backbone expects (B,3,224,224) images, got {tuple(images.shape)}')
@@ -536,7 +541,7 @@ class VitFn(torch.autograd.Function):
         prep_mode = engine.prepare(params, defer=True)
         need_bwd = training and any(p.requires_grad for p in params) and torch.is_grad_enabled()
         # (inside Function.forward grad mode is disabled; the caller passes the real flag via `training`)
-        need_bwd = training and any(p.requires_grad for p in params)
+        need_bwd = training and (any(p.requires_grad for p in params) or bool(ctx.needs_input_grad[0]))
         ws = engine.take_ws(B, need_bwd, dev)
         feats = torch.empty(B, 192, device=dev, dtype=torch.float32)
         parr = ptr_array(params)
@@ -577,6 +582,10 @@ class VitFn(torch.autograd.Function):
                                        'in-place update): the prepared bf16 weights no longer match the saved activations')
         dfeat = _f32c(dfeat)
         images, = ctx.saved_tensors
+        want_dx = bool(ctx.needs_input_grad[0])
+        d_img = torch.empty(ctx.batch, 3, 224, 224, device=dfeat.device, dtype=torch.float32) if want_dx else None
+        if not any(ctx.needs_input_grad[3:]):
+            return VitFn._backward_images_only(ctx, engine, images, dfeat, d_img)
         engine.ensure_grads(params)
         fresh = all(p.grad is None for p in params)
         owned = (not fresh) and all(p.grad is not None and p.grad.data_ptr() == v.data_ptr()
@@ -613,8 +622,12 @@ class VitFn(torch.autograd.Function):
                      first, last, ctx.mlp_path, stream_ptr(), engine.notify_stream.cuda_stream)
                 engine.range_hook(engine, first, last, True)
             else:
-                call('rovit_vit_backward', ptr(images), ptr(dfeat), parr, ptr(engine.prep), ptr(ctx.ws), garr, ctx.batch, depth,
-                     first, last, ctx.mlp_path, stream_ptr())
+                if d_img is not None and last == 0:
+                    call('rovit_vit_backward_input', ptr(images), ptr(dfeat), parr, ptr(engine.prep), ptr(ctx.ws), garr, ctx.batch, depth,
+                         first, last, ctx.mlp_path, stream_ptr(), ptr(d_img), 1, 1.0, 0)
+                else:
+                    call('rovit_vit_backward', ptr(images), ptr(dfeat), parr, ptr(engine.prep), ptr(ctx.ws), garr, ctx.batch, depth,
+                         first, last, ctx.mlp_path, stream_ptr())
                 if hooked:
                     engine.range_hook(engine, first, last, False)
                 if last in grad_taps:
@@ -635,8 +648,40 @@ class VitFn(torch.autograd.Function):
             for p, v in zip(params, engine.stage_views):
                 if p.requires_grad:
                     p.grad = v.clone() if p.grad is None else p.grad.add_(v)
+        VitFn._release(ctx, engine)
+        return (VitFn._image_grad(ctx, d_img),) + (None,) * (2 + engine.n_params)
+
+    @staticmethod
+    def _release(ctx, engine):
         if engine.last_ws is not None and engine.last_ws[0] is ctx.ws:
             engine.last_ws = None            # the workspace goes back to the pool: its saved activations are no longer valid
         engine.give_ws(ctx.batch, True, ctx.ws)
         ctx.ws = None
-        return (None,) * (3 + engine.n_params)
+
+    @staticmethod
+    def _image_grad(ctx, d_img):
+        if d_img is None or ctx.in_dtype == torch.float32:
+            return d_img
+        return d_img.to(ctx.in_dtype)
+
+    @staticmethod
+    def _backward_images_only(ctx, engine, images, dfeat, d_img):
+        """No backbone parameter wants a gradient: the dgrad chain alone (rovit_vit_backward_input with grads = NULL), down to the pixels
+        when the images want them, else only as far as the deepest tapped block.  One block range (cut at tapped blocks only): there is no
+        gradient to hand to a data-parallel reduction, so its hooks are not called and its stream state is not touched."""
+        depth, grad_taps = engine.depth, ctx.grad_taps
+        parr = ptr_array(ctx.params)
+        ranges, first = [], depth - 1
+        for c in sorted(grad_taps, reverse=True):
+            ranges.append((first, c))
+            first = c - 1
+        if d_img is not None and first >= 0:
+            ranges.append((first, 0))
+        for first, last in ranges:
+            call('rovit_vit_backward_input', ptr(images), ptr(dfeat), parr, ptr(engine.prep), ptr(ctx.ws), None, ctx.batch, depth,
+                 first, last, ctx.mlp_path, stream_ptr(), ptr(d_img) if last == 0 else None, 1, 1.0, 0)
+            if last in grad_taps:
+                from . import taps
+                grad_taps[last](last, taps.norm1_output_grad(ctx.params, ctx.ws, ctx.batch, depth, last))
+        VitFn._release(ctx, engine)
+        return (VitFn._image_grad(ctx, d_img),) + (None,) * (2 + engine.n_params)

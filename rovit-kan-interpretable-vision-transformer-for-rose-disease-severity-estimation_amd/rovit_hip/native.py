@@ -66,6 +66,7 @@ SIGNATURES = {
     'rovit_attention_probs': (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp]),
     'rovit_vit_backward': (_i, [_vp] * 6 + [_i] * 5 + [_vp]),
     'rovit_vit_backward_notify': (_i, [_vp] * 6 + [_i] * 5 + [_vp] + [_vp]),
+    'rovit_vit_backward_input': (_i, [_vp] * 6 + [_i] * 5 + [_vp] + [_vp, _i, _f, _i]),
     'rovit_gemm_nt': (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _vp]),
     'rovit_gemm_resid_ln': (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp]),
     'rovit_mlp_stream_bytes': (_sz, []),
@@ -90,6 +91,7 @@ SIGNATURES = {
     'rovit_im2col': (_i, [_vp, _vp, _i, _vp]),
     'rovit_patch_embed_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     'rovit_patch_embed_wgrad': (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
+    'rovit_patch_embed_dgrad': (_i, [_vp, _i, _vp, _vp, _i, _i, _f, _i, _vp]),
     'rovit_cls_rows': (_i, [_vp, _vp, _vp, _i, _i, _vp]),
     'rovit_cls_norm_fwd': (_i, [_vp] * 6 + [_i, _i, _f, _vp]),
     'rovit_cls_norm_bwd': (_i, [_vp] * 8 + [_i, _i, _i, _vp]),
