@@ -310,6 +310,14 @@ int rovit_vit_backward_notify(const float* images, const float* d_features, cons
 int rovit_vit_backward_input(const float* images, const float* d_features, const float* const* params, const void* prep, void* workspace,
                              float* const* grads, int batch, int depth, int first_block, int last_block, int mlp_path, rovit_stream_t stream,
                              float* d_images, int copies, float scale, int accumulate);
+/* Gradient-weighted attention relevance (Chefer, Gur & Wolf, ICCV 2021) of one scalar per image, on the workspace of a TRAINING
+ * rovit_vit_forward (training = 1; same batch, depth and mlp_path).  d_features fp32 (B,192) = d target / d features seeds the dgrad
+ * chain from block depth-1 down to block 0, run as rovit_vit_backward_input with grads == NULL (no weight gradient, no image gradient,
+ * no side stream); behind each block's attention-output gradient dO one rovit_attention_relevance_step (first = 1 in the last block),
+ * and block 0's attention backward and qkv dgrad are skipped.  relevance fp32 (B,197) receives row 0 of R_L = (I + A_L) ... (I + A_1),
+ * A_l = mean_h relu(dP_{l,h} * P_{l,h}) (index 0, the class token, included); scratch: fp32, batch * 3 * 197 floats. */
+int rovit_vit_backward_relevance(const float* d_features, const float* const* params, const void* prep, void* workspace, int batch, int depth,
+                                 int mlp_path, float* relevance, float* scratch, rovit_stream_t stream);
 
 /* ---- the individual backbone kernels (used by rovit_vit_* and exposed for unit tests / profiling) ---------- */
 /* C = A(M,K) W(N,K)^T + bias with a fused epilogue:
@@ -421,6 +429,14 @@ int rovit_patch_embed_wgrad(const void* dY, int ldy, const float* images, int ba
  * summed in the fp32 accumulators in the order s = 0, 1, ... before the scale.  bf16 MFMA, fp32 accumulation; no atomics. */
 int rovit_patch_embed_dgrad(const void* dY, int ldy, const void* W, float* d_images, int b_out, int copies, float scale, int accumulate,
                             rovit_stream_t stream);
+/* one block's relevance step (relevance.hip): u fp32 (B,197) <- u + u A,  A[i,j] = (1/3) sum_h relu(P_h[i,j] dP_h[i,j]), with
+ * P_h = exp2(log2(e)/8 Q_h K_h^T - lse2) from the block's saved qkv bf16 (B*197,576) and lse2 fp32 (B,3,197) (the forward's log2-sum-exp),
+ * dP_h = dO_h V_h^T from dout bf16 (B*197,192), the gradient with respect to the attention output.  first != 0: u is taken as e_0 and not
+ * read, and of Q, dout and lse2 only row 0 of every image is read (the training forward's last block writes no other row of lse2 or dO).
+ * scratch: fp32, batch * 3 * 197 floats.  Two launches; bf16 MFMA, fp32 sums in a fixed order, no atomics: bit-identical run to run.
+ * qkv and dout 16-byte aligned. */
+int rovit_attention_relevance_step(const void* qkv, const float* lse2, const void* dout, float* u, float* scratch, int batch, int first,
+                                   rovit_stream_t stream);
 int rovit_cls_rows(const float* cls, const float* pos, float* X, int batch, int tokens, rovit_stream_t stream);
 int rovit_cls_norm_fwd(const float* X, const float* gamma, const float* beta, float* feat, float* xhat, float* rstd, int batch,
                        int tokens, float eps, rovit_stream_t stream);

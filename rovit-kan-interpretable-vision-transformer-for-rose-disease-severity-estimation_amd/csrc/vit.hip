@@ -573,6 +573,8 @@ extern "C" int rovit_vit_gradcam_seeded(const float* const* params, const void* 
 // gradients.  Splitting the range lets the caller start a gradient all-reduce between calls.
 // grads[] mirrors params[]; every entry of the processed range is overwritten.
 // InputGrad (rovit_vit_backward_input): the image gradient of the range ending at block 0, and/or grads == NULL for the dgrad chain alone.
+// Relevance (rovit_vit_backward_relevance: grads == NULL, the whole depth): one relevance step per block on the dgrad stream, behind the
+// block's dO (relevance.hip); block 0 stops there, its attention backward and qkv dgrad feed nothing.
 namespace {
 struct InputGrad {
   float* d_images;
@@ -580,11 +582,15 @@ struct InputGrad {
   float scale;
   int accumulate;
 };
+struct Relevance {
+  float* u;          // (B,197) fp32: row 0 of R_L once block 0 is done
+  float* scratch;    // (B,3,197) fp32: the step kernel's per-head partials
+};
 int vit_backward_impl(const float* images, const float* d_features, const float* const* params, const void* prep, void* workspace,
                       float* const* grads, int batch, int depth, int first_block, int last_block, int mlp_path, rovit_stream_t stream,
-                      bool defer_join, hipStream_t notify, const InputGrad* ig = nullptr) {
+                      bool defer_join, hipStream_t notify, const InputGrad* ig = nullptr, const Relevance* rel = nullptr) {
   RUN(check_common(params, prep, workspace, batch, depth, mlp_path));
-  ROVIT_CHECK_ARG(grads || ig, ROVIT_ERR_NULL, "vit_backward: null grads");
+  ROVIT_CHECK_ARG(grads || ig || rel, ROVIT_ERR_NULL, "vit_backward: null grads");
   ROVIT_CHECK_ARG(first_block < depth && last_block >= 0 && first_block >= last_block, ROVIT_ERR_SHAPE,
                   "vit_backward: bad block range [%d..%d] for depth %d", first_block, last_block, depth);
   // the weight gradients and everything that serves them (the side stream, its events, the slabs) only when there are gradients to write
@@ -702,6 +708,11 @@ int vit_backward_impl(const float* images, const float* d_features, const float*
       // final-norm backward -> fc2 dgrad x gelu' -> fc1 dgrad -> norm2 backward -> proj dgrad on the class-token rows: ONE launch (five before)
       RUN(rovit_cls_tail_bwd(d_features, (const float*)(ws + L.xhat_cls), (const float*)(ws + L.rstd_cls), params[P_NORM_W], q + P.wfc2, q + P.wfc1,
                              q + P.wproj, s + L.dact, s + L.xhat2, (const float*)(s + L.rstd2), xin, dp, xmc, ws + L.dO, batch, T, stream));
+      // relevance: dO and lse2 of this block hold the class-token rows only (first = 1 reads nothing else)
+      if (rel) {
+        RUN(rovit_attention_relevance_step(s + L.qkv, (const float*)(s + L.lse), ws + L.dO, rel->u, rel->scratch, batch, 1, stream));
+        if (i == 0) break;
+      }
       // (no zero fills, round 4: only the CLS rows of dO and of the mid-block gradient carry gradient; the attention backward and the
       // qkv dgrad below are told so and treat the other rows as zeros without reading them)
       if (ss && !hand_over(ss, sA, sB)) EVFAIL("event hand-over");
@@ -755,6 +766,10 @@ int vit_backward_impl(const float* images, const float* d_features, const float*
                                       sA);                                                                         // A3
       if (cus != 256) rovit_set_cu_budget(256);
       if (rc_a3 != ROVIT_OK) return rc_a3;
+    }
+    if (rel) {                                    // before the next block's A3 overwrites dO
+      RUN(rovit_attention_relevance_step(s + L.qkv, (const float*)(s + L.lse), ws + L.dO, rel->u, rel->scratch, batch, 0, sA));
+      if (i == 0) break;
     }
     RUN(rovit_attention_bwd(s + L.qkv, s + L.o, (const float*)(s + L.lse), ws + L.dO, dq, batch, T, H, D / H, 0.125f, sA));       // A4
     // qkv dgrad fused with the backward of norm1
@@ -822,4 +837,14 @@ extern "C" int rovit_vit_backward_input(const float* images, const float* d_feat
   const InputGrad ig{d_images, copies, scale, accumulate};
   return vit_backward_impl(images, d_features, params, prep, workspace, grads, batch, depth, first_block, last_block, mlp_path, stream, false,
                            nullptr, &ig);
+}
+
+// gradient-weighted attention relevance: the dgrad chain alone from d_features over every block, one relevance step per block
+// (include/rovit_hip.h)
+extern "C" int rovit_vit_backward_relevance(const float* d_features, const float* const* params, const void* prep, void* workspace, int batch,
+                                            int depth, int mlp_path, float* relevance, float* scratch, rovit_stream_t stream) {
+  ROVIT_CHECK_ARG(relevance && scratch, ROVIT_ERR_NULL, "vit_backward_relevance: null relevance / scratch");
+  const Relevance rel{relevance, scratch};
+  return vit_backward_impl(nullptr, d_features, params, prep, workspace, nullptr, batch, depth, depth - 1, 0, mlp_path, stream, false, nullptr,
+                           nullptr, &rel);
 }

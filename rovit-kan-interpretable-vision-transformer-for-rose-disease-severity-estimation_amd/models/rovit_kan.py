@@ -226,6 +226,14 @@ class RoViTKAN(nn.Module):
         from rovit_hip import input_grad
         return input_grad.input_gradients(self, x, target, class_idx, steps, baseline, chunk, return_values)
 
+    def attention_relevance(self, x: torch.Tensor, target='class', class_idx=None, upsample: bool = True, chunk: int = 256,
+                            return_values: bool = False):
+        """Extension (not in the reference): gradient-weighted attention relevance (Chefer, Gur & Wolf 2021) of cls_logits,
+        ordinal_severity, mu, log_var or kan_severity for every image of the batch on the GPU, through every block
+        (rovit_hip.relevance)."""
+        from rovit_hip import relevance
+        return relevance.attention_relevance(self, x, target, class_idx, upsample, chunk, return_values)
+
     def count_parameters(self) -> Dict[str, int]:
         def n(m):
             return sum(p.numel() for p in m.parameters() if p.requires_grad)

@@ -11,7 +11,7 @@ from .gradcam import TARGETS, _check_coverage, _target_names, _targets
 from .native import RovitHipError, call, ptr, ptr_array, stream_ptr
 
 
-def _check_phase(model):
+def _check_phase(model, what='input_gradients'):
     """The head / KAN shapes of the fused head phase (the seeds come from its backward).  Raises before any launch."""
     c, o, u, k = model.classification_head, model.ordinal_head, model.uncertainty_head, model.kan_module
     hid, C_ = c.fc1.out_features, c.fc2.out_features
@@ -22,45 +22,45 @@ def _check_phase(model):
         ok = (k.degree == 3 and 1 <= len(k.kan_layers) <= 4 and d[0] == 192 and all(1 <= w <= 64 for w in d[1:])
               and all(8 <= l.knots.numel() <= 64 for l in k.kan_layers))
     if not ok:
-        raise RovitHipError('input_gradients: the heads / KAN stack are outside the shapes of the fused head phase (192 features, '
+        raise RovitHipError(f'{what}: the heads / KAN stack are outside the shapes of the fused head phase (192 features, '
                             'equal hidden widths 4..256 in multiples of 4, 2..8 classes, a degree-3 KAN of 1..4 layers of width <= 64); '
                             'use autograd through the model with images that require grad instead')
 
 
-def _check_args(model, x, target, class_idx, steps, baseline, chunk):
+def _check_args(model, x, target, class_idx, steps, baseline, chunk, what='input_gradients'):
     if not isinstance(x, torch.Tensor) or x.dim() != 4 or tuple(x.shape[1:]) != (3, 224, 224):
-        raise RovitHipError(f'input_gradients: expects (B,3,224,224) images, got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x)}')
+        raise RovitHipError(f'{what}: expects (B,3,224,224) images, got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x)}')
     if x.shape[0] < 1:
-        raise RovitHipError('input_gradients: empty batch')
+        raise RovitHipError(f'{what}: empty batch')
     if not x.dtype.is_floating_point:
-        raise RovitHipError(f'input_gradients: the images must be floating point, got {x.dtype}')
+        raise RovitHipError(f'{what}: the images must be floating point, got {x.dtype}')
     if isinstance(target, (list, tuple)):
-        raise RovitHipError(f'input_gradients: one target per call, got {target!r}')
+        raise RovitHipError(f'{what}: one target per call, got {target!r}')
     names, _ = _target_names(target, class_idx, model.curriculum_stage)
     if isinstance(steps, bool) or not isinstance(steps, int) or steps < 0:
-        raise RovitHipError(f'input_gradients: steps must be an int >= 0 (0: the plain gradient), got {steps!r}')
+        raise RovitHipError(f'{what}: steps must be an int >= 0 (0: the plain gradient), got {steps!r}')
     if isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1:
-        raise RovitHipError(f'input_gradients: chunk must be an int >= 1, got {chunk!r}')
+        raise RovitHipError(f'{what}: chunk must be an int >= 1, got {chunk!r}')
     if baseline is not None:
         if steps == 0:
-            raise RovitHipError('input_gradients: a baseline is only used by integrated gradients (steps >= 1)')
+            raise RovitHipError(f'{what}: a baseline is only used by integrated gradients (steps >= 1)')
         if not isinstance(baseline, torch.Tensor) or not baseline.dtype.is_floating_point:
-            raise RovitHipError(f'input_gradients: baseline must be a floating-point tensor, got {type(baseline).__name__}')
+            raise RovitHipError(f'{what}: baseline must be a floating-point tensor, got {type(baseline).__name__}')
         try:
             shape = torch.broadcast_shapes(baseline.shape, x.shape)
         except RuntimeError:
             shape = None
         if shape != x.shape:
-            raise RovitHipError(f'input_gradients: baseline of shape {tuple(baseline.shape)} does not broadcast to the images '
+            raise RovitHipError(f'{what}: baseline of shape {tuple(baseline.shape)} does not broadcast to the images '
                                 f'{tuple(x.shape)}')
         if baseline.device != x.device:
-            raise RovitHipError(f'input_gradients: baseline on {baseline.device}, images on {x.device}')
+            raise RovitHipError(f'{what}: baseline on {baseline.device}, images on {x.device}')
     head = model.classification_head
     targets = _targets(class_idx, x.shape[0], head.fc2.out_features, x.device) if target == 'class' else None
     _check_coverage(model, [n for n in names if n != 'class'])
-    _check_phase(model)
+    _check_phase(model, what)
     if not x.is_cuda:
-        raise RovitHipError('input_gradients: the images must be on the GPU (there is no CPU fallback)')
+        raise RovitHipError(f'{what}: the images must be on the GPU (there is no CPU fallback)')
     return targets
 
 
@@ -134,6 +134,13 @@ class _Backbone:
         n = imgs.shape[0]
         call('rovit_vit_backward_input', ptr(imgs), ptr(seed), self.pa, ptr(self.eng.prep), ptr(ws), None, n, self.vit.depth,
              self.vit.depth - 1, 0, self.mlp, stream_ptr(), ptr(out), copies, float(scale), int(accumulate))
+        self.eng.give_ws(n, True, ws)
+
+    def relevance(self, ws, seed, out, scratch):
+        """The dgrad chain alone with one relevance step per block (rovit_vit_backward_relevance): out (n,197) = row 0 of R_L."""
+        n = out.shape[0]
+        call('rovit_vit_backward_relevance', ptr(seed), self.pa, ptr(self.eng.prep), ptr(ws), n, self.vit.depth, self.mlp, ptr(out),
+             ptr(scratch), stream_ptr())
         self.eng.give_ws(n, True, ws)
 
 
