@@ -318,6 +318,20 @@ int rovit_vit_backward_input(const float* images, const float* d_features, const
  * A_l = mean_h relu(dP_{l,h} * P_{l,h}) (index 0, the class token, included); scratch: fp32, batch * 3 * 197 floats. */
 int rovit_vit_backward_relevance(const float* d_features, const float* const* params, const void* prep, void* workspace, int batch, int depth,
                                  int mlp_path, float* relevance, float* scratch, rovit_stream_t stream);
+/* Deletion / insertion curves (perturb.hip).  The patch embedding is a 16x16 convolution with stride 16, so every token row of an image
+ * perturbed patch by patch is a row of the clean image's or of its baseline's token table: embed both once, then assemble sequences.
+ * rovit_vit_embed: tokens fp32 (n,197,192) receives the rows rovit_vit_forward starts from -- its first two launches (rovit_cls_rows,
+ * rovit_patch_embed_fwd): row 0 = cls + pos[0], row 1 + p = patch(p) W^T + bias + pos[1 + p], p = 14 * row + column. */
+int rovit_vit_embed(const float* images, const float* const* params, const void* prep, float* tokens, int n, int depth, rovit_stream_t stream);
+/* The inference forward (training = 0) of n_seq sequences of `tokens` rows (1..197).  Row r of sequence s is v = src[s * tokens + r]:
+ * v >= 0 row v of img_tokens[seq_img[s]], v < 0 row -1 - v of base_tokens[base_shared ? 0 : seq_img[s]]; the tables hold n_img images
+ * (base_tokens: n_img, or 1 when base_shared) of 197 rows from rovit_vit_embed.  seq_img (n_seq) and src (n_seq * tokens): int32 device
+ * arrays; every index is clamped into its table.  Workspace: rovit_vit_workspace_bytes(n_seq, depth, 0), of which a shorter sequence
+ * uses a prefix.  From block 0's LayerNorm on, the launches of rovit_vit_forward at n_seq * tokens rows (mlp_path as there): with
+ * tokens = 197 and src[s * 197 + r] in {r, -1 - r} the features equal rovit_vit_forward's of the pixel image made from those patches. */
+int rovit_vit_forward_tokens(const float* img_tokens, const float* base_tokens, int n_img, int base_shared, const int* seq_img, const int* src,
+                             int tokens, const float* const* params, const void* prep, void* workspace, float* features, int n_seq, int depth,
+                             int mlp_path, rovit_stream_t stream);
 
 /* ---- the individual backbone kernels (used by rovit_vit_* and exposed for unit tests / profiling) ---------- */
 /* C = A(M,K) W(N,K)^T + bias with a fused epilogue:

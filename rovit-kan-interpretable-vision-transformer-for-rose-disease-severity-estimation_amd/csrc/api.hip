@@ -24,6 +24,7 @@ void rovit_set_error(const char* fmt, ...) {
 // (rovit_patch_embed_dgrad and rovit_vit_backward_input were added at 440 the same way: image gradients, input_grad.hip; the argument
 // lists of rovit_vit_backward and rovit_vit_backward_notify did not change.)
 // (rovit_attention_relevance_step and rovit_vit_backward_relevance were added at 440 the same way: attention relevance, relevance.hip.)
+// (rovit_vit_embed and rovit_vit_forward_tokens were added at 440 the same way: deletion / insertion curves, perturb.hip.)
 extern "C" int rovit_version(void) { return 440; }
 extern "C" const char* rovit_last_error_string(void) { return g_err; }
 

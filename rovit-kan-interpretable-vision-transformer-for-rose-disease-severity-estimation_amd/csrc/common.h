@@ -221,6 +221,10 @@ int rovit_gradcam_seed(const float* feat, const float* w1, const float* b1, cons
                        rovit_stream_t stream);
 int rovit_gradcam_cam(const void* dqkv, const void* wt, const void* xhat1, const float* gamma, const float* beta, float* g, double* spart,
                       float* act, float* grad, float* cam, int batch, rovit_stream_t stream);
+// perturb.hip: the residual stream of n_seq sequences of `tokens` rows gathered from token tables (n_img images, or one baseline when
+// base_shared) by seq_img (n_seq) and src (n_seq * tokens) -- rovit_vit_forward_tokens' first launch
+int rovit_gather_token_rows(const float* img_tokens, const float* base_tokens, int n_img, int base_shared, const int* seq_img, const int* src,
+                            float* X, int n_seq, int tokens, rovit_stream_t stream);
 // explain.hip: the same bf16 transposed qkv-weight copy on its own (rovit_vit_gradcam_seeded has no head seed to launch it beside)
 int rovit_gradcam_wt(const float* wqkv, void* wt, rovit_stream_t stream);
 // cls_tail.hip: the last block's post-attention half + the final norm on the class-token rows in one launch

@@ -78,8 +78,9 @@ struct Plan {          // byte offsets into the workspace
   int s_qkv, s_proj, s_fc1, s_fc2, s_pe;
   int s_projc, s_fc1c, s_fc2c;      // split counts when only the B CLS rows are processed (last block)
   size_t total;
-  Plan(int batch, int depth_, int training_) : B(batch), depth(depth_), training(training_) {
-    M = (size_t)B * T;
+  // tokens < 197: the inference forward of shorter sequences (rovit_vit_forward_tokens); its buffers are a prefix of the 197-token plan's
+  Plan(int batch, int depth_, int training_, int tokens = T) : B(batch), depth(depth_), training(training_) {
+    M = (size_t)B * tokens;
     size_t o = 0;
     X = o; o = al(o + M * D * 4);
     xhat_cls = o; o = al(o + (size_t)B * D * 4);
@@ -88,7 +89,7 @@ struct Plan {          // byte offsets into the workspace
     xhat1 = b; b = al(b + M * D * 2);
     rstd1 = b; b = al(b + M * 4);
     qkv = b; b = al(b + M * 3 * D * 2);
-    lse = b; b = al(b + (size_t)B * H * T * 4);
+    lse = b; b = al(b + (size_t)B * H * tokens * 4);
     this->o = b; b = al(b + M * D * 2);
     xhat2 = b; b = al(b + M * D * 2);
     rstd2 = b; b = al(b + M * 4);
@@ -284,14 +285,33 @@ extern "C" int rovit_vit_prepare(const float* const* params, void* prep, int dep
 }
 
 namespace {
-// prepare: 0 = the weights in `prep` are current; 1 = prepare them from `params` first; 2 = ... and write the constant tables too
+// The forward's first two launches: the class-token rows (cls + pos[0]) and the patch embedding (patch(p) W^T + bias + pos[1 + p]) of
+// `batch` images into the 197-token rows of X.  Also rovit_vit_embed's whole work.
+int embed_rows(const float* images, const float* const* params, const char* pb, const Prep& P, float* X, int batch, rovit_stream_t stream) {
+  RUN(rovit_cls_rows(params[P_CLS], params[P_POS], X, batch, T, stream));
+  // PatchEmbed: the GEMM gathers its A tiles from the images (no im2col buffer: 77 MB and one 42 us launch less per step)
+  return rovit_patch_embed_fwd(images, pb + P.wpe, params[P_PATCH_B], params[P_POS], X, batch, T, stream);
+}
+
+// rovit_vit_forward_tokens: where the rows of X come from instead of embed_rows (perturb.hip)
+struct TokenRows {
+  const float* img;
+  const float* base;
+  int n_img, base_shared;
+  const int* seq_img;
+  const int* src;
+};
+
+// prepare: 0 = the weights in `prep` are current; 1 = prepare them from `params` first; 2 = ... and write the constant tables too.
+// tokens: the sequence length (197 but for rovit_vit_forward_tokens); rows: gather X from token tables instead of embedding `images`.
 int vit_forward_impl(const float* images, const float* const* params, const void* prep, void* workspace, float* features,
                      void* const* attn_taps, float* const* prob_taps, int batch, int depth, int training, int mlp_path,
-                     rovit_stream_t stream, int prepare = 0, float* rollout = nullptr, int head_fusion = 0, bool gradcam = false) {
-  ROVIT_CHECK_ARG(images && features, ROVIT_ERR_NULL, "vit_forward: null images/features");
+                     rovit_stream_t stream, int prepare = 0, float* rollout = nullptr, int head_fusion = 0, bool gradcam = false,
+                     int tokens = T, const TokenRows* rows = nullptr) {
+  ROVIT_CHECK_ARG((images || rows) && features, ROVIT_ERR_NULL, "vit_forward: null images/features");
   RUN(check_common(params, prep, workspace, batch, depth, mlp_path));
   const Prep P(depth);
-  const Plan L(batch, depth, training);
+  const Plan L(batch, depth, training, tokens);
   const char* pb = (const char*)prep;
   char* ws = (char*)workspace;
   float* X = (float*)(ws + L.X);
@@ -313,9 +333,11 @@ int vit_forward_impl(const float* images, const float* const* params, const void
     RUN(vit_prepare_impl(params, const_cast<void*>(prep), depth, stream, ss_prep ? (rovit_stream_t)ss_prep->stream : stream, prepare == 2));
     if (ss_prep && !(ev_prep = hand_over(ss_prep, ss_prep->stream, nullptr, true))) { rovit_set_error("vit_forward: event record failed"); return ROVIT_ERR_LAUNCH; }
   }
-  RUN(rovit_cls_rows(params[P_CLS], params[P_POS], X, batch, T, stream));
-  // PatchEmbed: the GEMM gathers its A tiles from the images (no im2col buffer: 77 MB and one 42 us launch less per step)
-  RUN(rovit_patch_embed_fwd(images, pb + P.wpe, params[P_PATCH_B], params[P_POS], X, batch, T, stream));
+  if (rows) {
+    RUN(rovit_gather_token_rows(rows->img, rows->base, rows->n_img, rows->base_shared, rows->seq_img, rows->src, X, batch, tokens, stream));
+  } else {
+    RUN(embed_rows(images, params, pb, P, X, batch, stream));
+  }
   if (ev_prep && hipStreamWaitEvent((hipStream_t)stream, ev_prep, 0) != hipSuccess) { rovit_set_error("vit_forward: event wait failed"); return ROVIT_ERR_LAUNCH; }
   // Samples are independent in the forward pass, so the batch is cut into two halves that run the same kernel
   // chain on two HIP streams with no synchronisation until the final norm: every kernel here is a 20-50 us
@@ -339,20 +361,21 @@ int vit_forward_impl(const float* images, const float* const* params, const void
     const char* q = pb + P.blk0 + (size_t)i * P.blk_stride;
     char* s = ws + L.blk0 + (size_t)i * L.blk_stride;
     // Only token 0 of the LAST block's output is consumed (final norm + heads), and everything after the
-    // attention is row-wise: run proj / LN2 / MLP of that block on the B CLS rows only (row step T).
+    // attention is row-wise: run proj / LN2 / MLP of that block on the B CLS rows only (row step tokens).
     const bool cls_only = (i == depth - 1);
-    const int rs = cls_only ? T : 1;
+    const int rs = cls_only ? tokens : 1;
     // per-half views: r = first row of the half; activations are row-major with the images contiguous
-#define ROWS(ptr, width, esz) ((ptr) + (size_t)h.b0 * T * (width) * (esz))
+#define ROWS(ptr, width, esz) ((ptr) + (size_t)h.b0 * tokens * (width) * (esz))
     // LayerNorm1 of block 0 is a kernel of its own; every other LayerNorm of the loop is fused into the epilogue
     // of the GEMM that produces its input (proj -> norm2, fc2 -> next block's norm1).
     if (i == 0) EACH_HALF {
       const Half& h = halves[hh];
-      RUN(rovit_layernorm_fwd(X + (size_t)h.b0 * T * D, ROWS(s + L.xhat1, D, 2), (float*)ROWS(s + L.rstd1, 1, 4), h.nb * T, D, eps, h.st));
+      RUN(rovit_layernorm_fwd(X + (size_t)h.b0 * tokens * D, ROWS(s + L.xhat1, D, 2), (float*)ROWS(s + L.rstd1, 1, 4), h.nb * tokens, D, eps,
+                              h.st));
     }
     if (!qkv_done) EACH_HALF {
       const Half& h = halves[hh];
-      RUN(rovit_gemm_nt(ROWS(s + L.xhat1, D, 2), D, q + P.wqkv, D, h.nb * T, 3 * D, D, (const float*)(q + P.bqkv), EPI_BF16,
+      RUN(rovit_gemm_nt(ROWS(s + L.xhat1, D, 2), D, q + P.wqkv, D, h.nb * tokens, 3 * D, D, (const float*)(q + P.bqkv), EPI_BF16,
                         ROWS(s + L.qkv, 3 * D, 2), 3 * D, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, h.st));
     }
     qkv_done = false;
@@ -367,11 +390,11 @@ int vit_forward_impl(const float* images, const float* const* params, const void
       // the last block: only the class token's attention output is consumed (the half behind it runs on those rows alone), and a query's
       // output needs no other query -- 197 scores per (image, head) instead of 197 x 197 (taps want every token's output: full kernel)
       if (cls_only && !taps) {
-        RUN(rovit_attention_cls_fwd(ROWS(s + L.qkv, 3 * D, 2), ROWS(s + L.o, D, 2), (float*)(s + L.lse) + (size_t)h.b0 * H * T, h.nb, T, H, D / H,
-                                    0.125f, h.st));
+        RUN(rovit_attention_cls_fwd(ROWS(s + L.qkv, 3 * D, 2), ROWS(s + L.o, D, 2), (float*)(s + L.lse) + (size_t)h.b0 * H * tokens, h.nb, tokens,
+                                    H, D / H, 0.125f, h.st));
       } else {
-        RUN(rovit_attention_fwd(ROWS(s + L.qkv, 3 * D, 2), ROWS(s + L.o, D, 2), (float*)(s + L.lse) + (size_t)h.b0 * H * T, h.nb, T, H, D / H,
-                                0.125f, h.st));
+        RUN(rovit_attention_fwd(ROWS(s + L.qkv, 3 * D, 2), ROWS(s + L.o, D, 2), (float*)(s + L.lse) + (size_t)h.b0 * H * tokens, h.nb, tokens,
+                                H, D / H, 0.125f, h.st));
       }
     }
     // explainability tap: the attention module's output (proj(attention) + bias, before the residual add) for
@@ -381,7 +404,7 @@ int vit_forward_impl(const float* images, const float* const* params, const void
                         nullptr, 0, stream));
     // ... and, separately, the softmax probabilities (B,3,197,197) the reference's rollout code means to collect
     // (explainability/attention_maps.py:18-105)
-    if (prob_taps && prob_taps[i]) RUN(rovit_attention_probs(s + L.qkv, prob_taps[i], batch, T, H, D / H, 0.125f, stream));
+    if (prob_taps && prob_taps[i]) RUN(rovit_attention_probs(s + L.qkv, prob_taps[i], batch, tokens, H, D / H, 0.125f, stream));
     // ... and the attention rollout (rollout.hip), folded into a running (B,197) vector behind every block's attention (before the
     // block tail overwrites qkv with the next block's); its partial sums use the dact slot, which an inference forward never writes
     if (rollout) RUN(rovit_rollout_step(s + L.qkv, rollout, (float*)(s + L.dact), head_fusion, batch, i == 0, stream));
@@ -392,60 +415,60 @@ int vit_forward_impl(const float* images, const float* const* params, const void
         const Half& h = halves[hh];
         // (training, and the Grad-CAM++ forward: keep what the class-token backward reads)
         const bool keep = training || gradcam;
-        RUN(rovit_cls_tail_fwd(ROWS(s + L.o, D, 2), X + (size_t)h.b0 * T * D, q + P.wproj, bp[B_PROJB], q + P.wfc1, (const float*)(q + P.bfc1),
+        RUN(rovit_cls_tail_fwd(ROWS(s + L.o, D, 2), X + (size_t)h.b0 * tokens * D, q + P.wproj, bp[B_PROJB], q + P.wfc1, (const float*)(q + P.bfc1),
                                q + P.wfc2, bp[B_FC2B], params[P_NORM_W], params[P_NORM_B], keep ? ROWS(s + L.xhat2, D, 2) : nullptr,
                                keep ? (float*)ROWS(s + L.rstd2, 1, 4) : nullptr, keep ? ROWS(s + L.act, MLP, 2) : nullptr,
                                keep ? ROWS(s + L.dact, MLP, 2) : nullptr, features + (size_t)h.b0 * D,
-                               (float*)(ws + L.xhat_cls) + (size_t)h.b0 * D, (float*)(ws + L.rstd_cls) + h.b0, h.nb, T, eps, h.st));
+                               (float*)(ws + L.xhat_cls) + (size_t)h.b0 * D, (float*)(ws + L.rstd_cls) + h.b0, h.nb, tokens, eps, h.st));
       }
       continue;
     }
     // Everything behind the attention in ONE launch ("block tail", mlp_fused.hip: proj + residual + norm2 + MLP + residual + next
     // norm1 + the NEXT block's qkv projection; the residual stream stays in registers between the halves).
-    if (!cls_only && mlp_one_launch(mlp_path, (long)batch * T)) {
+    if (!cls_only && mlp_one_launch(mlp_path, (long)batch * tokens)) {
       char* sn = ws + L.blk0 + (size_t)(i + 1) * L.blk_stride;            // next block's saved-activation area
       const bool tail_qkv = true;
       qkv_done = tail_qkv;                                                // block i + 1 finds its qkv projection written
       EACH_HALF {
         const Half& h = halves[hh];
-        float* Xh = X + (size_t)h.b0 * T * D;
+        float* Xh = X + (size_t)h.b0 * tokens * D;
         RUN(rovit_block_tail_fwd(ROWS(s + L.o, D, 2), q + P.wmlp, bp[B_PROJB], (const float*)(q + P.bfc1), bp[B_FC2B], Xh,
                                  training ? ROWS(s + L.xhat2, D, 2) : nullptr, training ? (float*)ROWS(s + L.rstd2, 1, 4) : nullptr,
                                  training ? ROWS(s + L.act, 32, 2) : nullptr, training ? ROWS(s + L.dact, 32, 2) : nullptr,
                                  ROWS(sn + L.xhat1, D, 2), (float*)ROWS(sn + L.rstd1, 1, 4),
                                  tail_qkv ? (const float*)(q + P.blk_stride + P.bqkv) : nullptr, tail_qkv ? ROWS(sn + L.qkv, 3 * D, 2) : nullptr,
-                                 eps, h.nb * T, batch * T, h.st));
+                                 eps, h.nb * tokens, batch * tokens, h.st));
       }
       continue;
     }
     EACH_HALF {
       const Half& h = halves[hh];
-      float* Xh = X + (size_t)h.b0 * T * D;
+      float* Xh = X + (size_t)h.b0 * tokens * D;
       if (cls_only) {
         RUN(rovit_gemm_nt(ROWS(s + L.o, D, 2), D * rs, q + P.wproj, D, h.nb, D, D, bp[B_PROJB], EPI_RESID, nullptr, 0, nullptr, Xh, D * rs,
                           nullptr, 0, nullptr, 0, h.st));
-        RUN(rovit_layernorm_fwd_rows(Xh, ROWS(s + L.xhat2, D, 2), (float*)ROWS(s + L.rstd2, 1, 4), h.nb, T, eps, h.st));
+        RUN(rovit_layernorm_fwd_rows(Xh, ROWS(s + L.xhat2, D, 2), (float*)ROWS(s + L.rstd2, 1, 4), h.nb, tokens, eps, h.st));
       } else {
-        RUN(rovit_gemm_resid_ln(ROWS(s + L.o, D, 2), D, q + P.wproj, D, h.nb * T, D, bp[B_PROJB], Xh, ROWS(s + L.xhat2, D, 2),
+        RUN(rovit_gemm_resid_ln(ROWS(s + L.o, D, 2), D, q + P.wproj, D, h.nb * tokens, D, bp[B_PROJB], Xh, ROWS(s + L.xhat2, D, 2),
                                 (float*)ROWS(s + L.rstd2, 1, 4), eps, h.st));
       }
     }
     // two-launch MLP half (small batches, and the CLS rows of the last block): fc1 + GELU, then fc2 + residual + next LayerNorm
     EACH_HALF {
       const Half& h = halves[hh];
-      RUN(rovit_gemm_nt(ROWS(s + L.xhat2, D, 2), D * rs, q + P.wfc1, D, cls_only ? h.nb : h.nb * T, MLP, D, (const float*)(q + P.bfc1),
+      RUN(rovit_gemm_nt(ROWS(s + L.xhat2, D, 2), D * rs, q + P.wfc1, D, cls_only ? h.nb : h.nb * tokens, MLP, D, (const float*)(q + P.bfc1),
                         EPI_GELU, ROWS(s + L.act, MLP, 2), MLP * rs, training ? ROWS(s + L.dact, MLP, 2) : nullptr, nullptr, 0, nullptr, 0,
                         nullptr, 0, h.st));
     }
     EACH_HALF {
       const Half& h = halves[hh];
-      float* Xh = X + (size_t)h.b0 * T * D;
+      float* Xh = X + (size_t)h.b0 * tokens * D;
       if (cls_only) {
         RUN(rovit_gemm_nt(ROWS(s + L.act, MLP, 2), MLP * rs, q + P.wfc2, MLP, h.nb, D, MLP, bp[B_FC2B], EPI_RESID, nullptr, 0, nullptr, Xh,
                           D * rs, nullptr, 0, nullptr, 0, h.st));
       } else {
         char* sn = ws + L.blk0 + (size_t)(i + 1) * L.blk_stride;          // next block's saved-activation area
-        RUN(rovit_gemm_resid_ln(ROWS(s + L.act, MLP, 2), MLP, q + P.wfc2, MLP, h.nb * T, MLP, bp[B_FC2B], Xh, ROWS(sn + L.xhat1, D, 2),
+        RUN(rovit_gemm_resid_ln(ROWS(s + L.act, MLP, 2), MLP, q + P.wfc2, MLP, h.nb * tokens, MLP, bp[B_FC2B], Xh, ROWS(sn + L.xhat1, D, 2),
                                 (float*)ROWS(sn + L.rstd1, 1, 4), eps, h.st));
       }
     }
@@ -455,7 +478,7 @@ int vit_forward_impl(const float* images, const float* const* params, const void
   if (ss && !hand_over(ss, ss->stream, (hipStream_t)stream)) { rovit_set_error("vit_forward: event hand-over failed"); return ROVIT_ERR_LAUNCH; }
   if (!cls_fused)
     RUN(rovit_cls_norm_fwd(X, params[P_NORM_W], params[P_NORM_B], features, (float*)(ws + L.xhat_cls), (float*)(ws + L.rstd_cls), batch,
-                           T, eps, stream));
+                           tokens, eps, stream));
   return ROVIT_OK;
 }
 }  // namespace
@@ -464,6 +487,28 @@ int vit_forward_impl(const float* images, const float* const* params, const void
 extern "C" int rovit_vit_forward(const float* images, const float* const* params, const void* prep, void* workspace,
                                  float* features, int batch, int depth, int training, int mlp_path, rovit_stream_t stream) {
   return vit_forward_impl(images, params, prep, workspace, features, nullptr, nullptr, batch, depth, training, mlp_path, stream);
+}
+
+// The token rows rovit_vit_forward starts from, of n images: tokens fp32 (n,197,192), the two launches in front of block 0.
+extern "C" int rovit_vit_embed(const float* images, const float* const* params, const void* prep, float* tokens, int n, int depth,
+                               rovit_stream_t stream) {
+  ROVIT_CHECK_ARG(images && params && prep && tokens, ROVIT_ERR_NULL, "vit_embed: null images/params/prep/tokens");
+  ROVIT_CHECK_ARG(n > 0 && depth > 0 && depth <= 64, ROVIT_ERR_SHAPE, "vit_embed: bad n %d / depth %d", n, depth);
+  ROVIT_CHECK_ARG(rovit_aligned16(prep) && rovit_aligned16(tokens), ROVIT_ERR_ALIGN, "vit_embed: prep/tokens must be 16-byte aligned");
+  return embed_rows(images, params, (const char*)prep, Prep(depth), tokens, n, stream);
+}
+
+// Inference forward of n_seq sequences of `tokens` rows gathered from token tables (perturb.hip); from block 0's LayerNorm on the
+// launches of rovit_vit_forward at n_seq * tokens rows.  Workspace: rovit_vit_workspace_bytes(n_seq, depth, 0), of which it uses a prefix.
+extern "C" int rovit_vit_forward_tokens(const float* img_tokens, const float* base_tokens, int n_img, int base_shared, const int* seq_img,
+                                        const int* src, int tokens, const float* const* params, const void* prep, void* workspace,
+                                        float* features, int n_seq, int depth, int mlp_path, rovit_stream_t stream) {
+  ROVIT_CHECK_ARG(img_tokens && base_tokens && seq_img && src, ROVIT_ERR_NULL, "vit_forward_tokens: null token table / index array");
+  ROVIT_CHECK_ARG(tokens >= 1 && tokens <= T, ROVIT_ERR_SHAPE, "vit_forward_tokens: tokens must be in [1, %d], got %d", T, tokens);
+  ROVIT_CHECK_ARG(n_img > 0, ROVIT_ERR_SHAPE, "vit_forward_tokens: n_img must be >= 1, got %d", n_img);
+  const TokenRows rows{img_tokens, base_tokens, n_img, base_shared, seq_img, src};
+  return vit_forward_impl(nullptr, params, prep, workspace, features, nullptr, nullptr, n_seq, depth, 0, mlp_path, stream, 0, nullptr, 0,
+                          false, tokens, &rows);
 }
 
 // rovit_vit_prepare + rovit_vit_forward as ONE call (a training step prepares the weights after every optimizer step): the blocks'

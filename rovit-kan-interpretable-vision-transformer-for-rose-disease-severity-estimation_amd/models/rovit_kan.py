@@ -234,6 +234,14 @@ class RoViTKAN(nn.Module):
         from rovit_hip import relevance
         return relevance.attention_relevance(self, x, target, class_idx, upsample, chunk, return_values)
 
+    def perturbation_curves(self, x: torch.Tensor, saliency, target='class', class_idx=None, modes=('deletion', 'insertion'),
+                            steps: int = 28, perturbation: str = 'replace', baseline=None, chunk: int = 256):
+        """Extension (not in the reference): deletion / insertion curves and their areas (Petsiuk et al. 2018) of one or several
+        saliency maps for cls_logits' probability, ordinal_severity, mu, log_var or kan_severity on the GPU, patches replaced by a
+        baseline's or dropped from the sequence (rovit_hip.perturbation)."""
+        from rovit_hip import perturbation as pert
+        return pert.perturbation_curves(self, x, saliency, target, class_idx, modes, steps, perturbation, baseline, chunk)
+
     def count_parameters(self) -> Dict[str, int]:
         def n(m):
             return sum(p.numel() for p in m.parameters() if p.requires_grad)

@@ -136,6 +136,19 @@ class _Backbone:
              self.vit.depth - 1, 0, self.mlp, stream_ptr(), ptr(out), copies, float(scale), int(accumulate))
         self.eng.give_ws(n, True, ws)
 
+    def embed(self, imgs, out):
+        """The token rows the forward starts from (rovit_vit_embed): out (n,197,192) fp32."""
+        call('rovit_vit_embed', ptr(imgs), self.pa, ptr(self.eng.prep), ptr(out), imgs.shape[0], self.vit.depth, stream_ptr())
+
+    def forward_tokens(self, img_tokens, base_tokens, base_shared, seq_img, src, ws, mlp_path):
+        """Inference features (n,192) of the n sequences of src (n, tokens) gathered from the token tables (rovit_vit_forward_tokens);
+        ws: an inference workspace of at least n sequences (a shorter sequence uses a prefix of it)."""
+        n, tokens = src.shape
+        feats = torch.empty(n, 192, device=self.dev, dtype=torch.float32)
+        call('rovit_vit_forward_tokens', ptr(img_tokens), ptr(base_tokens), img_tokens.shape[0], int(base_shared), ptr(seq_img), ptr(src),
+             tokens, self.pa, ptr(self.eng.prep), ptr(ws), ptr(feats), n, self.vit.depth, int(mlp_path), stream_ptr())
+        return feats
+
     def relevance(self, ws, seed, out, scratch):
         """The dgrad chain alone with one relevance step per block (rovit_vit_backward_relevance): out (n,197) = row 0 of R_L."""
         n = out.shape[0]

@@ -69,6 +69,8 @@ SIGNATURES = {
     'rovit_vit_backward_input': (_i, [_vp] * 6 + [_i] * 5 + [_vp] + [_vp, _i, _f, _i]),
     'rovit_vit_backward_relevance': (_i, [_vp] * 4 + [_i] * 3 + [_vp] * 3),
     'rovit_attention_relevance_step': (_i, [_vp] * 5 + [_i, _i, _vp]),
+    'rovit_vit_embed': (_i, [_vp] * 4 + [_i, _i, _vp]),
+    'rovit_vit_forward_tokens': (_i, [_vp, _vp, _i, _i, _vp, _vp, _i] + [_vp] * 4 + [_i, _i, _i, _vp]),
     'rovit_gemm_nt': (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _vp]),
     'rovit_gemm_resid_ln': (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp]),
     'rovit_mlp_stream_bytes': (_sz, []),
