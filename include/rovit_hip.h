@@ -281,6 +281,13 @@ int rovit_vit_backward(const float* images, const float* d_features, const float
 size_t rovit_vit_f32_workspace_bytes(int batch);
 int rovit_vit_forward_f32(const float* images, const float* const* params, void* workspace, float* features, int batch, int depth,
                           rovit_stream_t stream);
+/* Where an activation of the fp32 forward lives inside its workspace (rovit_vit_f32_workspace_bytes(batch)): byte offset in *offset,
+ * extent in *bytes; host-only, no launch.  All fp32, row-major, M = batch * 197 token rows:
+ *   X: (M,192) the residual stream;  QKV: (M,576);  ATTN_O: (M,192) the attention output before proj;  ACT: (M,768) gelu(fc1)
+ * After rovit_vit_forward_f32(..., depth = d) they hold block d-1's values (X: the stream leaving it) for EVERY row, in the one-chain
+ * and in the two-chain schedule alike (the chains write disjoint row ranges of the same buffers). */
+enum { ROVIT_F32_WS_X = 0, ROVIT_F32_WS_QKV = 1, ROVIT_F32_WS_ATTN_O = 2, ROVIT_F32_WS_ACT = 3 };
+int rovit_vit_f32_workspace_field(int batch, int field, size_t* offset, size_t* bytes);
 /* Where a saved activation / backward temporary of block `block` lives inside a TRAINING workspace
  * (rovit_vit_workspace_bytes(batch, depth, 1)): byte offset in *offset, extent in *bytes.  This is what the
  * explainability taps read (reference explainability/gradcam.py:18-60 hooks blocks[-1].norm1 for activations and
@@ -289,7 +296,9 @@ int rovit_vit_forward_f32(const float* images, const float* const* params, void*
  *   QKV: bf16 (M,576); ATTN_O: bf16 (M,192) attention output before proj; ACT: bf16 gelu(fc1), (M,768) row-major when the
  *   two-launch MLP half ran (mlp_path, see rovit_vit_forward), CHUNK-MAJOR [24][M][32] when the one-launch half did
  *   DQKV: bf16 (M,576) gradient w.r.t. the qkv output of `block`, valid after rovit_vit_backward has processed that
- *   block and before it processes block-2 (call it with first_block = last_block = block, then read) */
+ *   block and before it processes block-2 (call it with first_block = last_block = block, then read)
+ * The last block (block = depth-1) runs everything behind its attention on the class-token rows alone: its ATTN_O, XHAT2, RSTD2 and
+ * ACT are written on rows b*197 (b < batch) only, the other rows of those buffers hold nothing meaningful (ACT row-major there). */
 enum { ROVIT_WS_XHAT1 = 0, ROVIT_WS_RSTD1 = 1, ROVIT_WS_QKV = 2, ROVIT_WS_ATTN_O = 3, ROVIT_WS_XHAT2 = 4, ROVIT_WS_RSTD2 = 5,
        ROVIT_WS_ACT = 6, ROVIT_WS_DQKV = 7 };
 int rovit_vit_workspace_field(int batch, int depth, int field, int block, size_t* offset, size_t* bytes);

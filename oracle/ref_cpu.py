@@ -323,6 +323,70 @@ def vit_forward(x: torch.Tensor, sd: Dict[str, torch.Tensor], prefix: str = '', 
     return t[:, 0]
 
 
+def vit_embed(x: torch.Tensor, sd: Dict[str, torch.Tensor], prefix: str = '') -> torch.Tensor:
+    """The residual stream entering block 0, (B, 197, dim): vit_forward's patch conv, class token and position embedding."""
+    B = x.shape[0]
+    t = F.conv2d(x, sd[prefix + 'patch_embed.proj.weight'], sd[prefix + 'patch_embed.proj.bias'], stride=VIT_PATCH)
+    t = t.flatten(2).transpose(1, 2)
+    return torch.cat([sd[prefix + 'cls_token'].expand(B, -1, -1), t], dim=1) + sd[prefix + 'pos_embed']
+
+
+def _ln_taps(t: torch.Tensor, eps: float):
+    """LayerNorm of the rows of t without its affine, and 1 / sqrt(var + eps) (biased variance), in t's dtype."""
+    var = t.var(dim=-1, unbiased=False, keepdim=True)
+    return F.layer_norm(t, (t.shape[-1],), None, None, eps), (var + eps).rsqrt().squeeze(-1)
+
+
+def vit_block_forward(t: torch.Tensor, sd: Dict[str, torch.Tensor], i: int, prefix: str = '', heads: int = VIT_HEADS,
+                      eps: float = 1e-6, taps: Optional[dict] = None) -> torch.Tensor:
+    """Block i of vit_forward from the residual stream t (B, N, dim) entering it, in t's dtype; returns the stream leaving it.
+    The operations are vit_forward's, in its order.  ``taps`` (a dict) receives the block's intermediate values:
+      t_in, xhat1 / rstd1 (norm1 without its affine, and its 1/sqrt(var + eps)), qkv (B,N,3 dim), attn_o (the attention output
+      before proj, (B,N,dim)), xhat2 / rstd2, act (gelu(fc1), (B,N,mlp)), t_out."""
+    B = t.shape[0]
+    dim = t.shape[-1]
+    hd = dim // heads
+    b = f'{prefix}blocks.{i}.'
+    t_in = t
+    h = F.layer_norm(t, (dim,), sd[b + 'norm1.weight'], sd[b + 'norm1.bias'], eps)
+    qkv_rows = F.linear(h, sd[b + 'attn.qkv.weight'], sd[b + 'attn.qkv.bias'])
+    qkv = qkv_rows.reshape(B, -1, 3, heads, hd).permute(2, 0, 3, 1, 4)
+    q, k, v = qkv[0], qkv[1], qkv[2]
+    a = torch.softmax((q * hd ** -0.5) @ k.transpose(-2, -1), dim=-1)
+    o = (a @ v).transpose(1, 2).reshape(B, -1, dim)
+    t = t + F.linear(o, sd[b + 'attn.proj.weight'], sd[b + 'attn.proj.bias'])
+    t_mid = t
+    h = F.layer_norm(t, (dim,), sd[b + 'norm2.weight'], sd[b + 'norm2.bias'], eps)
+    act = F.gelu(F.linear(h, sd[b + 'mlp.fc1.weight'], sd[b + 'mlp.fc1.bias']))
+    t = t + F.linear(act, sd[b + 'mlp.fc2.weight'], sd[b + 'mlp.fc2.bias'])
+    if taps is not None:
+        taps['t_in'] = t_in
+        taps['xhat1'], taps['rstd1'] = _ln_taps(t_in, eps)
+        taps['qkv'] = qkv_rows
+        taps['attn_o'] = o
+        taps['xhat2'], taps['rstd2'] = _ln_taps(t_mid, eps)
+        taps['act'] = act
+        taps['t_out'] = t
+    return t
+
+
+def vit_block_taps(x: torch.Tensor, sd: Dict[str, torch.Tensor], prefix: str = '', heads: int = VIT_HEADS, eps: float = 1e-6,
+                   depth: Optional[int] = None):
+    """vit_forward with every block's intermediate values kept (vit_block_forward's taps), in the dtype of x and sd.
+    Returns (taps, features): one dict per block and the final LayerNorm of the class-token row, as vit_forward returns it.
+    ``depth``: run only the first ``depth`` blocks (features then come from the stream leaving block depth - 1)."""
+    t = vit_embed(x, sd, prefix)
+    n = 0
+    while f'{prefix}blocks.{n}.norm1.weight' in sd and (depth is None or n < depth):
+        n += 1
+    out = []
+    for i in range(n):
+        out.append({})
+        t = vit_block_forward(t, sd, i, prefix, heads, eps, out[-1])
+    dim = t.shape[-1]
+    return out, F.layer_norm(t, (dim,), sd[prefix + 'norm.weight'], sd[prefix + 'norm.bias'], eps)[:, 0]
+
+
 def hf_vit_state_to_timm(hf_sd: Dict[str, torch.Tensor], depth: int) -> Dict[str, torch.Tensor]:
     """Weight mapping transformers.ViTModel -> timm key names."""
     sd = {'cls_token': hf_sd['embeddings.cls_token'], 'pos_embed': hf_sd['embeddings.position_embeddings'],

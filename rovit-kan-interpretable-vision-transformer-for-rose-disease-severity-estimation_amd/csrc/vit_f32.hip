@@ -48,9 +48,11 @@ constexpr int GBM = 128, GBK = 32, GST = GBK + 4;                // GST: LDS row
 //        element-wise order of ln_f32_kernel -- on the staging registers before they go to LDS; gamma / beta and the tile's (mean, rstd) wait in
 //        LDS (2.5 KB).
 // One-pass variance in fp32 is good to ~2e-7 (1 + mean^2 / var): fine for the model's rows (|mean| below the spread), not for a row that is a
-// large offset plus a small signal.  The consumer therefore checks mean^2 > 64 var per row and, for such a row only, recomputes both moments
-// from the row itself in two passes with fp64 accumulators (192 loads by one thread: never taken on the model's own activations, ~2 us per flagged tile when it
-// is; tests: a backbone with its position embedding shifted by +300).  Carrying the sums in fp64 instead was measured: 6.87 -> 6.95 ms per 256
+// large offset plus a small signal.  The consumer therefore checks mean^2 > var per row and, for such a row only, recomputes both moments
+// from the row itself in two passes with fp64 accumulators (192 loads by one thread: never taken on the model's own activations, whose largest
+// mean^2 / var is ~0.1; ~2 us per flagged tile when it is; tests: a backbone with its position embedding shifted by +300, and rows at
+// mean^2 / var from 0 to 1e4 in tests/test_gpu_token_rows.py).  The switch stood at mean^2 > 64 var until those rows showed the qkv and fc1
+// outputs of rows just below it 6-9x further from fp64 than the fp32 CPU oracle's; at batch 256 the forward takes 6.9 ms either way.  Carrying the sums in fp64 instead was measured: 6.87 -> 6.95 ms per 256
 // images for the 64-bit butterfly.  (Whole model against the CPU oracle: features 3.6e-6, as before the fold.)
 struct F32Ln {
   const float* stats_in;      // LNA
@@ -100,7 +102,7 @@ __global__ __launch_bounds__(256 * WN, WN == 2 ? 2 : 5) void gemm_f32_mfma_kerne
       const float* sp = ln.stats_in + (size_t)m * 6;
       float mean = ((sp[0] + sp[2]) + sp[4]) * (1.f / D);
       float var = fmaxf(((sp[1] + sp[3]) + sp[5]) * (1.f / D) - mean * mean, 0.f);
-      if (mean * mean > 64.f * var) {                                // ill-conditioned for the one-pass form: two passes over the row itself
+      if (mean * mean > var) {                                       // ill-conditioned for the one-pass form: two passes over the row itself
         const float* xr = A + (size_t)m * lda;                       // (fp64 accumulators: the path is rare, its accuracy is the point)
         double s1 = 0.0, s2 = 0.0;
         for (int k = 0; k < D; ++k) s1 += (double)xr[k];
@@ -453,6 +455,22 @@ ForkJoin* fork_join() {
 extern "C" size_t rovit_vit_f32_workspace_bytes(int batch) {
   const size_t M = (size_t)batch * T;
   return al(M * D * 4) * 3 + al(M * 3 * D * 4) + al(M * MLP * 4);
+}
+
+// where X / qkv / o / h live in that workspace (include/rovit_hip.h: rovit_vit_f32_workspace_field); the offsets are the ones
+// rovit_vit_forward_f32 carves below, and both half-batch chains write their rows of the same buffers
+extern "C" int rovit_vit_f32_workspace_field(int batch, int field, size_t* offset, size_t* bytes) {
+  ROVIT_CHECK_ARG(offset && bytes, ROVIT_ERR_NULL, "vit_f32_workspace_field: null output pointer");
+  ROVIT_CHECK_ARG(batch > 0, ROVIT_ERR_SHAPE, "vit_f32_workspace_field: bad batch %d", batch);
+  const size_t M = (size_t)batch * T, xs = al(M * D * 4);
+  switch (field) {
+    case ROVIT_F32_WS_X: *offset = 0; *bytes = M * D * 4; break;
+    case ROVIT_F32_WS_ATTN_O: *offset = 2 * xs; *bytes = M * D * 4; break;
+    case ROVIT_F32_WS_QKV: *offset = 3 * xs; *bytes = M * 3 * D * 4; break;
+    case ROVIT_F32_WS_ACT: *offset = 3 * xs + al(M * 3 * D * 4); *bytes = M * MLP * 4; break;
+    default: rovit_set_error("vit_f32_workspace_field: unknown field %d", field); return ROVIT_ERR_SHAPE;
+  }
+  return ROVIT_OK;
 }
 
 // images fp32 NCHW (B,3,224,224) -> features fp32 (B,192), every operation in fp32 (see the file header).  params as for

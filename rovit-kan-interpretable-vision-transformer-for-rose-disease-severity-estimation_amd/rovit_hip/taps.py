@@ -57,16 +57,33 @@ _FIELD_DTYPE = {WS_XHAT1: (torch.bfloat16, 192), WS_QKV: (torch.bfloat16, 576), 
 def workspace_view(ws: torch.Tensor, batch: int, depth: int, field: int, block: int, mlp_path: int = native.MLP_AUTO) -> torch.Tensor:
     """(M, width) view of one saved buffer of a training workspace -- zero-copy, except WS_ACT when the one-launch MLP half wrote it
     (mlp_path of the forward, see include/rovit_hip.h): that buffer is CHUNK-MAJOR [24][M][32] and is de-interleaved into a row-major
-    copy here (round 3 returned the raw bytes under a row-major shape)."""
+    copy here (round 3 returned the raw bytes under a row-major shape).
+    The last block's WS_ATTN_O, WS_XHAT2, WS_RSTD2 and WS_ACT are written on the class-token rows b * 197 only: for those the view is
+    (batch, width), just those rows."""
     off, nbytes = ctypes.c_size_t(), ctypes.c_size_t()
     call('rovit_vit_workspace_field', batch, depth, field, block, ctypes.byref(off), ctypes.byref(nbytes))
     dt, width = _FIELD_DTYPE[field]
     M = batch * 197
     flat = ws[off.value:off.value + nbytes.value].view(dt)
+    if block == depth - 1 and field in (WS_ATTN_O, WS_XHAT2, WS_RSTD2, WS_ACT):
+        return flat.view(batch, 197, width)[:, 0]
     if field == WS_ACT and (mlp_path == native.MLP_ONE_LAUNCH or (mlp_path == native.MLP_AUTO and M >= native.MLP_FUSED_MIN_ROWS)) \
             and block != depth - 1:            # (the last block's MLP half runs on the CLS rows with the two-launch kernels: row-major)
         return flat.view(24, M, 32).permute(1, 0, 2).reshape(M, width)
     return flat.view(M, width)
+
+
+# ---- views into the fp32 forward's workspace (include/rovit_hip.h: rovit_vit_f32_workspace_field) ---------------------
+F32_WS_X, F32_WS_QKV, F32_WS_ATTN_O, F32_WS_ACT = range(4)
+_F32_FIELD_WIDTH = {F32_WS_X: 192, F32_WS_QKV: 576, F32_WS_ATTN_O: 192, F32_WS_ACT: 768}
+
+
+def f32_workspace_view(ws: torch.Tensor, batch: int, field: int) -> torch.Tensor:
+    """(M, width) fp32 zero-copy view of one buffer of a rovit_vit_forward_f32 workspace: after a call with depth = d it holds block
+    d-1's values for every token row (F32_WS_X: the residual stream leaving the block)."""
+    off, nbytes = ctypes.c_size_t(), ctypes.c_size_t()
+    call('rovit_vit_f32_workspace_field', batch, field, ctypes.byref(off), ctypes.byref(nbytes))
+    return ws[off.value:off.value + nbytes.value].view(torch.float32).view(batch * 197, _F32_FIELD_WIDTH[field])
 
 
 def norm1_output(model, block: int) -> torch.Tensor:

@@ -4,6 +4,7 @@ import hashlib
 import os
 
 import numpy as np
+import pytest
 import torch
 
 from oracle import ref_cpu
@@ -201,3 +202,81 @@ def test_philox_restatement_against_the_published_known_answer_vectors():
         assert abs(float((m > 0).mean()) - 0.7) < 0.03
     assert not np.array_equal(masks[0], masks[1])
     assert not np.array_equal(masks[0], head_phase_masks(64, 128, 0.3, 1234, 44)[0])          # another offset, another draw
+
+
+# ---- per-block taps of the backbone (vit_block_taps / vit_block_forward) ------------------------------------------------
+
+def test_vit_block_taps_reproduce_vit_forward_bit_for_bit():
+    """The taps run vit_forward's operations in its order: the same features, and the blocks chained through vit_block_forward
+    from the first block's t_in give the same streams."""
+    g = torch.Generator().manual_seed(21)
+    sd = ref_cpu.init_vit_state(3, g)
+    x = torch.randn(2, 3, 224, 224, generator=g)
+    with torch.no_grad():
+        taps, feats = ref_cpu.vit_block_taps(x, sd)
+        want = ref_cpu.vit_forward(x, sd)
+        assert torch.equal(feats, want)
+        assert torch.equal(taps[0]['t_in'], ref_cpu.vit_embed(x, sd))
+        for i, tp in enumerate(taps):
+            assert torch.equal(ref_cpu.vit_block_forward(tp['t_in'], sd, i), tp['t_out'])
+            if i:
+                assert torch.equal(tp['t_in'], taps[i - 1]['t_out'])
+        assert torch.equal(taps[-1]['t_out'], ref_cpu.vit_forward(x, sd, return_tokens=True))
+    # shapes, and the LayerNorm taps are the normalised rows without the affine
+    tp = taps[1]
+    assert tp['qkv'].shape == (2, 197, 576) and tp['attn_o'].shape == (2, 197, 192) and tp['act'].shape == (2, 197, 768)
+    assert tp['rstd1'].shape == (2, 197) and tp['rstd2'].shape == (2, 197)
+    t = tp['t_in'].double()
+    xh = (t - t.mean(-1, keepdim=True)) / (t.var(-1, unbiased=False, keepdim=True) + 1e-6).sqrt()
+    assert float((tp['xhat1'].double() - xh).abs().max()) < 1e-5
+    assert float((tp['xhat1'].double() * tp['rstd1'].double().reciprocal().unsqueeze(-1) - (t - t.mean(-1, keepdim=True))).abs().max()) < 1e-5
+
+
+def _hf_vit(sd, depth):
+    """transformers.ViTModel built from a local config holding the weights of sd (the mapping of oracle/make_golden.py)."""
+    tr = pytest.importorskip('transformers')
+    cfg = tr.ViTConfig(hidden_size=192, num_hidden_layers=depth, num_attention_heads=3, intermediate_size=768, layer_norm_eps=1e-6,
+                       qkv_bias=True, hidden_act='gelu', hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0, image_size=224,
+                       patch_size=16)
+    vm = tr.ViTModel(cfg, add_pooling_layer=False).eval()
+    hf = vm.state_dict()
+    if 'layers.0.attention.q_proj.weight' not in hf:
+        pytest.skip('transformers with the older ViT parameter names')
+    with torch.no_grad():
+        hf['embeddings.cls_token'].copy_(sd['cls_token'])
+        hf['embeddings.position_embeddings'].copy_(sd['pos_embed'])
+        hf['embeddings.patch_embeddings.projection.weight'].copy_(sd['patch_embed.proj.weight'])
+        hf['embeddings.patch_embeddings.projection.bias'].copy_(sd['patch_embed.proj.bias'])
+        hf['layernorm.weight'].copy_(sd['norm.weight']); hf['layernorm.bias'].copy_(sd['norm.bias'])
+        for i in range(depth):
+            s, d = f'layers.{i}.', f'blocks.{i}.'
+            for n, w, b in zip('qkv', sd[d + 'attn.qkv.weight'].chunk(3), sd[d + 'attn.qkv.bias'].chunk(3)):
+                hf[s + f'attention.{n}_proj.weight'].copy_(w); hf[s + f'attention.{n}_proj.bias'].copy_(b)
+            for hn, tn in (('attention.o_proj', 'attn.proj'), ('layernorm_before', 'norm1'), ('layernorm_after', 'norm2'),
+                           ('mlp.fc1', 'mlp.fc1'), ('mlp.fc2', 'mlp.fc2')):
+                hf[s + hn + '.weight'].copy_(sd[d + tn + '.weight']); hf[s + hn + '.bias'].copy_(sd[d + tn + '.bias'])
+    vm.load_state_dict(hf)
+    return vm
+
+
+def test_vit_block_taps_every_residual_stream_row_matches_transformers():
+    """Every layer's residual stream, every token row, against transformers.ViTModel's hidden_states (the independent implementation of the
+    DeiT-Tiny arithmetic), both run in fp64: the features alone barely see a wrong patch row (the last block does not consume them at all)."""
+    depth, B = 4, 2
+    g = torch.Generator().manual_seed(22)
+    sd = {k: v.double() for k, v in ref_cpu.init_vit_state(depth, g).items()}
+    x = torch.randn(B, 3, 224, 224, generator=g, dtype=torch.float64)
+    vm = _hf_vit(sd, depth).double()
+    with torch.no_grad():
+        hs = vm(pixel_values=x, output_hidden_states=True).hidden_states
+        taps, feats = ref_cpu.vit_block_taps(x, sd)
+        final = vm(pixel_values=x).last_hidden_state[:, 0]
+    assert len(hs) == depth + 1
+    streams = [taps[0]['t_in']] + [tp['t_out'] for tp in taps]
+    worst = 0.0
+    for i, (h, t) in enumerate(zip(hs, streams)):
+        err = (h - t).abs().amax(-1) / t.abs().amax(-1).clamp_min(1.0)           # per row, relative to the row's scale
+        worst = max(worst, float(err.max()))
+        assert float(err.max()) < 1e-12, (i, float(err.max()))
+    print(f'per-row residual streams vs transformers (fp64): {worst:.2e}')
+    assert float((final - feats).abs().max()) < 1e-12
