@@ -521,6 +521,64 @@ int rovit_joint_loss(const float* cls_logits, const float* ordinal_logits, const
                      rovit_stream_t stream);
 int rovit_scale_buffers(float* const* bufs, const int* counts, int n, const float* scale, rovit_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Test-set evaluation and validation without a per-batch host round trip (evaluate.hip).
+ * rovit_eval_accumulate replaces the collection part of Evaluator.evaluate (evaluation/evaluator.py:37-67: softmax, argmax,
+ * squeeze, exp(0.5 log_var) and five device-to-host copies per batch) and of Trainer.val_epoch (training/trainer.py:183-231: six
+ * .item() per batch): ONE launch per batch writes rows [offset, offset + batch) of the caller's record arrays (capacity rows each):
+ *   probs (capacity, C) = softmax with expf(logit - row max);  pred = FIRST argmax of those fp32 probabilities (torch.argmax /
+ *   np.argmax);  label (a class label outside [0, C) is recorded as -1 and counted by the finalise);  sev_pred = kan_severity, or the
+ *   severity label as float when kan_severity is NULL (evaluator.py:50-53);  sev_true;  uncertainty = exp(0.5 log_var) (NaN when
+ *   log_var is NULL).  losses (the five floats rovit_joint_loss left on the device) go to row loss_row of loss_table (loss_capacity, 5).
+ * The host knows the row offset, so there is no device counter and no synchronisation; every value is per-sample.
+ * rovit_eval_finalize replaces evaluation/metrics.py:9-61,96-122 (accuracy, f1_score, confusion_matrix,
+ * precision_recall_fscore_support, mae, spearmanr, brier_score, ece): once per epoch it reduces the n recorded rows to `result`,
+ * ROVIT_EVAL_RESULT_WORDS 8-byte words:
+ *   int64  [ROVIT_EVAL_CONFUSION + t * C + p] confusion matrix   [ROVIT_EVAL_BIN_COUNT + k], [ROVIT_EVAL_BIN_CORRECT + k] per ECE bin
+ *          [ROVIT_EVAL_RANK + 0..2] sum (Ra-n-1)(Rb-n-1), sum (Ra-n-1)^2, sum (Rb-n-1)^2 with the doubled tie-averaged rank
+ *          R_i = 2 #{x_j < x_i} + #{x_j == x_i} + 1 of sev_true (a) and sev_pred (b), counted, not sorted (exact for n <= 2^20)
+ *          [ROVIT_EVAL_NONFINITE + 0..1] non-finite values in sev_true / sev_pred   [ROVIT_EVAL_BAD_LABELS]   [ROVIT_EVAL_N]
+ *   double [ROVIT_EVAL_BIN_CONF + k] sum of confidences per bin (lo < conf <= hi against bin_edges, n_bins + 1 doubles, conf widened)
+ *          [ROVIT_EVAL_BRIER] sum_i sum_c (p_ic - onehot_ic)^2   [ROVIT_EVAL_ABS_ERR] sum |sev_true - sev_pred|
+ *          [ROVIT_EVAL_LOSS + 0..4] column sums of the first n_loss_rows rows of loss_table
+ * Integers are added with integer atomics (order cannot change them); every floating sum is fp64 over a fixed partition of the rows
+ * (256-row chunks, fixed tree inside and across chunks): bit-identical from run to run and independent of the batch split.
+ * The whole block is zeroed first, so words nothing writes (bins beyond n_bins, padding) are 0 and blocks compare byte for byte.
+ * Workspaces (device, caller's): rank_counts 4 n uint32, partials rovit_eval_partials_doubles(n) doubles.
+ * Both refuse a bad descriptor before any launch.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define ROVIT_EVAL_MAX_CLASSES 8
+#define ROVIT_EVAL_MAX_BINS 64
+#define ROVIT_EVAL_MAX_ROWS (1 << 20)
+enum {
+  ROVIT_EVAL_CONFUSION = 0, ROVIT_EVAL_BIN_COUNT = 64, ROVIT_EVAL_BIN_CORRECT = 128, ROVIT_EVAL_RANK = 192, ROVIT_EVAL_NONFINITE = 195,
+  ROVIT_EVAL_BAD_LABELS = 197, ROVIT_EVAL_N = 198, ROVIT_EVAL_INT_WORDS = 200,
+  ROVIT_EVAL_BIN_CONF = 200, ROVIT_EVAL_BRIER = 264, ROVIT_EVAL_ABS_ERR = 265, ROVIT_EVAL_LOSS = 266, ROVIT_EVAL_RESULT_WORDS = 272
+};
+typedef struct rovit_eval_batch {
+  int batch, num_classes, offset, capacity, severity_is_int64, loss_row, loss_capacity;
+  const float* cls_logits;          /* (batch, C) */
+  const float* kan_severity;        /* (batch) or NULL */
+  const float* log_var;             /* (batch) or NULL */
+  const long long* class_labels;    /* (batch) */
+  const void* severity_labels;      /* (batch) fp32, or int64 with severity_is_int64 != 0 */
+  const float* losses;              /* [5] or NULL */
+  float* probs; int* pred; int* label; float* sev_pred; float* sev_true; float* uncertainty;
+  float* loss_table;                /* (loss_capacity, 5); required with losses */
+} rovit_eval_batch;
+typedef struct rovit_eval_final {
+  int n, num_classes, n_bins, n_loss_rows;
+  const float* probs; const int* pred; const int* label; const float* sev_pred; const float* sev_true;
+  const float* loss_table;          /* required when n_loss_rows > 0 */
+  const double* bin_edges;          /* n_bins + 1 */
+  unsigned int* rank_counts;        /* workspace, 4 n */
+  double* partials;                 /* workspace, rovit_eval_partials_doubles(n) */
+  void* result;                     /* ROVIT_EVAL_RESULT_WORDS 8-byte words */
+} rovit_eval_final;
+size_t rovit_eval_partials_doubles(int n);
+int rovit_eval_accumulate(const rovit_eval_batch* p, rovit_stream_t stream);
+int rovit_eval_finalize(const rovit_eval_final* p, rovit_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,8 @@ void rovit_set_error(const char* fmt, ...) {
 // (rovit_attention_relevance_step and rovit_vit_backward_relevance were added at 440 the same way: attention relevance, relevance.hip.)
 // (rovit_vit_embed and rovit_vit_forward_tokens were added at 440 the same way: deletion / insertion curves, perturb.hip.)
 // (rovit_vit_f32_workspace_field was added at 440 the same way: a host-only view of the fp32 forward's workspace, vit_f32.hip.)
+// (rovit_eval_accumulate, rovit_eval_finalize and rovit_eval_partials_doubles were added at 440 the same way: test-set evaluation and
+// validation with one synchronisation per epoch, evaluate.hip.)
 extern "C" int rovit_version(void) { return 440; }
 extern "C" const char* rovit_last_error_string(void) { return g_err; }
 

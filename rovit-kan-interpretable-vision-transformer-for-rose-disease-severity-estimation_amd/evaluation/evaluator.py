@@ -1,0 +1,92 @@
+"""The reference's evaluation/evaluator.py (:16-110 Evaluator, :226-253 load_model_for_evaluation) on ``rovit_hip.evaluation``: one
+launch per batch records the predictions on the device, one launch per epoch reduces them, one device-to-host copy brings the result
+block back.  Same constructor, same returned dict, same printed table, same ``evaluation_results.txt``.  Figures are not drawn
+(SURVEY.md section 2); ``evaluate(return_arrays=True)`` hands back the arrays the reference's plots are made from.  A last batch of one
+sample works (the reference's ``squeeze()`` + ``np.concatenate`` raises there)."""
+from pathlib import Path
+from typing import Dict
+
+import torch
+
+from evaluation.metrics import count_params, fps
+from rovit_hip.evaluation import EvalAccumulator, class_table
+
+RULE = '=' * 60
+
+
+class Evaluator:
+
+    def __init__(self, model, test_loader, config, device):
+        self.model = model.to(device)
+        self.test_loader = test_loader
+        self.config = config
+        self.device = torch.device(device)
+        self.model.eval()
+        self.accumulator = None
+
+    def collect(self) -> EvalAccumulator:
+        """The collection loop alone: one forward and one record launch per batch, nothing copied to the host."""
+        acc = self.accumulator = EvalAccumulator(len(self.config.data.class_names))
+        self.model.eval()
+        with torch.no_grad():
+            for images, class_labels, severity_labels in self.test_loader:
+                acc.update(self.model(images.to(self.device)), class_labels, severity_labels)
+        return acc
+
+    def evaluate(self, return_arrays: bool = False):
+        print(f'\n{RULE}\nRunning Evaluation on Test Set\n{RULE}\n')
+        names = list(self.config.data.class_names)
+        acc = self.collect()
+        m = acc.compute()                                   # the loop's one synchronisation
+        metrics = {k: m[k] for k in ('accuracy', 'macro_f1', 'weighted_f1', 'mae', 'spearman_rho', 'spearman', 'brier_score', 'ece')}
+        metrics['fps'] = fps(self.model, (1, 3, 224, 224), self.device, n=100)
+        metrics['params'] = count_params(self.model)
+        metrics['params_m'] = metrics['params'] / 1e6
+        metrics['per_class'] = class_table(m['per_class'], names)
+        self._print_results(metrics)
+        self._save_results(metrics)
+        return (metrics, acc.arrays()) if return_arrays else metrics
+
+    @staticmethod
+    def _summary(metrics: Dict, rho_label: str):
+        rows = (('Accuracy:', f"{metrics['accuracy']:.2f}%"), ('Macro F1:', f"{metrics['macro_f1']:.2f}%"), ('MAE:', f"{metrics['mae']:.4f}"),
+                (rho_label, f"{metrics['spearman_rho']:.4f}"), ('Brier Score:', f"{metrics['brier_score']:.4f}"),
+                ('ECE:', f"{metrics['ece']:.4f}"), ('FPS:', f"{metrics['fps']:.1f}"), ('Parameters:', f"{metrics['params']:,}"))
+        return [f'{label:<16}{value}' for label, value in rows]
+
+    def _print_results(self, metrics: Dict) -> None:
+        print('\n'.join(['', RULE, 'Evaluation Results', RULE] + self._summary(metrics, 'Spearman rho:') + [RULE, '']))
+        print('Per-Class Metrics:')
+        print(f"{'Class':<20} {'Precision':<12} {'Recall':<12} {'F1-Score':<12} {'Support':<10}")
+        print('-' * 70)
+        for name, c in metrics['per_class'].items():
+            print(f"{name:<20} {c['precision']:>10.2f}%  {c['recall']:>10.2f}%  {c['f1']:>10.2f}%  {c['support']:>8}")
+        print()
+
+    def _save_results(self, metrics: Dict) -> None:
+        results_dir = getattr(getattr(self.config, 'paths', None), 'results_dir', None)
+        if results_dir is None:
+            return
+        results_dir = Path(results_dir)
+        results_dir.mkdir(parents=True, exist_ok=True)
+        lines = ['RoViT-KAN Evaluation Results', RULE, ''] + self._summary(metrics, "Spearman's rho:") + ['', 'Per-Class Metrics:', '-' * 60]
+        for name, c in metrics['per_class'].items():
+            lines += [f'{name}:', f"  Precision: {c['precision']:.2f}%", f"  Recall:    {c['recall']:.2f}%", f"  F1-Score:  {c['f1']:.2f}%",
+                      f"  Support:   {c['support']}", '']
+        path = results_dir / 'evaluation_results.txt'
+        path.write_text('\n'.join(lines) + '\n', encoding='utf-8')
+        print(f'Results saved to {path}')
+
+
+def load_model_for_evaluation(checkpoint_path: Path, config, device):
+    from models.rovit_kan import RoViTKAN
+    mc = config.model
+    model = RoViTKAN(embed_dim=mc.embed_dim, hidden_dim=mc.hidden_dim, num_classes=config.data.num_classes, kan_layers=mc.kan_layers,
+                     kan_num_knots=mc.kan_num_knots, kan_degree=mc.kan_degree, dropout=mc.dropout, pretrained=False)
+    checkpoint = torch.load(checkpoint_path, map_location=device, weights_only=False)
+    model.load_state_dict(checkpoint['model_state_dict'])
+    model.to(device)
+    model.eval()
+    print(f'Model loaded from {checkpoint_path}')
+    print(f"Checkpoint epoch: {checkpoint['epoch']}")
+    return model

@@ -1,0 +1,372 @@
+"""Test-set evaluation and validation with one device synchronisation per epoch.
+
+Replaces the collection loop of the reference's ``Evaluator.evaluate`` (evaluation/evaluator.py:37-67: softmax, argmax, squeeze,
+exp and five device-to-host copies per batch), the six ``.item()`` per batch of ``Trainer.val_epoch`` (training/trainer.py:183-231)
+and the sklearn / scipy calls of evaluation/metrics.py.
+
+``EvalAccumulator.update`` is ONE launch per batch (``rovit_eval_accumulate``): it records probabilities, predicted class, label,
+predicted and true severity, exp(0.5 log_var) and, optionally, the five loss values ``JointLoss`` left on the device, at a row offset
+the host already knows.  ``compute`` launches ``rovit_eval_finalize`` and copies its 272-word result block to the host: the epoch's only
+synchronisation.  Everything reported is derived from that block on the host in fp64.
+
+On CPU tensors the same class runs the plain torch / numpy fp64 restatement below (``result_block_from_arrays``), as
+``JointLoss._forward_tensor_ops`` does: the host logic is testable without a GPU, and ``evaluation.metrics`` is built on it.
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import native
+from .native import RovitHipError
+
+LOSS_KEYS = ('cls_loss', 'ord_loss', 'unc_loss', 'kan_loss', 'total_loss')        # order of rovit_joint_loss's losses_out
+
+
+# ---- host restatement (fp64 / exact integers) -----------------------------------------------------------------------------------
+
+def doubled_ranks(x: np.ndarray) -> np.ndarray:
+    """R_i = 2 #{x_j < x_i} + #{x_j == x_i} + 1: twice the tie-averaged rank, an exact integer (mean exactly n + 1)."""
+    x = np.asarray(x, dtype=np.float64).reshape(-1)
+    s = np.sort(x)
+    lo = np.searchsorted(s, x, side='left').astype(np.int64)
+    hi = np.searchsorted(s, x, side='right').astype(np.int64)
+    return 2 * lo + (hi - lo) + 1
+
+
+def rank_sums(a: np.ndarray, b: np.ndarray):
+    """(sum da db, sum da^2, sum db^2, non-finite in a, non-finite in b) with d = R - n - 1, as Python integers."""
+    a = np.asarray(a, dtype=np.float64).reshape(-1)
+    b = np.asarray(b, dtype=np.float64).reshape(-1)
+    n = a.shape[0]
+    bad_a, bad_b = int((~np.isfinite(a)).sum()), int((~np.isfinite(b)).sum())
+    if bad_a or bad_b:
+        return 0, 0, 0, bad_a, bad_b
+    da = (doubled_ranks(a) - (n + 1)).astype(object)          # Python integers: exact beyond int64 too
+    db = (doubled_ranks(b) - (n + 1)).astype(object)
+    return int((da * db).sum()), int((da * da).sum()), int((db * db).sum()), 0, 0
+
+
+def rho_from_rank_sums(sab: int, saa: int, sbb: int, bad_a: int = 0, bad_b: int = 0) -> float:
+    """Spearman's rho = Pearson correlation of the tie-averaged ranks; NaN for a constant column or any non-finite value."""
+    if bad_a or bad_b or saa <= 0 or sbb <= 0:
+        return float('nan')
+    return float(sab) / (math.sqrt(float(saa)) * math.sqrt(float(sbb)))
+
+
+def bin_edges(n_bins: int) -> np.ndarray:
+    return np.linspace(0, 1, n_bins + 1)
+
+
+def result_block_from_arrays(y_true, y_pred, y_probs, severity_true, severity_pred, num_classes: int, n_bins: int = 10,
+                             loss_rows: Optional[np.ndarray] = None) -> np.ndarray:
+    """The result block of ``rovit_eval_finalize`` (include/rovit_hip.h) from recorded arrays, on the host: int64 words with the fp64
+    section stored bit for bit.  Sums are over the whole arrays, so the block cannot depend on how the rows arrived."""
+    C = int(num_classes)
+    y_true = np.asarray(y_true).astype(np.int64).reshape(-1)
+    y_pred = np.asarray(y_pred).astype(np.int64).reshape(-1)
+    p = np.asarray(y_probs, dtype=np.float64).reshape(len(y_true), C)
+    st = np.asarray(severity_true, dtype=np.float64).reshape(-1)
+    sp = np.asarray(severity_pred, dtype=np.float64).reshape(-1)
+    n = len(y_true)
+    blk = np.zeros(native.EVAL_RESULT_WORDS, dtype=np.int64)
+    f = blk.view(np.float64)
+    ok = (y_true >= 0) & (y_true < C)
+    pred = np.clip(y_pred, 0, C - 1)
+    blk[native.EVAL_CONFUSION:native.EVAL_CONFUSION + C * C] = np.bincount(y_true[ok] * C + pred[ok], minlength=C * C)
+    conf = p[np.arange(n), pred]
+    edges = bin_edges(n_bins)
+    correct = pred == y_true
+    for k in range(n_bins):
+        m = (conf > edges[k]) & (conf <= edges[k + 1])
+        blk[native.EVAL_BIN_COUNT + k] = int(m.sum())
+        blk[native.EVAL_BIN_CORRECT + k] = int((m & correct).sum())
+        f[native.EVAL_BIN_CONF + k] = conf[m].sum()
+    onehot = np.zeros_like(p)
+    onehot[np.arange(n)[ok], y_true[ok]] = 1.0
+    f[native.EVAL_BRIER] = ((p - onehot) ** 2).sum(axis=1).sum()
+    f[native.EVAL_ABS_ERR] = np.abs(st - sp).sum()
+    sab, saa, sbb, bad_a, bad_b = rank_sums(st, sp)
+    blk[native.EVAL_RANK:native.EVAL_RANK + 3] = [sab, saa, sbb]
+    blk[native.EVAL_NONFINITE:native.EVAL_NONFINITE + 2] = [bad_a, bad_b]
+    blk[native.EVAL_BAD_LABELS] = int((~ok).sum())
+    blk[native.EVAL_N] = n
+    if loss_rows is not None and len(loss_rows):
+        f[native.EVAL_LOSS:native.EVAL_LOSS + 5] = np.asarray(loss_rows, dtype=np.float64).reshape(-1, 5).sum(axis=0)
+    return blk
+
+
+def prf_from_confusion(cm: np.ndarray):
+    """precision, recall, F1 (fractions) and support per class with sklearn's ``zero_division=0``."""
+    cm = np.asarray(cm, dtype=np.float64)
+    tp = np.diag(cm)
+    pred_n, true_n = cm.sum(axis=0), cm.sum(axis=1)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        prec = np.where(pred_n > 0, tp / pred_n, 0.0)
+        rec = np.where(true_n > 0, tp / true_n, 0.0)
+        f1 = np.where(pred_n + true_n > 0, 2.0 * tp / (pred_n + true_n), 0.0)
+    return prec, rec, f1, true_n.astype(np.int64)
+
+
+def f1_averages(cm: np.ndarray):
+    """(macro, weighted) F1 as fractions.  Macro averages over the classes that occur in the labels or the predictions, which is what
+    ``f1_score(average='macro')`` without ``labels=`` does; weighted weighs by support."""
+    _, _, f1, support = prf_from_confusion(cm)
+    cm = np.asarray(cm)
+    present = (cm.sum(axis=0) + cm.sum(axis=1)) > 0
+    macro = float(f1[present].mean()) if present.any() else 0.0
+    weighted = float((f1 * support).sum() / support.sum()) if support.sum() > 0 else 0.0
+    return macro, weighted
+
+
+def metrics_from_block(blk: np.ndarray, num_classes: int, n_bins: int, n_loss_rows: int = 0) -> Dict:
+    """Every reported metric from one result block (reference units: percent where evaluation/metrics.py returns percent)."""
+    C = int(num_classes)
+    blk = np.asarray(blk, dtype=np.int64)
+    f = blk.view(np.float64)
+    n = int(blk[native.EVAL_N])
+    if n < 1:
+        raise RovitHipError('evaluation: no samples recorded')
+    if int(blk[native.EVAL_BAD_LABELS]):
+        raise RovitHipError(f'evaluation: {int(blk[native.EVAL_BAD_LABELS])} class labels outside [0, {C})')
+    cm = blk[native.EVAL_CONFUSION:native.EVAL_CONFUSION + C * C].reshape(C, C).copy()
+    prec, rec, f1, support = prf_from_confusion(cm)
+    macro, weighted = f1_averages(cm)
+    ece = 0.0
+    for k in range(n_bins):
+        cnt = int(blk[native.EVAL_BIN_COUNT + k])
+        if cnt > 0:
+            ece += abs(f[native.EVAL_BIN_CONF + k] / cnt - int(blk[native.EVAL_BIN_CORRECT + k]) / cnt) * (cnt / n)
+    rho = rho_from_rank_sums(*(int(v) for v in blk[native.EVAL_RANK:native.EVAL_RANK + 5]))
+    m = {'n': n, 'correct': int(np.trace(cm)), 'accuracy': float(np.trace(cm)) / n * 100.0, 'macro_f1': macro * 100.0, 'weighted_f1': weighted * 100.0,
+         'mae': float(f[native.EVAL_ABS_ERR]) / n, 'spearman_rho': rho, 'spearman': rho, 'brier_score': float(f[native.EVAL_BRIER]) / n,
+         'ece': float(ece), 'confusion_matrix': cm,
+         'per_class': [{'precision': float(prec[c]) * 100.0, 'recall': float(rec[c]) * 100.0, 'f1': float(f1[c]) * 100.0,
+                        'support': int(support[c])} for c in range(C)]}
+    if n_loss_rows > 0:
+        sums = f[native.EVAL_LOSS:native.EVAL_LOSS + 5]
+        for k, name in enumerate(LOSS_KEYS):
+            m['loss' if name == 'total_loss' else name] = float(sums[k]) / n_loss_rows          # means over BATCHES (trainer.py:221-228)
+    return m
+
+
+# ---- the accumulator ---------------------------------------------------------------------------------------------------------
+
+def _loss_vector(losses) -> torch.Tensor:
+    """The five loss values as one contiguous fp32 vector [cls, ord, unc, kan, total], without a launch when they already are one
+    (``JointLoss`` on the device returns views of the kernel's five-float output)."""
+    if isinstance(losses, torch.Tensor):
+        v = losses.detach().reshape(-1)
+        if v.numel() != 5:
+            raise RovitHipError(f'evaluation: a loss tensor must hold 5 values [cls, ord, unc, kan, total], got {v.numel()}')
+        return v.float().contiguous()
+    ts = [losses[k].detach() for k in LOSS_KEYS]
+    base = ts[0]
+    if all(t.dtype == torch.float32 and t.numel() == 1 and t.device == base.device
+           and t.untyped_storage().data_ptr() == base.untyped_storage().data_ptr()
+           and t.storage_offset() == base.storage_offset() + i for i, t in enumerate(ts)):
+        return base.as_strided((5,), (1,), base.storage_offset())
+    return torch.stack([t.float().reshape(()) for t in ts])
+
+
+class EvalAccumulator:
+    """Streaming score card of one pass over a data set; see the module docstring.  ``update`` never synchronises."""
+
+    def __init__(self, num_classes: int, n_bins: int = 10, capacity: int = 4096):
+        if not (isinstance(num_classes, int) and 2 <= num_classes <= native.EVAL_MAX_CLASSES):
+            raise RovitHipError(f'EvalAccumulator: num_classes must be in 2..{native.EVAL_MAX_CLASSES}, got {num_classes!r}')
+        if not (isinstance(n_bins, int) and 1 <= n_bins <= native.EVAL_MAX_BINS):
+            raise RovitHipError(f'EvalAccumulator: n_bins must be in 1..{native.EVAL_MAX_BINS}, got {n_bins!r}')
+        if not (isinstance(capacity, int) and 1 <= capacity <= native.EVAL_MAX_ROWS):
+            raise RovitHipError(f'EvalAccumulator: capacity must be in 1..{native.EVAL_MAX_ROWS}, got {capacity!r}')
+        self.num_classes, self.n_bins, self._capacity0 = num_classes, n_bins, capacity
+        self.reset()
+
+    def reset(self) -> None:
+        self.n = 0
+        self.n_loss_rows = 0
+        self.device: Optional[torch.device] = None
+        self._has_uncertainty = False
+        self._rec: Dict[str, torch.Tensor] = {}
+        self._loss_table: Optional[torch.Tensor] = None
+        self._edges: Optional[torch.Tensor] = None
+        self._cpu: List[Dict[str, torch.Tensor]] = []          # CPU path: the batches as they came
+        self._cpu_losses: List[torch.Tensor] = []
+        self._block: Optional[np.ndarray] = None
+
+    # -- device record arrays --
+    _FIELDS = (('probs', torch.float32), ('pred', torch.int32), ('label', torch.int32), ('sev_pred', torch.float32),
+               ('sev_true', torch.float32), ('uncertainty', torch.float32))
+
+    def _alloc(self, cap: int) -> Dict[str, torch.Tensor]:
+        return {k: torch.empty((cap, self.num_classes) if k == 'probs' else (cap,), dtype=dt, device=self.device) for k, dt in self._FIELDS}
+
+    def _reserve(self, rows: int) -> None:
+        cap = self._rec['pred'].shape[0] if self._rec else 0
+        if rows <= cap:
+            return
+        if rows > native.EVAL_MAX_ROWS:
+            raise RovitHipError(f'EvalAccumulator: {rows} samples exceed the limit of {native.EVAL_MAX_ROWS} (the rank sums are exact in '
+                                'int64 up to there)')
+        new_cap = min(native.EVAL_MAX_ROWS, max(rows, 2 * cap, self._capacity0))
+        new = self._alloc(new_cap)
+        for k, t in self._rec.items():
+            new[k][:self.n].copy_(t[:self.n])             # device-to-device, stream-ordered: no synchronisation
+        self._rec = new
+
+    def _reserve_losses(self, rows: int) -> None:
+        cap = self._loss_table.shape[0] if self._loss_table is not None else 0
+        if rows <= cap:
+            return
+        new = torch.empty((max(rows, 2 * cap, 256), 5), dtype=torch.float32, device=self.device)
+        if self._loss_table is not None:
+            new[:self.n_loss_rows].copy_(self._loss_table[:self.n_loss_rows])
+        self._loss_table = new
+
+    def update(self, outputs: Dict[str, Optional[torch.Tensor]], class_labels: torch.Tensor, severity_labels: torch.Tensor,
+               losses=None) -> None:
+        """Record one batch: the model's output dict, the class labels and the severity labels (host or device tensors), and
+        optionally the dict ``JointLoss`` returned (or a 5-vector [cls, ord, unc, kan, total])."""
+        logits = outputs['cls_logits'].detach()
+        if logits.dim() != 2 or logits.shape[1] != self.num_classes or logits.shape[0] < 1:
+            raise RovitHipError(f'EvalAccumulator.update: cls_logits must be (B >= 1, {self.num_classes}), got {tuple(logits.shape)}')
+        B = logits.shape[0]
+        kan, lv = outputs.get('kan_severity'), outputs.get('log_var')
+        if outputs.get('mu') is None:
+            lv = None                                     # evaluator.py:64: uncertainty needs both mu and log_var
+        for name, t in (('kan_severity', kan), ('log_var', lv), ('class_labels', class_labels), ('severity_labels', severity_labels)):
+            if t is not None and t.numel() != B:
+                raise RovitHipError(f'EvalAccumulator.update: {name} has {t.numel()} values for a batch of {B}')
+        if self.device is None:
+            self.device = logits.device
+        elif logits.device != self.device:
+            raise RovitHipError(f'EvalAccumulator.update: batch on {logits.device}, earlier batches on {self.device}; reset() first')
+        self._block = None
+        if lv is not None:
+            self._has_uncertainty = True
+        if not logits.is_cuda:
+            self._cpu.append({'logits': logits.float(), 'kan': None if kan is None else kan.detach().float().reshape(-1),
+                              'lv': None if lv is None else lv.detach().float().reshape(-1),
+                              'label': class_labels.detach().long().reshape(-1).cpu(), 'sev': severity_labels.detach().reshape(-1).cpu()})
+            if losses is not None:
+                self._cpu_losses.append(_loss_vector(losses).cpu())
+                self.n_loss_rows += 1
+            self.n += B
+            return
+        dev = self.device
+        f = lambda t: None if t is None else t.detach().float().reshape(-1).contiguous()
+        logits, kan, lv = logits.float().contiguous(), f(kan), f(lv)
+        # host labels: an asynchronous copy on the current stream, not .numpy()
+        labels = class_labels.detach().reshape(-1).to(dev, non_blocking=True).long().contiguous()
+        sev = severity_labels.detach().reshape(-1).to(dev, non_blocking=True)
+        sev_i64 = sev.dtype == torch.int64
+        sev = (sev if sev_i64 else sev.float()).contiguous()
+        self._reserve(self.n + B)
+        lvec = None
+        if losses is not None:
+            lvec = _loss_vector(losses).to(dev, non_blocking=True)
+            self._reserve_losses(self.n_loss_rows + 1)
+        d = native.EvalBatch()
+        d.batch, d.num_classes, d.offset, d.capacity, d.severity_is_int64 = B, self.num_classes, self.n, self._rec['pred'].shape[0], int(sev_i64)
+        d.loss_row, d.loss_capacity = self.n_loss_rows, 0 if self._loss_table is None else self._loss_table.shape[0]
+        d.cls_logits, d.kan_severity, d.log_var = native.ptr(logits), native.ptr(kan), native.ptr(lv)
+        d.class_labels, d.severity_labels, d.losses = native.ptr(labels), native.ptr(sev), native.ptr(lvec)
+        for k, _ in self._FIELDS:
+            setattr(d, k, native.ptr(self._rec[k]))
+        d.loss_table = native.ptr(self._loss_table)
+        native.call('rovit_eval_accumulate', ctypes.byref(d), native.stream_ptr())
+        self.n += B
+        if lvec is not None:
+            self.n_loss_rows += 1
+
+    # -- results --
+    def _cpu_arrays(self):
+        cat = lambda k: torch.cat([b[k] for b in self._cpu])
+        logits = cat('logits')
+        probs = torch.softmax(logits, dim=1)
+        sev_true = torch.cat([b['sev'].float() for b in self._cpu])
+        sev_pred = torch.cat([b['sev'].float() if b['kan'] is None else b['kan'] for b in self._cpu])
+        unc = torch.cat([torch.full((len(b['label']),), float('nan')) if b['lv'] is None else torch.exp(0.5 * b['lv']) for b in self._cpu])
+        label = cat('label')
+        label = torch.where((label >= 0) & (label < self.num_classes), label, torch.full_like(label, -1))
+        return {'probs': probs.numpy(), 'pred': torch.argmax(probs, dim=1).numpy().astype(np.int32), 'label': label.numpy().astype(np.int32),
+                'sev_pred': sev_pred.numpy(), 'sev_true': sev_true.numpy(), 'uncertainty': unc.numpy()}
+
+    def result_block(self) -> np.ndarray:
+        """The finalise's result block as 272 int64 words on the host (fp64 section bit for bit).  On the device this is the epoch's
+        one synchronising call; the block is kept until the next ``update`` or ``reset``."""
+        if self._block is not None:
+            return self._block
+        if self.n < 1:
+            raise RovitHipError('EvalAccumulator: nothing recorded yet')
+        if not self.device.type == 'cuda':
+            a = self._cpu_arrays()
+            rows = torch.stack(self._cpu_losses).numpy() if self._cpu_losses else None
+            self._block = result_block_from_arrays(a['label'], a['pred'], a['probs'], a['sev_true'], a['sev_pred'], self.num_classes,
+                                                   self.n_bins, rows)
+            return self._block
+        dev = self.device
+        if self._edges is None:
+            self._edges = torch.from_numpy(bin_edges(self.n_bins)).to(dev, non_blocking=True)
+        counts = torch.empty(4 * self.n, dtype=torch.int32, device=dev)
+        partials = torch.empty(native.load().rovit_eval_partials_doubles(self.n), dtype=torch.float64, device=dev)
+        result = torch.empty(native.EVAL_RESULT_WORDS, dtype=torch.int64, device=dev)
+        d = native.EvalFinal()
+        d.n, d.num_classes, d.n_bins, d.n_loss_rows = self.n, self.num_classes, self.n_bins, self.n_loss_rows
+        for k in ('probs', 'pred', 'label', 'sev_pred', 'sev_true'):
+            setattr(d, k, native.ptr(self._rec[k]))
+        d.loss_table = native.ptr(self._loss_table)
+        d.bin_edges, d.rank_counts, d.partials, d.result = (native.ptr(t) for t in (self._edges, counts, partials, result))
+        native.call('rovit_eval_finalize', ctypes.byref(d), native.stream_ptr())
+        self._block = result.cpu().numpy()               # the single device-to-host copy of the epoch
+        return self._block
+
+    def compute(self) -> Dict:
+        return metrics_from_block(self.result_block(), self.num_classes, self.n_bins, self.n_loss_rows)
+
+    def arrays(self) -> Dict[str, Optional[np.ndarray]]:
+        """``y_true, y_pred, y_probs, severity_true, severity_pred, uncertainty`` as numpy (what the reference's plots need);
+        ``uncertainty`` is None when no batch carried mu and log_var."""
+        if self.n < 1:
+            raise RovitHipError('EvalAccumulator: nothing recorded yet')
+        if self.device.type == 'cuda':
+            a = {k: t[:self.n].cpu().numpy() for k, t in self._rec.items()}
+        else:
+            a = self._cpu_arrays()
+        return {'y_true': a['label'].astype(np.int64), 'y_pred': a['pred'].astype(np.int64), 'y_probs': a['probs'],
+                'severity_true': a['sev_true'], 'severity_pred': a['sev_pred'],
+                'uncertainty': a['uncertainty'] if self._has_uncertainty else None}
+
+
+def validate(model: torch.nn.Module, loader, loss_fn, n_bins: int = 10) -> Dict[str, float]:
+    """The reference's ``Trainer.val_epoch`` (training/trainer.py:183-231) with one synchronisation: eval mode, no_grad,
+    ``loss_fn(outputs, class_labels, severity_labels, stage=4)`` per batch; returns loss, cls_loss, ord_loss, unc_loss, kan_loss as means
+    over batches and accuracy (percent) over samples."""
+    model.eval()
+    dev = next(model.parameters()).device
+    acc: Optional[EvalAccumulator] = None
+    with torch.no_grad():
+        for images, class_labels, severity_labels in loader:
+            images = images.to(dev, non_blocking=True)
+            class_labels = class_labels.to(dev, non_blocking=True)
+            severity_labels = severity_labels.to(dev, non_blocking=True)
+            outputs = model(images)
+            losses = loss_fn(outputs, class_labels, severity_labels, stage=4)
+            if acc is None:
+                acc = EvalAccumulator(int(outputs['cls_logits'].shape[1]), n_bins)
+            acc.update(outputs, class_labels, severity_labels, losses=losses)
+    if acc is None:
+        raise RovitHipError('validate: the loader yielded no batch')
+    m = acc.compute()
+    out = {k: m[k] for k in ('loss', 'cls_loss', 'ord_loss', 'unc_loss', 'kan_loss')}
+    out['accuracy'] = 100. * m['correct'] / m['n']          # the trainer's own expression (trainer.py:228), to the last bit
+    return out
+
+
+def class_table(per_class: Sequence[Dict], class_names: Sequence[str]) -> Dict[str, Dict]:
+    """The per-class list of ``compute()`` keyed by class name, as evaluation/metrics.py's ``per_class_metrics`` returns it."""
+    return {name: dict(per_class[i]) for i, name in enumerate(class_names)}

@@ -110,6 +110,9 @@ SIGNATURES = {
     'rovit_adamw_flat': (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _f, _f, _f, _f, _f, _i, _vp]),
     'rovit_sq_norm_clip': (_i, [_vp, _vp, _i, _f, _vp, _vp, _vp, _sz, _vp]),
     'rovit_adamw_flat_multi': (_i, [_vp] * 7 + [_i, _vp, _f, _f, _f, _f, _vp]),
+    'rovit_eval_partials_doubles': (_sz, [_i]),
+    'rovit_eval_accumulate': (_i, [_vp, _vp]),
+    'rovit_eval_finalize': (_i, [_vp, _vp]),
 }
 
 
@@ -134,6 +137,27 @@ class HeadMC(C.Structure):
                 ('ord_probs', _vp), ('ord_severity', _vp), ('ord_severity_std', _vp),
                 ('unc_mu', _vp), ('epistemic_var', _vp), ('aleatoric_var', _vp), ('unc_std', _vp),
                 ('s_cls', _vp), ('s_ord', _vp), ('s_mu', _vp), ('s_lv', _vp)]
+
+
+class EvalBatch(C.Structure):
+    """``rovit_eval_batch`` of include/rovit_hip.h, field for field."""
+    _fields_ = [('batch', _i), ('num_classes', _i), ('offset', _i), ('capacity', _i), ('severity_is_int64', _i), ('loss_row', _i),
+                ('loss_capacity', _i), ('cls_logits', _vp), ('kan_severity', _vp), ('log_var', _vp), ('class_labels', _vp),
+                ('severity_labels', _vp), ('losses', _vp), ('probs', _vp), ('pred', _vp), ('label', _vp), ('sev_pred', _vp),
+                ('sev_true', _vp), ('uncertainty', _vp), ('loss_table', _vp)]
+
+
+class EvalFinal(C.Structure):
+    """``rovit_eval_final`` of include/rovit_hip.h, field for field."""
+    _fields_ = [('n', _i), ('num_classes', _i), ('n_bins', _i), ('n_loss_rows', _i), ('probs', _vp), ('pred', _vp), ('label', _vp),
+                ('sev_pred', _vp), ('sev_true', _vp), ('loss_table', _vp), ('bin_edges', _vp), ('rank_counts', _vp), ('partials', _vp),
+                ('result', _vp)]
+
+
+# word offsets inside rovit_eval_finalize's result block (the ROVIT_EVAL_* enum of include/rovit_hip.h)
+EVAL_CONFUSION, EVAL_BIN_COUNT, EVAL_BIN_CORRECT, EVAL_RANK, EVAL_NONFINITE, EVAL_BAD_LABELS, EVAL_N = 0, 64, 128, 192, 195, 197, 198
+EVAL_BIN_CONF, EVAL_BRIER, EVAL_ABS_ERR, EVAL_LOSS, EVAL_RESULT_WORDS = 200, 264, 265, 266, 272
+EVAL_MAX_CLASSES, EVAL_MAX_BINS, EVAL_MAX_ROWS = 8, 64, 1 << 20
 
 
 # entry points only the developer library exports (round-2 / round-3 experiments that lost; tools/ A/B them)
