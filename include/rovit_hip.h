@@ -579,6 +579,44 @@ size_t rovit_eval_partials_doubles(int n);
 int rovit_eval_accumulate(const rovit_eval_batch* p, rovit_stream_t stream);
 int rovit_eval_finalize(const rovit_eval_final* p, rovit_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Per-edge activation statistics of one KAN layer over a data set (kan_stats.hip): what the edge functions of models/kan.py:70-95 do
+ * ON DATA, where KANLayer.plot_activation (:97-114) and explainability/kan_viz.py only draw a few of them over [-1, 1].
+ * For the layer's n input rows x (n, in_f), with s_ij(v) = sum_k spline_w[i,j,k] B_k(tanh v), phi_ij(v) = lin_w[j,i] v + s_ij(v) and
+ * z_nj = lin_b[j] + sum_i phi_ij(x_ni), rovit_kan_edge_stats writes this layer's section of the caller's result buffer,
+ * rovit_kan_stats_words(in_f, out_f, n_knots) 8-byte words with E = in_f * out_f:
+ *   double [q E + i out_f + j], q = ROVIT_KAN_STATS_SUM / _SQ / _ABS / _SPLINE_ABS / _LINEAR_ABS: sum phi, sum phi^2, sum |phi|, sum |s|
+ *          and |lin_w[j,i]| sum |x_i| (the linear term's L1 share) of edge (i, j)
+ *   double [5E + j], [5E + out_f + j]: sum z_j, sum z_j^2         double [5E + 2 out_f + i]: sum |x_i|
+ *   int64  [5E + 2 out_f + in_f + i n_knots + t]: rows whose tanh(x_i) lies in knot interval t, the index the forward's basis search
+ *          finds after its clamp (t >= n_knots - 4: the truncated basis is zero there; t = n_knots - 1 only for tanh == knots[last])
+ *   int64  [.. + in_f n_knots]: non-finite inputs      int64 [.. + 1]: n
+ * The basis, the interval and the cutoff decisions are the forward kernels' own (kan_device.h).  No (n, in, out) intermediate exists: the
+ * sums are kept in registers as fp32 over at most 16 rows and folded into fp64, then added over a partition of the rows that depends on n
+ * and the layer shape only, in a fixed order: the section is bit-identical from run to run, and the error does not grow with n.
+ * Integers are added with integer atomics.  The section is zeroed first.  Shapes: in_f, out_f >= 1, 5 <= n_knots <= 64.
+ * partials: device workspace of rovit_kan_stats_partials_doubles(n, in_f, out_f, n_knots) doubles.
+ * rovit_kan_curves: ys (in_f, out_f, num_points) = s_ij(xs[p]) (+ lin_w[j,i] xs[p] when lin_w is not NULL) with xs the NORMALISED
+ * coordinate (no tanh), plot_activation's convention, for every edge in one launch.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define ROVIT_KAN_STATS_MAX_ROWS (1 << 22)
+enum { ROVIT_KAN_STATS_SUM = 0, ROVIT_KAN_STATS_SQ = 1, ROVIT_KAN_STATS_ABS = 2, ROVIT_KAN_STATS_SPLINE_ABS = 3, ROVIT_KAN_STATS_LINEAR_ABS = 4 };
+typedef struct rovit_kan_stats {
+  int n, in_f, out_f, n_knots;
+  const float* x;                   /* (n, in_f) */
+  const float* spline_w;            /* (in_f, out_f, n_knots - 4) */
+  const float* knots;               /* (n_knots) */
+  const float* lin_w;               /* (out_f, in_f) */
+  const float* lin_b;               /* (out_f) */
+  double* partials;                 /* workspace */
+  void* result;                     /* this layer's section */
+} rovit_kan_stats;
+size_t rovit_kan_stats_words(int in_f, int out_f, int n_knots);
+size_t rovit_kan_stats_partials_doubles(int n, int in_f, int out_f, int n_knots);
+int rovit_kan_edge_stats(const rovit_kan_stats* p, rovit_stream_t stream);
+int rovit_kan_curves(const float* xs, const float* spline_w, const float* knots, const float* lin_w, float* ys, int in_f, int out_f,
+                     int n_knots, int num_points, rovit_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,16 @@ struct Basis4 {
   float v[4];   // value of basis j-m, m = 0..3
 };
 
+// Knot interval of an already clamped coordinate xc: a guess from the uniform spacing, then an exact search on the stored knots.
+// The one search of this file: kan_basis and kan_interval both call it.
+__device__ __forceinline__ int kan_search(float xc, const float* knots, int nk, float t0, float inv_h0) {
+  int j = (int)floorf((xc - t0) * inv_h0);
+  j = j < 0 ? 0 : (j > nk - 1 ? nk - 1 : j);
+  while (j > 0 && xc < knots[j]) --j;                          // exact search on the stored knots
+  while (j < nk - 1 && xc >= knots[j + 1]) ++j;
+  return j;
+}
+
 // knots: LDS or global pointer to nk fp32 knots (uniform by construction, but the STORED values are used
 // for the interval search and for h, as the reference does: kan.py:24,33-38).
 template <bool DERIV>
@@ -20,10 +30,7 @@ __device__ __forceinline__ Basis4 kan_basis(float xn, const float* knots, int nk
   const int nb = nk - 4;
   const float t0 = knots[0], tl = knots[nk - 1];
   float xc = fminf(fmaxf(xn, t0), tl);                         // kan.py:16
-  int j = (int)floorf((xc - t0) * inv_h0);
-  j = j < 0 ? 0 : (j > nk - 1 ? nk - 1 : j);
-  while (j > 0 && xc < knots[j]) --j;                          // exact search on the stored knots
-  while (j < nk - 1 && xc >= knots[j + 1]) ++j;
+  const int j = kan_search(xc, knots, nk, t0, inv_h0);
   if (j >= nb) {                                               // truncation: SURVEY.md 0.2
     r.j = -1; r.v[0] = r.v[1] = r.v[2] = r.v[3] = 0.f;
     if (DERIV) dv[0] = dv[1] = dv[2] = dv[3] = 0.f;
@@ -49,6 +56,13 @@ __device__ __forceinline__ Basis4 kan_basis(float xn, const float* knots, int nk
   for (int m = 0; m < 4; ++m)
     if (j - m < 0) { r.v[m] = 0.f; if (DERIV) dv[m] = 0.f; }   // left edge loses terms
   return r;
+}
+
+// kan_basis's clamp and search alone, for callers that need the index inside the truncated zone too (kan_basis reports -1 for all
+// of it): kan_stats.hip's occupancy counts.
+__device__ __forceinline__ int kan_interval(float xn, const float* knots, int nk, float inv_h0) {
+  const float t0 = knots[0], tl = knots[nk - 1];
+  return kan_search(fminf(fmaxf(xn, t0), tl), knots, nk, t0, inv_h0);
 }
 
 __device__ __forceinline__ float act_apply(float z, int act) {

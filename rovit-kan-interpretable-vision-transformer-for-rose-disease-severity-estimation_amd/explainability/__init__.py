@@ -1,3 +1,4 @@
-"""Drop-in for the reference's ``explainability`` package: attention rollout and Grad-CAM++ computed on the GPU."""
+"""Drop-in for the reference's ``explainability`` package: attention rollout, Grad-CAM++ and the KAN head's edge statistics computed on the GPU."""
 from .attention_maps import ViTAttentionRollout  # noqa: F401
 from .gradcam import GradCAMPlusPlus  # noqa: F401
+from .kan_viz import KANVisualizer  # noqa: F401

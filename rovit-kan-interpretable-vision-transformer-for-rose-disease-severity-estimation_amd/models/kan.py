@@ -56,6 +56,19 @@ class KANLayer(nn.Module):
         ys = (basis * self.spline_weights[input_idx, output_idx].detach()).sum(dim=1)
         return xs.cpu().numpy(), ys.cpu().numpy()
 
+    def activation_curves(self, num_points: int = 100, include_linear: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        """Extension (not in the reference): ``plot_activation`` of EVERY edge in one launch and one copy.  Returns ``(xs, ys)`` with
+        ``ys`` of shape (in, out, num_points); ``xs`` is the normalised coordinate (no tanh), as in ``plot_activation``;
+        ``include_linear`` adds the edge's linear term ``linear.weight[j, i] * xs``."""
+        xs = torch.linspace(-1, 1, num_points, device=self.knots.device)
+        w = self.spline_weights.detach().float().contiguous()
+        kn = self.knots.detach().float().contiguous()
+        lw = self.linear.weight.detach().float().contiguous() if include_linear else None
+        ys = torch.empty(self.in_features, self.out_features, num_points, device=xs.device, dtype=torch.float32)
+        native.call('rovit_kan_curves', native.ptr(xs), native.ptr(w), native.ptr(kn), native.ptr(lw), native.ptr(ys), self.in_features,
+                    self.out_features, kn.numel(), num_points, native.stream_ptr())
+        return xs.cpu().numpy(), ys.cpu().numpy()
+
 
 class KANSeverityModule(nn.Module):
     def __init__(self, layers: List[int] = [384, 64, 16, 1], num_knots: int = 5, degree: int = 3):

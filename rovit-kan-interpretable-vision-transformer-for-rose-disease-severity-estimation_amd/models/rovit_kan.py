@@ -242,6 +242,20 @@ class RoViTKAN(nn.Module):
         from rovit_hip import perturbation as pert
         return pert.perturbation_curves(self, x, saliency, target, class_idx, modes, steps, perturbation, baseline, chunk)
 
+    def kan_edge_stats(self, x_or_loader, chunk: int = 256):
+        """Extension (not in the reference): per-edge activation statistics of the KAN head over images (a (B,3,224,224) tensor, or an
+        iterable of batches whose first element is the images): magnitude, spline share, knot-span occupancy and dead-zone share
+        of every edge on the GPU (rovit_hip.kan_stats)."""
+        from rovit_hip import kan_stats
+        return kan_stats.model_edge_stats(self, x_or_loader, chunk)
+
+    def kan_attribution(self, x_or_loader, chunk: int = 256):
+        """Extension (not in the reference): ``kan_edge_stats`` plus pykan's attribution scores of every edge, node and backbone
+        feature for the severity output: ``{'stats', 'edge_scores', 'node_scores', 'feature_scores'}``."""
+        from rovit_hip import kan_stats
+        stats = kan_stats.model_edge_stats(self, x_or_loader, chunk)
+        return {'stats': stats, **kan_stats.kan_attribution(stats)}
+
     def count_parameters(self) -> Dict[str, int]:
         def n(m):
             return sum(p.numel() for p in m.parameters() if p.requires_grad)

@@ -113,6 +113,10 @@ SIGNATURES = {
     'rovit_eval_partials_doubles': (_sz, [_i]),
     'rovit_eval_accumulate': (_i, [_vp, _vp]),
     'rovit_eval_finalize': (_i, [_vp, _vp]),
+    'rovit_kan_stats_words': (_sz, [_i, _i, _i]),
+    'rovit_kan_stats_partials_doubles': (_sz, [_i, _i, _i, _i]),
+    'rovit_kan_edge_stats': (_i, [_vp, _vp]),
+    'rovit_kan_curves': (_i, [_vp] * 5 + [_i] * 4 + [_vp]),
 }
 
 
@@ -158,6 +162,27 @@ class EvalFinal(C.Structure):
 EVAL_CONFUSION, EVAL_BIN_COUNT, EVAL_BIN_CORRECT, EVAL_RANK, EVAL_NONFINITE, EVAL_BAD_LABELS, EVAL_N = 0, 64, 128, 192, 195, 197, 198
 EVAL_BIN_CONF, EVAL_BRIER, EVAL_ABS_ERR, EVAL_LOSS, EVAL_RESULT_WORDS = 200, 264, 265, 266, 272
 EVAL_MAX_CLASSES, EVAL_MAX_BINS, EVAL_MAX_ROWS = 8, 64, 1 << 20
+
+
+class KANStats(C.Structure):
+    """``rovit_kan_stats`` of include/rovit_hip.h, field for field."""
+    _fields_ = [('n', _i), ('in_f', _i), ('out_f', _i), ('n_knots', _i), ('x', _vp), ('spline_w', _vp), ('knots', _vp), ('lin_w', _vp),
+                ('lin_b', _vp), ('partials', _vp), ('result', _vp)]
+
+
+# rovit_kan_edge_stats' section of one layer (the ROVIT_KAN_STATS_* enum and the layout comment of include/rovit_hip.h)
+KAN_STATS_SUM, KAN_STATS_SQ, KAN_STATS_ABS, KAN_STATS_SPLINE_ABS, KAN_STATS_LINEAR_ABS = 0, 1, 2, 3, 4
+KAN_STATS_MAX_ROWS, KAN_MAX_KNOTS = 1 << 22, 64
+
+
+def kan_stats_offsets(in_f: int, out_f: int, n_knots: int) -> dict:
+    """Word offsets inside one layer's section; ``words`` equals rovit_kan_stats_words(in_f, out_f, n_knots)."""
+    e = in_f * out_f
+    pre = 5 * e
+    abs_in = pre + 2 * out_f
+    occ = abs_in + in_f
+    bad = occ + in_f * n_knots
+    return {'edge': 0, 'pre': pre, 'abs_in': abs_in, 'occupancy': occ, 'nonfinite': bad, 'n': bad + 1, 'words': bad + 2}
 
 
 # entry points only the developer library exports (round-2 / round-3 experiments that lost; tools/ A/B them)
