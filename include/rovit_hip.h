@@ -617,6 +617,43 @@ int rovit_kan_edge_stats(const rovit_kan_stats* p, rovit_stream_t stream);
 int rovit_kan_curves(const float* xs, const float* spline_w, const float* knots, const float* lin_w, float* ys, int in_f, int out_f,
                      int n_knots, int num_points, rovit_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Per-sample augmentation of a device-resident uint8 image store (augment_batch.hip).  Serves the batches of
+ * training/trainer.py:79-82 (`images, class_labels, severity_labels`, moved with .to(device)) and the loaders scripts/train.py:73-84
+ * builds with create_dataloaders(..., augmented_transform=, original_transform=): the data set is decoded ONCE and kept on the device
+ * as uint8, and ONE launch per batch gathers by index, draws each sample's augmentation, resamples, colour-transforms, normalises and
+ * writes the fp32 NCHW batch the backbone reads.  The reference's data/transforms.py is not in its checkout: the transform is this
+ * repository's definition ("parity unpinned"), stated in full in rovit_hip/augment.py.
+ *   src (n_images, 3, src_h, src_w) uint8   indices (batch) int64 into the store   out (batch, 3, out_h, out_w) fp32
+ *   row of sample n, 12 floats: [flip_h, flip_v, area, log_ratio, ux, uy, theta, brightness, contrast, saturation, hue, 0]
+ * Geometry: r = exp(log_ratio), w = min(Ws, Ws sqrt(area r)), h = min(Hs, Hs sqrt(area / r)), cx = ux (Ws - w) + w/2, cy likewise;
+ *   dx = ((j + .5)/Wo - .5) w (1 - 2 flip_h), dy = ((i + .5)/Ho - .5) h (1 - 2 flip_v), sx = cx + cos dx - sin dy - .5,
+ *   sy = cy + sin dx + cos dy - .5, clamped to the image; bilinear on u8/255 with the upper taps clamped to the last row / column
+ *   (= grid_sample(mode='bilinear', padding_mode='border', align_corners=False)); no antialiasing.
+ * Colour: A = T^-1 diag(1, saturation Rot(2 pi hue)) T with T the NTSC RGB->YIQ matrix; z = clamp(brightness (.5 + contrast (A v - .5)),
+ *   0, 1); out = (z - mean_c) / std_c with the ImageNet constants.
+ * params != NULL: the rows are read from it.  params == NULL: each row is drawn from Philox4x32-10, key = seed, counter =
+ *   (index in the STORE, r, epoch lo, epoch hi), r = 0, 1, 2, u = (word >> 8) 2^-24:  r = 0: flip_h = u < p_hflip, flip_v = u < p_vflip,
+ *   area = scale_lo + u (scale_hi - scale_lo), log_ratio likewise;  r = 1: ux, uy, theta = (2u - 1) theta_max, brightness = 1 + (2u - 1)
+ *   jitter;  r = 2: contrast, saturation likewise, hue = (2u - 1) hue jitter.  An image's row depends on (index, seed, epoch) alone, and
+ *   a pixel's arithmetic on its row alone: out rows are bit-identical for every batch size, order and split.
+ * params_out != NULL: the rows used are written there (batch, 12).
+ * An index outside [0, n_images) is not dereferenced: that sample's output and params_out row are NaN.
+ * Refused before any launch: null pointers, out overlapping src, out_w % 4 != 0, out not 16-byte aligned, an empty store or batch,
+ * 0 < scale_lo <= scale_hi <= 1 violated, probabilities outside [0, 1], unordered or negative ranges (config is checked when given;
+ * it may be NULL only with params).
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct rovit_augment_config {
+  float p_hflip, p_vflip;              /* probabilities */
+  float scale_lo, scale_hi;            /* crop area as a fraction of the source */
+  float log_ratio_lo, log_ratio_hi;    /* log of the crop's aspect ratio */
+  float theta_max;                     /* radians */
+  float brightness, contrast, saturation, hue;   /* jitter half-widths */
+} rovit_augment_config;
+int rovit_augment_batch(const unsigned char* src, int n_images, int src_h, int src_w, const long long* indices, int batch,
+                        const float* params, float* params_out, const rovit_augment_config* config, unsigned long long seed,
+                        unsigned long long epoch, float* out, int out_h, int out_w, rovit_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

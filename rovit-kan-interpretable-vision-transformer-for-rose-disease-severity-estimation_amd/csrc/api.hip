@@ -28,6 +28,9 @@ void rovit_set_error(const char* fmt, ...) {
 // (rovit_vit_f32_workspace_field was added at 440 the same way: a host-only view of the fp32 forward's workspace, vit_f32.hip.)
 // (rovit_eval_accumulate, rovit_eval_finalize and rovit_eval_partials_doubles were added at 440 the same way: test-set evaluation and
 // validation with one synchronisation per epoch, evaluate.hip.)
+// (rovit_kan_stats_words, rovit_kan_stats_partials_doubles, rovit_kan_edge_stats and rovit_kan_curves were added at 440 the same way:
+// per-edge KAN activation statistics, kan_stats.hip.)
+// (rovit_augment_batch was added at 440 the same way: per-sample augmentation of a device-resident uint8 image store, augment_batch.hip.)
 extern "C" int rovit_version(void) { return 440; }
 extern "C" const char* rovit_last_error_string(void) { return g_err; }
 

@@ -37,11 +37,12 @@ class RoseLeafDataset(Dataset):
 
     ``synthetic=N`` skips the file system: N seeded ``randn`` images with labels drawn uniformly over the classes
     (severity = ``severity_map[class]``, the identity on the reference's class order, configs/config.py:19-24),
-    optionally resident on ``device``."""
+    optionally resident on ``device``.  ``materialize=False`` draws the same labels but no fp32 images (the images then live in a
+    ``DeviceImageStore`` as uint8, ``create_dataloaders(device_cache=True)``); indexing such a dataset raises."""
 
     def __init__(self, root_dir=None, class_names: Sequence[str] = (), severity_map: Optional[Dict[str, int]] = None,
                  transform: Optional[Callable] = None, mode: str = 'augmented', synthetic: Optional[int] = None,
-                 seed: int = 0, device: Optional[torch.device] = None, image_size: int = IMAGE_SIZE):
+                 seed: int = 0, device: Optional[torch.device] = None, image_size: int = IMAGE_SIZE, materialize: bool = True):
         self.root_dir = Path(root_dir) if root_dir is not None else None
         self.class_names = list(class_names)
         self.severity_map = dict(severity_map) if severity_map is not None else {c: i for i, c in enumerate(self.class_names)}
@@ -62,7 +63,9 @@ class RoseLeafDataset(Dataset):
             g = torch.Generator().manual_seed(seed)
             self.labels = torch.randint(0, len(self.class_names), (synthetic,), generator=g)
             dev = device if device is not None else torch.device('cpu')
-            if dev.type == 'cuda':
+            if not materialize:
+                pass
+            elif dev.type == 'cuda':
                 gd = torch.Generator(device=dev).manual_seed(seed)
                 self.images = torch.randn(synthetic, 3, image_size, image_size, device=dev, generator=gd)
             else:
@@ -95,6 +98,8 @@ class RoseLeafDataset(Dataset):
             return torch.from_numpy(np.asarray(im).copy()).permute(2, 0, 1).float().div_(255.0)
 
     def __getitem__(self, idx: int):
+        if self.images is None and not self.samples:
+            raise RuntimeError('this synthetic RoseLeafDataset holds labels only (materialize=False): its images are in a DeviceImageStore')
         img = self.images[idx] if self.images is not None else self._load(self.samples[idx][0])
         if self.transform is not None:
             img = self.transform(img)
@@ -146,6 +151,59 @@ class DeviceBatchLoader:
                 yield imgs, self._labels_host.index_select(0, order[lo:hi]), self._sev_host.index_select(0, order[lo:hi])
 
 
+class DeviceAugmentLoader:
+    """``DeviceBatchLoader``'s contract over a ``rovit_hip.augment.DeviceImageStore``: ``.dataset`` is a ``Subset`` of the store's
+    ``RoseLeafDataset``, ``len()`` = batches, iteration yields ``(images, class_labels, severity_labels)`` with the images an fp32
+    (B, 3, H, W) device batch made by ONE launch (gather by index + per-sample augmentation + normalisation, rovit_augment_batch) and the
+    labels on the host (``labels_on_device=True``: on the device).  Every ``__iter__`` is a new epoch: the epoch counter, which with
+    ``seed`` and the image's index in the store decides the image's augmentation and with ``seed`` the shuffled order, advances by one;
+    ``set_epoch(e)`` sets the epoch the NEXT iteration uses.  The order is uploaded once per epoch; ``indices`` are checked against the
+    store here, on the host."""
+
+    def __init__(self, store, indices: Sequence[int], batch_size: int, shuffle: bool, config=None, seed: int = 0,
+                 drop_last: bool = False, labels_on_device: bool = False, out_size: Tuple[int, int] = (IMAGE_SIZE, IMAGE_SIZE)):
+        from rovit_hip.augment import AugmentConfig
+        self.store, self.batch_size, self.shuffle, self.drop_last = store, int(batch_size), shuffle, drop_last
+        self.config = config if config is not None else AugmentConfig()
+        self.config.validate()
+        self.seed, self.labels_on_device, self.out_size = int(seed), labels_on_device, tuple(out_size)
+        self._idx = torch.as_tensor(list(indices), dtype=torch.long)
+        if self.batch_size <= 0 or self._idx.numel() == 0:
+            raise ValueError('DeviceAugmentLoader needs a positive batch size and at least one index')
+        if int(self._idx.min()) < 0 or int(self._idx.max()) >= len(store):
+            raise IndexError(f'store index outside [0, {len(store)})')
+        self.dataset = Subset(store.dataset, self._idx.tolist())
+        self._labels_host, self._sev_host = store.labels.cpu(), store.severities.cpu()
+        self.epoch = 0
+
+    def set_epoch(self, epoch: int) -> None:
+        self.epoch = int(epoch)
+
+    def __len__(self) -> int:
+        n = self._idx.numel()
+        return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
+
+    def epoch_order(self, epoch: int) -> torch.Tensor:
+        """Store indices in the order epoch ``epoch`` visits them (host tensor): a function of (seed, epoch) alone."""
+        if not self.shuffle:
+            return self._idx
+        g = torch.Generator().manual_seed((self.seed * 1000003 + epoch) & 0x7FFFFFFFFFFFFFFF)
+        return self._idx[torch.randperm(self._idx.numel(), generator=g)]
+
+    def __iter__(self):
+        epoch, self.epoch = self.epoch, self.epoch + 1
+        order = self.epoch_order(epoch)
+        order_dev = order.to(self.store.device, non_blocking=True)
+        for b in range(len(self)):
+            lo, hi = b * self.batch_size, (b + 1) * self.batch_size
+            sel = order_dev[lo:hi]
+            imgs = self.store.batch(sel, self.config, self.seed, epoch, out_size=self.out_size)
+            if self.labels_on_device:
+                yield imgs, self.store.labels.index_select(0, sel), self.store.severities.index_select(0, sel)
+            else:
+                yield imgs, self._labels_host.index_select(0, order[lo:hi]), self._sev_host.index_select(0, order[lo:hi])
+
+
 def _split(n: int, frac: float, seed: int) -> Tuple[List[int], List[int]]:
     perm = torch.randperm(n, generator=torch.Generator().manual_seed(seed)).tolist()
     k = int(round(n * frac))
@@ -156,13 +214,38 @@ def create_dataloaders(augmented_root=None, original_root=None, class_names: Seq
                        severity_map: Optional[Dict[str, int]] = None, augmented_transform: Optional[Callable] = None,
                        original_transform: Optional[Callable] = None, batch_size: int = 32, train_val_split: float = 0.8,
                        num_workers: int = 0, seed: int = 42, synthetic: Optional[int] = None,
-                       device: Optional[torch.device] = None):
+                       device: Optional[torch.device] = None, device_cache: bool = False, device_augment=None,
+                       store_size: Optional[Tuple[int, int]] = None):
     """-> (train_loader, val_loader, test_loader); call as scripts/train.py:73-84 does.  ``synthetic=N`` (or
     ``$ROVIT_SYNTHETIC_DATA``) replaces both folders by N (train+val) and N//4 (test) seeded random images resident on
-    ``device`` (default: the current CUDA/HIP device when there is one)."""
+    ``device`` (default: the current CUDA/HIP device when there is one).
+
+    ``device_cache=True``: both sets (folders decoded once with PIL, or synthetic uniform-noise images) are kept on ``device`` as uint8
+    stores of ``store_size`` = (Hs, Ws) (default 224 x 224) and all three loaders are ``DeviceAugmentLoader``s; the train loader
+    augments with ``device_augment`` (a ``rovit_hip.augment.AugmentConfig``, default flip + normalise = ``augmented_transforms()``), the
+    other two normalise only.  ``augmented_transform`` / ``original_transform`` are not applied on this path (the kernel does both jobs)."""
     if synthetic is None and not (augmented_root is not None and Path(augmented_root).exists()):
         env = os.environ.get('ROVIT_SYNTHETIC_DATA')
         synthetic = int(env) if env else None
+    if device_cache:
+        from rovit_hip.augment import AugmentConfig, DeviceImageStore
+        if device is None:
+            device = torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else torch.device('cpu')
+        size = tuple(store_size) if store_size is not None else (IMAGE_SIZE, IMAGE_SIZE)
+        if synthetic is not None:
+            full = RoseLeafDataset(None, class_names, severity_map, None, 'augmented', synthetic, seed, device, materialize=False)
+            test = RoseLeafDataset(None, class_names, severity_map, None, 'original', max(1, synthetic // 4), seed + 1, device,
+                                   materialize=False)
+        else:
+            full = RoseLeafDataset(augmented_root, class_names, severity_map, None, 'augmented')
+            test = RoseLeafDataset(original_root, class_names, severity_map, None, 'original')
+        full_store = DeviceImageStore.from_dataset(full, device, size, seed=seed)
+        test_store = DeviceImageStore.from_dataset(test, device, size, seed=seed + 1)
+        tr, va = _split(len(full), train_val_split, seed)
+        ident = AugmentConfig.identity()
+        return (DeviceAugmentLoader(full_store, tr, batch_size, True, device_augment, seed),
+                DeviceAugmentLoader(full_store, va, batch_size, False, ident, seed),
+                DeviceAugmentLoader(test_store, list(range(len(test))), batch_size, False, ident, seed))
     if synthetic is not None:
         if device is None:
             device = torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else torch.device('cpu')

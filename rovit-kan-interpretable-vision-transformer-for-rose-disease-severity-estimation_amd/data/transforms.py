@@ -125,3 +125,12 @@ def original_transforms():
 
 def inference_transforms():
     return Compose([Normalize()])
+
+
+def device_augmentation(**kw):
+    """-> ``rovit_hip.augment.AugmentConfig(**kw)`` for ``create_dataloaders(device_cache=True, device_augment=...)``: the ranges of the
+    fused on-device augmentation (hflip, vflip, scale, ratio, rotate_deg, brightness, contrast, saturation, hue).  Its colour part is the
+    DALI "ColorTwist" form (fixed order, contrast pivot 0.5), not torchvision's ColorJitter; see rovit_hip/augment.py -- like the rest of
+    this module "parity unpinned" against the reference, whose data/transforms.py is not in its checkout."""
+    from rovit_hip.augment import AugmentConfig
+    return AugmentConfig(**kw)

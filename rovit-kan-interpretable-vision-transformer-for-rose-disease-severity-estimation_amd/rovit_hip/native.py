@@ -117,6 +117,7 @@ SIGNATURES = {
     'rovit_kan_stats_partials_doubles': (_sz, [_i, _i, _i, _i]),
     'rovit_kan_edge_stats': (_i, [_vp, _vp]),
     'rovit_kan_curves': (_i, [_vp] * 5 + [_i] * 4 + [_vp]),
+    'rovit_augment_batch': (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, C.c_ulonglong, C.c_ulonglong, _vp, _i, _i, _vp]),
 }
 
 
@@ -183,6 +184,12 @@ def kan_stats_offsets(in_f: int, out_f: int, n_knots: int) -> dict:
     occ = abs_in + in_f
     bad = occ + in_f * n_knots
     return {'edge': 0, 'pre': pre, 'abs_in': abs_in, 'occupancy': occ, 'nonfinite': bad, 'n': bad + 1, 'words': bad + 2}
+
+
+class AugmentConfigC(C.Structure):
+    """``rovit_augment_config`` of include/rovit_hip.h, field for field."""
+    _fields_ = [(k, _f) for k in ('p_hflip', 'p_vflip', 'scale_lo', 'scale_hi', 'log_ratio_lo', 'log_ratio_hi', 'theta_max',
+                                  'brightness', 'contrast', 'saturation', 'hue')]
 
 
 # entry points only the developer library exports (round-2 / round-3 experiments that lost; tools/ A/B them)
