@@ -522,6 +522,56 @@ int rovit_joint_loss(const float* cls_logits, const float* ordinal_logits, const
 int rovit_scale_buffers(float* const* bufs, const int* counts, int n, const float* scale, rovit_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * A training epoch with one synchronisation (train_epoch.hip).
+ * rovit_joint_loss_mixed replaces the CutMix / MixUp branch of Trainer.train_epoch (training/trainer.py:104-111: the loss twice on the
+ * same head outputs, then lam * a[k] + (1 - lam) * b[k] on the five dict entries) and the bookkeeping of :144-153 (five loss .item(),
+ * max / eq / sum and a sixth .item() per step) with ONE launch of rovit_joint_loss's shape and arithmetic (one shared statement of the
+ * per-row formulas, csrc/joint_loss_row.h).
+ *   class_targets_b == NULL: every loss and every gradient is bit-identical to rovit_joint_loss on the same inputs; lam is not read.
+ *   class_targets_b != NULL: the focal term of a row is lam f(t_a) + (1 - lam) f(t_b) and its gradient is mixed the same way; softmax
+ *     and lse are computed once per row; the ordinal, heteroscedastic and KAN terms do not depend on the class label and are computed
+ *     once (the reference's lam x + (1 - lam) x equals x to rounding).  0 <= lam <= 1, passed by value: the host drew it.
+ *   A class label outside [0, num_classes) in either column makes the class loss and the total NaN instead of reading out of bounds.
+ * table != NULL: the launch also writes row `row` (< capacity) of the caller's epoch table, ROVIT_TRAIN_ROW_WORDS 4-byte words per row:
+ *   float [ROVIT_TRAIN_ROW_LOSS + 0..4] = losses_out;  int [ROVIT_TRAIN_ROW_CORRECT] rows whose FIRST-maximum argmax of cls_logits (a NaN
+ *   counts as the maximum, as in torch.max) equals class_targets_a (trainer.py:151-153);  int [ROVIT_TRAIN_ROW_BATCH] = batch;
+ *   int [ROVIT_TRAIN_ROW_NONFINITE] = 1 when the total is not finite.  The host hands out the row index, so a row has one writer: plain
+ *   stores, no atomics, no device counter, no synchronisation.
+ * rovit_train_finalize reduces rows [0, n_rows) to `result`, ROVIT_TRAIN_RESULT_WORDS 8-byte words:
+ *   int64  [ROVIT_TRAIN_N_ROWS], [ROVIT_TRAIN_SAMPLES], [ROVIT_TRAIN_CORRECT], [ROVIT_TRAIN_NONFINITE] (rows whose flag is set)
+ *   double [ROVIT_TRAIN_LOSS + 0..4] column sums of the five losses, each row widened to fp64, added in a fixed order (strided over 256
+ *          threads, then a fixed tree): bit-identical from run to run.  It is the epoch's one device-to-host copy.
+ * Both refuse a bad descriptor before any launch.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define ROVIT_TRAIN_MAX_ROWS (1 << 20)
+enum {
+  ROVIT_TRAIN_ROW_LOSS = 0, ROVIT_TRAIN_ROW_CORRECT = 5, ROVIT_TRAIN_ROW_BATCH = 6, ROVIT_TRAIN_ROW_NONFINITE = 7, ROVIT_TRAIN_ROW_WORDS = 8,
+  ROVIT_TRAIN_N_ROWS = 0, ROVIT_TRAIN_SAMPLES = 1, ROVIT_TRAIN_CORRECT = 2, ROVIT_TRAIN_NONFINITE = 3, ROVIT_TRAIN_LOSS = 4,
+  ROVIT_TRAIN_RESULT_WORDS = 9
+};
+typedef struct rovit_train_loss {
+  int batch, num_classes, severity_is_int64, row, capacity;
+  float lam, lambda_ord, mu_unc, nu_kan, focal_gamma;
+  const float* cls_logits;            /* (batch, C) */
+  const float* ordinal_logits;        /* (batch, C - 1) or NULL: head gated, as in rovit_joint_loss */
+  const float* mu; const float* log_var; const float* kan_severity;      /* (batch) or NULL */
+  const long long* class_targets_a;   /* (batch) */
+  const long long* class_targets_b;   /* (batch) or NULL: not mixed */
+  const void* severity_targets;       /* (batch) fp32, or int64 with severity_is_int64 != 0 */
+  const float* focal_alpha;           /* (C) or NULL */
+  float* d_cls; float* d_ord; float* d_mu; float* d_lv; float* d_kan;    /* d(total)/d(head output) for an upstream gradient of 1 */
+  float* losses_out;                  /* [5]: cls, ord, unc, kan, total */
+  void* table;                        /* (capacity, ROVIT_TRAIN_ROW_WORDS) 4-byte words, or NULL: nothing recorded */
+} rovit_train_loss;
+typedef struct rovit_train_final {
+  int n_rows, capacity;
+  const void* table;
+  void* result;                       /* ROVIT_TRAIN_RESULT_WORDS 8-byte words */
+} rovit_train_final;
+int rovit_joint_loss_mixed(const rovit_train_loss* p, rovit_stream_t stream);
+int rovit_train_finalize(const rovit_train_final* p, rovit_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Test-set evaluation and validation without a per-batch host round trip (evaluate.hip).
  * rovit_eval_accumulate replaces the collection part of Evaluator.evaluate (evaluation/evaluator.py:37-67: softmax, argmax,
  * squeeze, exp(0.5 log_var) and five device-to-host copies per batch) and of Trainer.val_epoch (training/trainer.py:183-231: six

@@ -31,6 +31,8 @@ void rovit_set_error(const char* fmt, ...) {
 // (rovit_kan_stats_words, rovit_kan_stats_partials_doubles, rovit_kan_edge_stats and rovit_kan_curves were added at 440 the same way:
 // per-edge KAN activation statistics, kan_stats.hip.)
 // (rovit_augment_batch was added at 440 the same way: per-sample augmentation of a device-resident uint8 image store, augment_batch.hip.)
+// (rovit_joint_loss_mixed and rovit_train_finalize were added at 440 the same way: the CutMix / MixUp loss with a per-batch record and the
+// per-epoch reduction, train_epoch.hip.)
 extern "C" int rovit_version(void) { return 440; }
 extern "C" const char* rovit_last_error_string(void) { return g_err; }
 

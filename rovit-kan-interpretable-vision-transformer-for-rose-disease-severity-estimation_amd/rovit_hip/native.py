@@ -110,6 +110,8 @@ SIGNATURES = {
     'rovit_adamw_flat': (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _f, _f, _f, _f, _f, _i, _vp]),
     'rovit_sq_norm_clip': (_i, [_vp, _vp, _i, _f, _vp, _vp, _vp, _sz, _vp]),
     'rovit_adamw_flat_multi': (_i, [_vp] * 7 + [_i, _vp, _f, _f, _f, _f, _vp]),
+    'rovit_joint_loss_mixed': (_i, [_vp, _vp]),
+    'rovit_train_finalize': (_i, [_vp, _vp]),
     'rovit_eval_partials_doubles': (_sz, [_i]),
     'rovit_eval_accumulate': (_i, [_vp, _vp]),
     'rovit_eval_finalize': (_i, [_vp, _vp]),
@@ -163,6 +165,26 @@ class EvalFinal(C.Structure):
 EVAL_CONFUSION, EVAL_BIN_COUNT, EVAL_BIN_CORRECT, EVAL_RANK, EVAL_NONFINITE, EVAL_BAD_LABELS, EVAL_N = 0, 64, 128, 192, 195, 197, 198
 EVAL_BIN_CONF, EVAL_BRIER, EVAL_ABS_ERR, EVAL_LOSS, EVAL_RESULT_WORDS = 200, 264, 265, 266, 272
 EVAL_MAX_CLASSES, EVAL_MAX_BINS, EVAL_MAX_ROWS = 8, 64, 1 << 20
+
+
+class TrainLoss(C.Structure):
+    """``rovit_train_loss`` of include/rovit_hip.h, field for field."""
+    _fields_ = [('batch', _i), ('num_classes', _i), ('severity_is_int64', _i), ('row', _i), ('capacity', _i),
+                ('lam', _f), ('lambda_ord', _f), ('mu_unc', _f), ('nu_kan', _f), ('focal_gamma', _f),
+                ('cls_logits', _vp), ('ordinal_logits', _vp), ('mu', _vp), ('log_var', _vp), ('kan_severity', _vp),
+                ('class_targets_a', _vp), ('class_targets_b', _vp), ('severity_targets', _vp), ('focal_alpha', _vp),
+                ('d_cls', _vp), ('d_ord', _vp), ('d_mu', _vp), ('d_lv', _vp), ('d_kan', _vp), ('losses_out', _vp), ('table', _vp)]
+
+
+class TrainFinal(C.Structure):
+    """``rovit_train_final`` of include/rovit_hip.h, field for field."""
+    _fields_ = [('n_rows', _i), ('capacity', _i), ('table', _vp), ('result', _vp)]
+
+
+# rovit_joint_loss_mixed's epoch-table row (4-byte words) and rovit_train_finalize's result block (8-byte words): the ROVIT_TRAIN_* enum
+TRAIN_ROW_LOSS, TRAIN_ROW_CORRECT, TRAIN_ROW_BATCH, TRAIN_ROW_NONFINITE, TRAIN_ROW_WORDS = 0, 5, 6, 7, 8
+TRAIN_N_ROWS, TRAIN_SAMPLES, TRAIN_CORRECT, TRAIN_NONFINITE, TRAIN_LOSS, TRAIN_RESULT_WORDS = 0, 1, 2, 3, 4, 9
+TRAIN_MAX_ROWS = 1 << 20
 
 
 class KANStats(C.Structure):
