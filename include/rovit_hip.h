@@ -504,6 +504,17 @@ int rovit_sq_norm_clip(const float* const* bufs, const size_t* counts, int n_buf
 int rovit_adamw_flat_multi(float* const* p, const float* const* g, float* const* m, float* const* v, const size_t* n, const float* lr,
                            const int* t, int n_segs, const float* grad_scale, float beta1, float beta2, float eps, float weight_decay,
                            rovit_stream_t stream);
+/* rovit_adamw_flat_multi with an exponential moving average of the parameters updated in the same launch (the reference has none:
+ * parity unpinned).  Same segments, pieces and AdamW arithmetic (p, m, v come out bit-identical); after an element's new p,
+ * ema += omd * (p - ema) with omd = (float)(1 - (double)ema_decay[i]) -- the lerp form, which leaves ema == p exactly as it is.
+ * Per segment: g[i] == NULL = EMA only (p is read; p, m, v are not written; m[i], v[i] may be NULL, t[i] is ignored); ema[i] == NULL =
+ * plain AdamW; both NULL is ROVIT_ERR_NULL.  ema_decay[i] outside [0, 1) is ROVIT_ERR_SHAPE.  ema 16-byte aligned like the others.
+ * rovit_swap_flat_multi exchanges the contents of up to four buffer pairs a[i] <-> b[i] (n[i] floats each, 16-byte aligned, a pair
+ * does not overlap) in one launch: the parameters and their average change places for validation. */
+int rovit_adamw_ema_flat_multi(float* const* p, const float* const* g, float* const* m, float* const* v, float* const* ema,
+                               const size_t* n, const float* lr, const int* t, const float* ema_decay, int n_segs,
+                               const float* grad_scale, float beta1, float beta2, float eps, float weight_decay, rovit_stream_t stream);
+int rovit_swap_flat_multi(float* const* a, float* const* b, const size_t* n, int n_segs, rovit_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Joint multi-task loss, forward + gradient in one launch: JointLoss.forward (training/losses.py:139-181) with

@@ -208,6 +208,114 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const AdamSegs sg, con
   }
 }
 
+// ---- the same pass with an exponential moving average of the parameters as one more stream (read ema, write ema) ----
+// Per segment (block-uniform): g == NULL -> EMA only (p is read; p, m, v are not written); ema == NULL -> plain AdamW.  p, m, v must come
+// out bit-identical to adamw_multi_kernel's (tests/test_gpu_ema.py).  That kernel leaves the choice of which product of a sum is fused
+// to the compiler (-ffp-contract=fast), and the same expressions inlined here were contracted differently (m = fma(1 - beta1, gr, beta1 m)
+// against fma(beta1, m, (1 - beta1) gr) there), so adamw_element states every fused multiply-add adamw_multi_kernel's gfx950 code
+// makes, body and tail alike, and leaves nothing to contract.  The average is updated in the lerp form e += omd * (p_new - e),
+// omd = 1 - decay: e == p stays e exactly, so a segment that was never stepped needs no launch.
+struct AdamEmaSegs { float* p[4]; const float* g[4]; float* m[4]; float* v[4]; float* e[4]; unsigned long long n[4];
+                     float lr[4], inv_bc1[4], inv_sqrt_bc2[4], omd[4]; unsigned first[5]; int nseg; };
+__device__ __forceinline__ void adamw_element(float& P, float& M, float& V, float G, float gs, float beta1, float beta2, float eps,
+                                              float decay, float step, float inv_sqrt_bc2) {
+#pragma clang fp contract(off)
+  const float gr = G * gs;
+  M = __builtin_fmaf(beta1, M, (1.f - beta1) * gr);
+  V = __builtin_fmaf(gr, (1.f - beta2) * gr, beta2 * V);
+  const float denom = __builtin_fmaf(sqrtf(V), inv_sqrt_bc2, eps);
+  P = __builtin_fmaf(decay, P, -(step * (M / denom)));
+}
+__device__ __forceinline__ float ema_element(float e, float p, float omd) { return __builtin_fmaf(omd, p - e, e); }
+__global__ __launch_bounds__(256) void adamw_ema_multi_kernel(const AdamEmaSegs sg, const float* __restrict__ grad_scale, float beta1,
+                                                              float beta2, float eps, float wd) {
+  int k = 0;
+#pragma unroll
+  for (int q = 1; q < 4; ++q)
+    if (q < sg.nseg && blockIdx.x >= sg.first[q]) k = q;
+#define SEL(a) (k == 0 ? sg.a[0] : (k == 1 ? sg.a[1] : (k == 2 ? sg.a[2] : sg.a[3])))
+  float* p = SEL(p); const float* g = SEL(g); float* m = SEL(m); float* v = SEL(v); float* ema = SEL(e);
+  const unsigned long long n = SEL(n);
+  const float lr = SEL(lr), inv_bc1 = SEL(inv_bc1), inv_sqrt_bc2 = SEL(inv_sqrt_bc2), omd = SEL(omd);
+  const unsigned f0 = SEL(first);
+#undef SEL
+  const unsigned long long n4 = n / 4;
+  const unsigned long long base = (unsigned long long)(blockIdx.x - f0) * ADAM_PIECE4;
+  if (!g) {                                       // EMA only: a segment that has been stepped before and is frozen now
+#pragma unroll
+    for (int u = 0; u < ADAM_PIECE4 / 256; ++u) {
+      const unsigned long long i = base + u * 256 + threadIdx.x;
+      if (i < n4) {
+        const float4 pp = ((const float4*)p)[i];
+        float4 ee = ((float4*)ema)[i];
+        ee.x = ema_element(ee.x, pp.x, omd); ee.y = ema_element(ee.y, pp.y, omd);
+        ee.z = ema_element(ee.z, pp.z, omd); ee.w = ema_element(ee.w, pp.w, omd);
+        ((float4*)ema)[i] = ee;
+      }
+    }
+    if (blockIdx.x == f0)
+      for (unsigned long long i = n4 * 4 + threadIdx.x; i < n; i += 256) ema[i] = ema_element(ema[i], p[i], omd);
+    return;
+  }
+  const float gs = grad_scale ? *grad_scale : 1.f;
+  const float decay = __builtin_fmaf(-lr, wd, 1.f);
+  const float step = lr * inv_bc1;
+#pragma unroll
+  for (int u = 0; u < ADAM_PIECE4 / 256; ++u) {
+    const unsigned long long i = base + u * 256 + threadIdx.x;
+    if (i < n4) {
+      float4 pp = ((float4*)p)[i], mm = ((float4*)m)[i], vv = ((float4*)v)[i];
+      const float4 gg = ((const float4*)g)[i];
+      float4 ee = ema ? ((float4*)ema)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+      float* P = (float*)&pp; float* M = (float*)&mm; float* V = (float*)&vv; const float* G = (const float*)&gg; float* E = (float*)&ee;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        adamw_element(P[e], M[e], V[e], G[e], gs, beta1, beta2, eps, decay, step, inv_sqrt_bc2);
+        E[e] = ema_element(E[e], P[e], omd);
+      }
+      ((float4*)p)[i] = pp; ((float4*)m)[i] = mm; ((float4*)v)[i] = vv;
+      if (ema) ((float4*)ema)[i] = ee;
+    }
+  }
+  if (blockIdx.x == f0) {
+    for (unsigned long long i = n4 * 4 + threadIdx.x; i < n; i += 256) {
+      float P = p[i], M = m[i], V = v[i];
+      adamw_element(P, M, V, g[i], gs, beta1, beta2, eps, decay, step, inv_sqrt_bc2);
+      p[i] = P; m[i] = M; v[i] = V;
+      if (ema) ema[i] = ema_element(ema[i], P, omd);
+    }
+  }
+}
+
+// ---- exchange the contents of up to four buffer pairs in place (parameters <-> their average), same piece layout ----
+struct SwapSegs { float* a[4]; float* b[4]; unsigned long long n[4]; unsigned first[5]; int nseg; };
+__global__ __launch_bounds__(256) void swap_multi_kernel(const SwapSegs sg) {
+  int k = 0;
+#pragma unroll
+  for (int q = 1; q < 4; ++q)
+    if (q < sg.nseg && blockIdx.x >= sg.first[q]) k = q;
+#define SEL(a) (k == 0 ? sg.a[0] : (k == 1 ? sg.a[1] : (k == 2 ? sg.a[2] : sg.a[3])))
+  float* a = SEL(a); float* b = SEL(b);
+  const unsigned long long n = SEL(n);
+  const unsigned f0 = SEL(first);
+#undef SEL
+  const unsigned long long n4 = n / 4;
+  const unsigned long long base = (unsigned long long)(blockIdx.x - f0) * ADAM_PIECE4;
+#pragma unroll
+  for (int u = 0; u < ADAM_PIECE4 / 256; ++u) {
+    const unsigned long long i = base + u * 256 + threadIdx.x;
+    if (i < n4) {
+      const float4 x = ((float4*)a)[i], y = ((float4*)b)[i];
+      ((float4*)a)[i] = y; ((float4*)b)[i] = x;
+    }
+  }
+  if (blockIdx.x == f0)
+    for (unsigned long long i = n4 * 4 + threadIdx.x; i < n; i += 256) {
+      const float x = a[i], y = b[i];
+      a[i] = y; b[i] = x;
+    }
+}
+
 }  // namespace
 
 extern "C" int rovit_clip_coef(const float* sq, float max_norm, float* coef, float* norm_out, rovit_stream_t stream) {
@@ -295,5 +403,64 @@ extern "C" int rovit_adamw_flat_multi(float* const* p, const float* const* g, fl
   sg.first[n_segs] = blocks; sg.nseg = n_segs;
   hipLaunchKernelGGL(adamw_multi_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, sg, grad_scale, beta1, beta2, eps, weight_decay);
   ROVIT_CHECK_LAUNCH("adamw_multi_kernel");
+  return ROVIT_OK;
+}
+
+// rovit_adamw_flat_multi with an exponential moving average of the parameters updated in the same launch: after the element's new p,
+// e += omd * (p - e) with omd = (float)(1 - ema_decay[i]).  g[i] == NULL: EMA only (p read; p, m, v untouched; m[i], v[i] may be NULL, t[i]
+// ignored).  ema[i] == NULL: plain AdamW for that segment.
+extern "C" int rovit_adamw_ema_flat_multi(float* const* p, const float* const* g, float* const* m, float* const* v, float* const* ema,
+                                          const size_t* n, const float* lr, const int* t, const float* ema_decay, int n_segs,
+                                          const float* grad_scale, float beta1, float beta2, float eps, float weight_decay, rovit_stream_t stream) {
+  ROVIT_CHECK_ARG(p && g && m && v && ema && n && lr && t && ema_decay, ROVIT_ERR_NULL, "adamw_ema_flat_multi: null pointer");
+  ROVIT_CHECK_ARG(n_segs >= 1 && n_segs <= 4, ROVIT_ERR_SHAPE, "adamw_ema_flat_multi: 1..4 segments, got %d", n_segs);
+  AdamEmaSegs sg{};
+  unsigned blocks = 0;
+  for (int i = 0; i < n_segs; ++i) {
+    ROVIT_CHECK_ARG(p[i] && (g[i] || ema[i]), ROVIT_ERR_NULL, "adamw_ema_flat_multi: null pointer in segment %d", i);
+    ROVIT_CHECK_ARG(rovit_aligned16(p[i]) && rovit_aligned16(g[i]) && rovit_aligned16(ema[i]), ROVIT_ERR_ALIGN,
+                    "adamw_ema_flat_multi: buffers of segment %d must be 16-byte aligned", i);
+    sg.p[i] = p[i]; sg.g[i] = g[i]; sg.e[i] = ema[i]; sg.n[i] = n[i];
+    if (g[i]) {
+      ROVIT_CHECK_ARG(m[i] && v[i], ROVIT_ERR_NULL, "adamw_ema_flat_multi: null moment buffer in segment %d", i);
+      ROVIT_CHECK_ARG(t[i] >= 1, ROVIT_ERR_SHAPE, "adamw_ema_flat_multi: step count must be >= 1");
+      ROVIT_CHECK_ARG(rovit_aligned16(m[i]) && rovit_aligned16(v[i]), ROVIT_ERR_ALIGN,
+                      "adamw_ema_flat_multi: buffers of segment %d must be 16-byte aligned", i);
+      const double bc1 = 1.0 - pow((double)beta1, t[i]), bc2 = 1.0 - pow((double)beta2, t[i]);
+      sg.m[i] = m[i]; sg.v[i] = v[i];
+      sg.lr[i] = lr[i]; sg.inv_bc1[i] = (float)(1.0 / bc1); sg.inv_sqrt_bc2[i] = (float)(1.0 / sqrt(bc2));
+    }
+    if (ema[i]) {
+      ROVIT_CHECK_ARG(ema_decay[i] >= 0.f && ema_decay[i] < 1.f, ROVIT_ERR_SHAPE,
+                      "adamw_ema_flat_multi: ema_decay of segment %d must be in [0, 1), got %g", i, (double)ema_decay[i]);
+      sg.omd[i] = (float)(1.0 - (double)ema_decay[i]);
+    }
+    sg.first[i] = blocks;
+    const unsigned b = (unsigned)((n[i] / 4 + ADAM_PIECE4 - 1) / ADAM_PIECE4);
+    blocks += b < 1 ? 1 : b;
+  }
+  sg.first[n_segs] = blocks; sg.nseg = n_segs;
+  hipLaunchKernelGGL(adamw_ema_multi_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, sg, grad_scale, beta1, beta2, eps, weight_decay);
+  ROVIT_CHECK_LAUNCH("adamw_ema_multi_kernel");
+  return ROVIT_OK;
+}
+
+// a[i] <-> b[i] for up to four buffer pairs in one launch (HOST arrays; 16-byte aligned; a pair must not overlap)
+extern "C" int rovit_swap_flat_multi(float* const* a, float* const* b, const size_t* n, int n_segs, rovit_stream_t stream) {
+  ROVIT_CHECK_ARG(a && b && n, ROVIT_ERR_NULL, "swap_flat_multi: null pointer");
+  ROVIT_CHECK_ARG(n_segs >= 1 && n_segs <= 4, ROVIT_ERR_SHAPE, "swap_flat_multi: 1..4 segments, got %d", n_segs);
+  SwapSegs sg{};
+  unsigned blocks = 0;
+  for (int i = 0; i < n_segs; ++i) {
+    ROVIT_CHECK_ARG(a[i] && b[i], ROVIT_ERR_NULL, "swap_flat_multi: null pointer in segment %d", i);
+    ROVIT_CHECK_ARG(rovit_aligned16(a[i]) && rovit_aligned16(b[i]), ROVIT_ERR_ALIGN,
+                    "swap_flat_multi: buffers of segment %d must be 16-byte aligned", i);
+    sg.a[i] = a[i]; sg.b[i] = b[i]; sg.n[i] = n[i]; sg.first[i] = blocks;
+    const unsigned bl = (unsigned)((n[i] / 4 + ADAM_PIECE4 - 1) / ADAM_PIECE4);
+    blocks += bl < 1 ? 1 : bl;
+  }
+  sg.first[n_segs] = blocks; sg.nseg = n_segs;
+  hipLaunchKernelGGL(swap_multi_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, sg);
+  ROVIT_CHECK_LAUNCH("swap_multi_kernel");
   return ROVIT_OK;
 }

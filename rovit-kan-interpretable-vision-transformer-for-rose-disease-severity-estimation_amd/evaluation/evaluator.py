@@ -78,13 +78,18 @@ class Evaluator:
         print(f'Results saved to {path}')
 
 
-def load_model_for_evaluation(checkpoint_path: Path, config, device):
+def load_model_for_evaluation(checkpoint_path: Path, config, device, use_ema=None):
+    """``use_ema``: None loads the checkpoint's ``'ema_state_dict'`` (the averaged weights of an ``ema_decay`` run) when it has one and
+    ``'model_state_dict'`` otherwise; True insists on the average (KeyError without one); False loads the raw weights."""
     from models.rovit_kan import RoViTKAN
     mc = config.model
     model = RoViTKAN(embed_dim=mc.embed_dim, hidden_dim=mc.hidden_dim, num_classes=config.data.num_classes, kan_layers=mc.kan_layers,
                      kan_num_knots=mc.kan_num_knots, kan_degree=mc.kan_degree, dropout=mc.dropout, pretrained=False)
     checkpoint = torch.load(checkpoint_path, map_location=device, weights_only=False)
-    model.load_state_dict(checkpoint['model_state_dict'])
+    if use_ema and 'ema_state_dict' not in checkpoint:
+        raise KeyError(f'{checkpoint_path} holds no ema_state_dict (use_ema=True)')
+    averaged = use_ema is not False and 'ema_state_dict' in checkpoint
+    model.load_state_dict(checkpoint['ema_state_dict' if averaged else 'model_state_dict'])
     model.to(device)
     model.eval()
     print(f'Model loaded from {checkpoint_path}')

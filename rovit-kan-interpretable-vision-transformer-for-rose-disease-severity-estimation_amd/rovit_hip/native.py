@@ -110,6 +110,8 @@ SIGNATURES = {
     'rovit_adamw_flat': (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _f, _f, _f, _f, _f, _i, _vp]),
     'rovit_sq_norm_clip': (_i, [_vp, _vp, _i, _f, _vp, _vp, _vp, _sz, _vp]),
     'rovit_adamw_flat_multi': (_i, [_vp] * 7 + [_i, _vp, _f, _f, _f, _f, _vp]),
+    'rovit_adamw_ema_flat_multi': (_i, [_vp] * 9 + [_i, _vp, _f, _f, _f, _f, _vp]),
+    'rovit_swap_flat_multi': (_i, [_vp, _vp, _vp, _i, _vp]),
     'rovit_joint_loss_mixed': (_i, [_vp, _vp]),
     'rovit_train_finalize': (_i, [_vp, _vp]),
     'rovit_eval_partials_doubles': (_sz, [_i]),

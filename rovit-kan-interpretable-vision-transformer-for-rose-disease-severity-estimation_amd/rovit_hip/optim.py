@@ -15,12 +15,19 @@ either way, so the norm is bit-reproducible) -> fused clip-scale + decoupled wei
 A module whose parameters received no gradient this step (curriculum stage gating) is skipped entirely, like
 torch.optim.AdamW skips parameters with ``grad is None``; its bias-correction step count does not advance.
 
+``ema_decay`` (off by default; the reference has no weight average, so its semantics are this repository's: parity unpinned) keeps an
+exponential moving average of every parameter in two more flat buffers, ``ema_flat`` / ``o_ema``, laid out like ``p_flat`` / ``o_flat``.
+The average is one more stream of the AdamW launch (rovit_adamw_ema_flat_multi: read ema, write ema; ``e += (1 - d) (p_new - e)``), so a
+step makes the launches it makes without it.  ``swap_ema()`` exchanges parameters and average in place for validation (one launch each
+way), ``ema_state_dict()`` / ``load_ema_state_dict()`` read and write the average under the model's own keys.
+
 ``RoViTAdamW`` is a ``torch.optim.Optimizer`` with the reference's two parameter groups (``param_groups[0]`` =
 backbone at lr/10, ``param_groups[1]`` = heads/KAN at lr), so ``CosineAnnealingLR`` (training/optimizer.py:35-44) and
 ``get_lr`` (:47-49) work on it unchanged; ``build_optimizer`` / ``build_scheduler`` / ``get_lr`` mirror that file.
 """
 from __future__ import annotations
 
+import contextlib
 from typing import List, Optional
 
 import torch
@@ -31,6 +38,15 @@ from .native import call, ptr, stream_ptr
 
 def _pad4(n: int) -> int:
     return (n + 3) // 4 * 4
+
+
+def ema_reference(e, p_new, decay):
+    """One step of the average in numpy fp64, ``e + omd (p_new - e)``, with ``omd`` the fp32 value the host hands the kernel:
+    ``(float)(1 - (double)(float)decay)`` (rovit_adamw_ema_flat_multi).  What the tests compare the kernel's fp32 recursion against."""
+    import numpy as np
+    omd = np.float64(np.float32(1.0 - np.float64(np.float32(decay))))
+    e = np.asarray(e, dtype=np.float64)
+    return e + omd * (np.asarray(p_new, dtype=np.float64) - e)
 
 
 class _Segment:
@@ -50,7 +66,13 @@ class _Segment:
 
 class RoViTAdamW(torch.optim.Optimizer):
     def __init__(self, model, lr: float = 1e-4, weight_decay: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
-                 max_grad_norm: Optional[float] = 1.0):
+                 max_grad_norm: Optional[float] = 1.0, ema_decay: Optional[float] = None, ema_warmup: bool = True):
+        if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
+            raise ValueError(f'ema_decay must be in [0, 1), got {ema_decay}')
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        self.ema_flat = self.o_ema = None
+        self._swapped = False
         self.model = model
         self.max_grad_norm = max_grad_norm
         self.vit = model.backbone.model
@@ -99,7 +121,7 @@ class RoViTAdamW(torch.optim.Optimizer):
                                        '(model.to(device); building the optimizer earlier is fine)')
         if any(p.device != dev for p in list(self.bb_params) + self.other_params):
             raise native.RovitHipError('RoViTAdamW: all parameters must live on one device')
-        old = None if self.p_flat is None else (self.m_flat, self.v_flat, self.o_m, self.o_v)
+        old = None if self.p_flat is None else (self.m_flat, self.v_flat, self.o_m, self.o_v, self.ema_flat, self.o_ema)
         self.p_flat = self._rehome(self.bb_params, self._bb_offsets, self._bb_total, dev)
         self.m_flat = torch.zeros_like(self.p_flat)
         self.v_flat = torch.zeros_like(self.p_flat)
@@ -113,9 +135,12 @@ class RoViTAdamW(torch.optim.Optimizer):
         self.o_v = torch.zeros_like(self.o_flat)
         # the fused head phase (models/rovit_kan.py) may write its parameter gradients straight into these views: no per-step pack copy
         self.model._head_grad_views = {p.data_ptr(): v for s in self.segments for p, v in zip(s.params, s.grad_views)}
-        if old is not None:                                  # the model was moved after the buffers existed: keep the moments
-            for dst, src in zip((self.m_flat, self.v_flat, self.o_m, self.o_v), old):
-                dst.copy_(src)
+        if self.ema_decay is not None:                       # the average starts as the parameters; the padding floats stay zero
+            self.ema_flat, self.o_ema = self.p_flat.clone(), self.o_flat.clone()
+        if old is not None:                                  # the model was moved after the buffers existed: keep the moments (and the average)
+            for dst, src in zip((self.m_flat, self.v_flat, self.o_m, self.o_v, self.ema_flat, self.o_ema), old):
+                if dst is not None and src is not None:
+                    dst.copy_(src)
         self._sq = torch.zeros((), dtype=torch.float32, device=dev)
         # ticket + fixed-order block partials of rovit_sq_norm_clip (one per 4096 gradient floats; bit-reproducible norm)
         self._sq_scratch = torch.zeros(16 + (self._bb_total + 4095) // 4096 + (self._o_total + 4095) // 4096 + 8, dtype=torch.float32, device=dev)
@@ -194,6 +219,8 @@ class RoViTAdamW(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        if self._swapped:
+            raise native.RovitHipError('optimizer.step() inside swap_ema(): the parameters are the average there')
         if self._stale():
             if any(p.grad is not None for p in self.bb_params) and self.p_flat is not None:
                 raise native.RovitHipError('the model was moved between backward and optimizer.step(): run the step again')
@@ -226,12 +253,19 @@ class RoViTAdamW(torch.optim.Optimizer):
                 self.last_grad_norm = self._norm
                 coef = ptr(self._coef)
         # AdamW over the backbone and every run of active segments that share a step count: ONE launch
+        # (with ema_decay: the same launch updates the average; a frozen segment that has been stepped before rides along as an
+        # EMA-only segment -- its average still trails its parameters -- and one with t == 0 is skipped: its average IS its parameters)
+        ema = self.ema_decay is not None
         segs = []
         hyper = lambda g_: (float(g_['betas'][0]), float(g_['betas'][1]), float(g_['eps']), float(g_['weight_decay']))
         if bb:
             self.t += 1
-            segs.append((self.p_flat, eng.grad_flat, self.m_flat, self.v_flat, self.p_flat.numel(), float(gb['lr']), self.t, hyper(gb)))
+            segs.append((self.p_flat, eng.grad_flat, self.m_flat, self.v_flat, self.p_flat.numel(), float(gb['lr']), self.t, hyper(gb),
+                         self.ema_flat, self.ema_decay_at(self.t)))
             eng._prep_key = None            # parameters changed behind torch's version counters: re-prepare weights
+        elif ema and self.t > 0:
+            segs.append((self.p_flat, None, None, None, self.p_flat.numel(), float(gb['lr']), self.t, hyper(gb),
+                         self.ema_flat, self.ema_decay_at(self.t)))
         if active and hasattr(self.model, 'kan_module') and hasattr(self.model.kan_module, 'invalidate_prepared'):
             self.model.kan_module.invalidate_prepared()      # parameters change behind torch's version counters
         for first, last in self._runs(active, same_t=True):
@@ -239,17 +273,119 @@ class RoViTAdamW(torch.optim.Optimizer):
             for s in active[active.index(first):active.index(last) + 1]:
                 s.t += 1
             o = first.offset
-            segs.append((self.o_flat[o:], self.o_grad[o:], self.o_m[o:], self.o_v[o:], n, float(gh['lr']), first.t, hyper(gh)))
+            segs.append((self.o_flat[o:], self.o_grad[o:], self.o_m[o:], self.o_v[o:], n, float(gh['lr']), first.t, hyper(gh),
+                         self.o_ema[o:] if ema else None, self.ema_decay_at(first.t)))
+        if ema:
+            for first, last in self._runs([s for s in self.segments if s not in active and s.t > 0], same_t=True):
+                o = first.offset
+                segs.append((self.o_flat[o:], None, None, None, last.offset + last.numel - o, float(gh['lr']), first.t, hyper(gh),
+                             self.o_ema[o:], self.ema_decay_at(first.t)))
         # (one launch when the groups share betas / eps / weight decay, as the reference's do; else one per distinct setting)
         for hp in dict.fromkeys(c[7] for c in segs):
             same = [c for c in segs if c[7] == hp]
             for i in range(0, len(same), 4):
                 chunk = same[i:i + 4]
                 pa = lambda k: (C.c_void_p * len(chunk))(*[ptr(c[k]) for c in chunk])
+                if ema:
+                    call('rovit_adamw_ema_flat_multi', pa(0), pa(1), pa(2), pa(3), pa(8), (C.c_size_t * len(chunk))(*[c[4] for c in chunk]),
+                         (C.c_float * len(chunk))(*[c[5] for c in chunk]), (C.c_int * len(chunk))(*[c[6] for c in chunk]),
+                         (C.c_float * len(chunk))(*[c[9] for c in chunk]), len(chunk), coef, hp[0], hp[1], hp[2], hp[3], sp)
+                    continue
                 call('rovit_adamw_flat_multi', pa(0), pa(1), pa(2), pa(3), (C.c_size_t * len(chunk))(*[c[4] for c in chunk]),
                      (C.c_float * len(chunk))(*[c[5] for c in chunk]), (C.c_int * len(chunk))(*[c[6] for c in chunk]), len(chunk), coef,
                      hp[0], hp[1], hp[2], hp[3], sp)
         return loss
+
+    # ---- the weight average ----------------------------------------------------------------------------------------------------------
+    def ema_decay_at(self, t: int) -> float:
+        """Decay of a segment's t-th step (t counted after that step's increment): ``min(d, (1 + t) / (10 + t))`` with warm-up (the rule
+        of tf.train.ExponentialMovingAverage), else ``d``; 0.0 with the average off."""
+        if self.ema_decay is None:
+            return 0.0
+        return min(self.ema_decay, (1.0 + t) / (10.0 + t)) if self.ema_warmup else self.ema_decay
+
+    def _require_ema(self, what: str):
+        if self.ema_decay is None:
+            raise native.RovitHipError(f'{what}: this optimizer keeps no weight average (ema_decay is None)')
+
+    def _ema_buffers(self):
+        """(backbone, head / KAN) buffers that hold the average right now: the parameter buffers inside swap_ema(); the pending
+        checkpoint state, or (None, None) = the parameters themselves, while the flat buffers do not exist yet."""
+        if self._stale() and self.bb_params[0].device.type == 'cuda':
+            self._build()
+        if self.p_flat is None:
+            pend = self._pending_flat or {}
+            return pend.get('ema_flat'), pend.get('o_ema')
+        return (self.p_flat, self.o_flat) if self._swapped else (self.ema_flat, self.o_ema)
+
+    def _ema_slots(self):
+        """id(parameter) -> (0 = backbone buffer | 1 = head / KAN buffer, offset)."""
+        slots = {id(p): (0, o) for p, o in zip(self.bb_params, self._bb_offsets)}
+        slots.update({id(p): (1, o) for s in self.segments for p, o in zip(s.params, s.offsets)})
+        return slots
+
+    @torch.no_grad()
+    def ema_state_dict(self):
+        """The average under the keys and shapes of ``model.state_dict()``: parameters are clones out of the average buffers, buffers
+        (the KAN knots) are the model's."""
+        self._require_ema('ema_state_dict')
+        bufs, slots = self._ema_buffers(), self._ema_slots()
+        params = dict(self.model.named_parameters())
+        sd = {}
+        for k, v in self.model.state_dict().items():
+            p = params.get(k)
+            if p is None or bufs[slots[id(p)][0]] is None:
+                sd[k] = v.detach().clone()
+            else:
+                which, o = slots[id(p)]
+                sd[k] = bufs[which][o:o + p.numel()].view_as(p).clone()
+        return sd
+
+    @torch.no_grad()
+    def load_ema_state_dict(self, sd):
+        """Inverse of ``ema_state_dict``: every parameter's entry is copied into the average (entries of buffers are not parameters and
+        are left to ``model.load_state_dict``).  Needs the model on the device."""
+        self._require_ema('load_ema_state_dict')
+        if self._stale():
+            self._build()
+        bufs, slots = self._ema_buffers(), self._ema_slots()
+        for k, p in self.model.named_parameters():
+            which, o = slots[id(p)]
+            bufs[which][o:o + p.numel()].view_as(p).copy_(sd[k])
+        if self._swapped:                                    # the average is under the model right now
+            self.engine._prep_key = None
+            if hasattr(self.model, 'kan_module') and hasattr(self.model.kan_module, 'invalidate_prepared'):
+                self.model.kan_module.invalidate_prepared()
+
+    def _swap(self):
+        import ctypes as C
+        pairs = [(self.p_flat, self.ema_flat), (self.o_flat, self.o_ema)]
+        call('rovit_swap_flat_multi', (C.c_void_p * 2)(*[ptr(a) for a, _ in pairs]), (C.c_void_p * 2)(*[ptr(b) for _, b in pairs]),
+             (C.c_size_t * 2)(*[a.numel() for a, _ in pairs]), 2, stream_ptr())
+        self.engine._prep_key = None                         # parameters changed behind torch's version counters
+        if hasattr(self.model, 'kan_module') and hasattr(self.model.kan_module, 'invalidate_prepared'):
+            self.model.kan_module.invalidate_prepared()
+
+    @contextlib.contextmanager
+    def swap_ema(self):
+        """``with optimizer.swap_ema(): validate(model, ...)`` -- the model computes with the averaged weights inside the block.
+        Parameters and average change places in the flat buffers (one rovit_swap_flat_multi launch on entry, one on exit; the prepared
+        bf16 / KAN weights are invalidated both times), so no tensor is reallocated and every view stays valid.  Meant for ``no_grad``
+        use between steps: ``step()`` refuses to run inside, and gradients computed inside would be gradients at the average."""
+        self._require_ema('swap_ema')
+        if self._swapped:
+            raise native.RovitHipError('swap_ema() entered twice')
+        if self._stale():
+            self._build()
+        with torch.no_grad():
+            self._swap()
+        self._swapped = True
+        try:
+            yield self
+        finally:
+            with torch.no_grad():
+                self._swap()
+            self._swapped = False
 
     @staticmethod
     def _runs(active, same_t: bool = False):
@@ -272,6 +408,9 @@ class RoViTAdamW(torch.optim.Optimizer):
             return sd
         sd['rovit_flat'] = {'m_flat': self.m_flat.clone(), 'v_flat': self.v_flat.clone(), 'o_m': self.o_m.clone(),
                             'o_v': self.o_v.clone(), 't': self.t, 'segment_t': {s.name: s.t for s in self.segments}}
+        if self.ema_decay is not None:
+            e, oe = self._ema_buffers()
+            sd['rovit_flat'].update(ema_flat=e.clone(), o_ema=oe.clone())
         return sd
 
     def _load_flat(self, flat):
@@ -280,6 +419,10 @@ class RoViTAdamW(torch.optim.Optimizer):
         self.t = int(flat['t'])
         for s in self.segments:
             s.t = int(flat['segment_t'].get(s.name, 0))
+        if self.ema_decay is not None:                       # a state without an average (saved with EMA off): start from the parameters
+            e, oe = self._ema_buffers()
+            e.copy_(flat['ema_flat'] if 'ema_flat' in flat else self.p_flat)
+            oe.copy_(flat['o_ema'] if 'o_ema' in flat else self.o_flat)
 
     def load_state_dict(self, state_dict):
         flat = state_dict.get('rovit_flat')
@@ -296,7 +439,8 @@ class RoViTAdamW(torch.optim.Optimizer):
 def build_optimizer(model, config) -> RoViTAdamW:
     """training/optimizer.py:7-32 on the HIP path (clip_grad_norm_ of trainer.py:123-126 is inside step())."""
     clip = getattr(getattr(config, 'flags', None), 'gradient_clip', 1.0)
-    return RoViTAdamW(model, lr=config.train.learning_rate, weight_decay=config.train.weight_decay, max_grad_norm=clip)
+    return RoViTAdamW(model, lr=config.train.learning_rate, weight_decay=config.train.weight_decay, max_grad_norm=clip,
+                      ema_decay=getattr(config.train, 'ema_decay', None), ema_warmup=getattr(config.train, 'ema_warmup', True))
 
 
 def build_scheduler(optimizer, config):

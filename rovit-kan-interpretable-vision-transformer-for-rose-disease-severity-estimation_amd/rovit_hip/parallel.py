@@ -8,6 +8,9 @@ kernels run (bucketed overlap; default 2 buckets tapering 8 : 4 blocks = 14.2 / 
 of range hand-over on one MI355X, measured with a one-rank RCCL group; 3 buckets taper 6 : 4 : 2 blocks = 10.6 / 7.1 / 4.1 MB: large enough for xGMI's
 per-link bandwidth, and the last bucket, whose all-reduce is exposed, is the smallest).  Head/KAN gradients (0.7 MB) go in one flat bucket after backward.
 
+A weight average kept by the optimizer (``RoViTAdamW(ema_decay=...)``) needs no exchange: it is a function of the parameters, which are
+identical on every rank after the averaged all-reduce, so every rank holds the same average.
+
 The class only needs ``flat`` tensors and ranges, so its bucket logic is exercised on CPU with the gloo backend.
 """
 from __future__ import annotations

@@ -16,6 +16,9 @@ gradient_clip, freeze_backbone_epochs, curriculum), ``config.train`` (epochs, ea
   ``mixed_precision`` flag is accepted (and selects the branch above), no ``scaler_state_dict`` is written, one found at load is ignored.  What
   a scaler's skipped steps would have told the user is ``trainer.last_train_record.nonfinite_batches``, the batches of the last epoch whose
   total loss was not finite.
+* With an optimizer that keeps a weight average (``RoViTAdamW(ema_decay=...)``; the reference has none) ``val_epoch`` validates the
+  averaged weights (``optimizer.swap_ema()``), so early stopping and ``best_model.pth`` follow them; the checkpoint gains
+  ``'ema_state_dict'`` while ``'model_state_dict'`` stays the raw weights training resumes from.  Without one nothing changes.
 """
 from pathlib import Path
 from typing import Dict, List, Optional
@@ -68,7 +71,13 @@ class Trainer:
             print(f'  {record.nonfinite_batches} of {record.n_batches} batches had a non-finite loss')
         return metrics
 
+    def _has_ema(self) -> bool:
+        return getattr(self.optimizer, 'ema_decay', None) is not None
+
     def val_epoch(self) -> Dict[str, float]:
+        if self._has_ema():
+            with self.optimizer.swap_ema():
+                return validate(self.model, self.val_loader, self.loss_fn)
         return validate(self.model, self.val_loader, self.loss_fn)
 
     def fit(self) -> Dict[str, List[float]]:
@@ -108,10 +117,13 @@ class Trainer:
         return history
 
     def save_checkpoint(self, path, epoch: int, metrics: Dict) -> None:
-        """The reference's keys, minus ``scaler_state_dict`` (there is no scaler)."""
-        torch.save({'epoch': epoch, 'model_state_dict': self.model.state_dict(), 'optimizer_state_dict': self.optimizer.state_dict(),
-                    'scheduler_state_dict': self.scheduler.state_dict(), 'best_val_loss': self.best_val_loss, 'metrics': metrics,
-                    'config': self.config}, path)
+        """The reference's keys, minus ``scaler_state_dict`` (there is no scaler); plus ``ema_state_dict`` with an averaging optimizer."""
+        ck = {'epoch': epoch, 'model_state_dict': self.model.state_dict(), 'optimizer_state_dict': self.optimizer.state_dict(),
+              'scheduler_state_dict': self.scheduler.state_dict(), 'best_val_loss': self.best_val_loss, 'metrics': metrics,
+              'config': self.config}
+        if self._has_ema():
+            ck['ema_state_dict'] = self.optimizer.ema_state_dict()
+        torch.save(ck, path)
 
     def load_checkpoint(self, path) -> None:
         """Restores model, optimiser, scheduler and ``best_val_loss``; a ``scaler_state_dict`` (a reference checkpoint) is ignored.  The
@@ -119,6 +131,8 @@ class Trainer:
         checkpoint = torch.load(path, map_location=self.device, weights_only=False)
         self.model.load_state_dict(checkpoint['model_state_dict'])
         self.optimizer.load_state_dict(checkpoint['optimizer_state_dict'])
+        if self._has_ema() and 'ema_state_dict' in checkpoint:
+            self.optimizer.load_ema_state_dict(checkpoint['ema_state_dict'])
         self.scheduler.load_state_dict(checkpoint['scheduler_state_dict'])
         self.best_val_loss = checkpoint['best_val_loss']
         print(f"Checkpoint loaded from {path}\nEpoch: {checkpoint['epoch']}\nVal Loss: {checkpoint['best_val_loss']:.4f}")
