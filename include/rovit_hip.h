@@ -641,6 +641,57 @@ int rovit_eval_accumulate(const rovit_eval_batch* p, rovit_stream_t stream);
 int rovit_eval_finalize(const rovit_eval_final* p, rovit_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Non-parametric bootstrap of that score card (eval_bootstrap.hip): what the reference's ablation table (experiments/ablation.py:
+ * get_component_importance, the "delta Acc" column) lacks -- an interval per metric and, through equal draws for two models, a paired test.
+ * rovit_eval_bootstrap reads the accumulator's record arrays and the `less` counts the finalise left in rank_counts (words [0, n) of
+ * sev_true, [2n, 3n) of sev_pred), so rovit_eval_finalize must have run on the same rows first.
+ * Draw j of replicate r: Philox4x32-10, key = seed, counter = (j / 4, r, ROVIT_EVAL_BOOT_STREAM, 0); word j % 4 gives
+ *   idx = (word * n) >> 32 in 64-bit arithmetic (bias at most n / 2^32).  A function of (seed, r, j, n) alone: two accumulators of the
+ *   same length resample the same rows.
+ * Stratified (perm and starts both non-NULL): perm is a permutation of the rows grouped by true class, rows with a bad label last;
+ *   starts holds the C + 2 segment starts (starts[0] = 0, starts[C + 1] = n).  Draw j belongs to the segment s that contains j and picks
+ *   perm[starts[s] + ((word * n_s) >> 32)], n_s the segment's length: every replicate has the data's class supports.
+ * Ranks without a sort: with H[less[idx_j]] += 1 over the draws and P the exclusive prefix sum of H, the doubled tie-averaged rank of draw
+ *   j inside the resample is 2 P[v] + H[v] + 1, v = less[idx_j] (less[i] is the first sorted slot of row i's tie group).
+ * table (num_resamples, ROVIT_EVAL_BOOT_COLS) doubles, row r from replicate r's sums with the arithmetic of rovit_hip/evaluation.py
+ *   (metrics_from_block, f1_averages): accuracy, macro F1 (over the classes present in that replicate's labels or predictions), weighted
+ *   F1 (percent), MAE, Spearman's rho (NaN for a constant column or any non-finite value), Brier, ECE, then per class c precision,
+ *   recall, F1 (percent) at ROVIT_EVAL_BOOT_PRECISION / _RECALL / _F1 + c (0 for c >= C); zero division gives 0; the last column is 0.
+ * blocks, when not NULL: (num_resamples, ROVIT_EVAL_RESULT_WORDS) 8-byte words, replicate r's full result block in the ROVIT_EVAL_*
+ *   layout, every word written (unwritten words and the loss sums 0; the rank sums 0 beside a non-finite severity).
+ * Integers are added with integer atomics; every floating sum follows an order fixed by (n, the workgroup size, the draws): table and
+ * blocks are bit-identical from run to run, for every grid and on both sides of the threshold below.
+ * H lives in LDS for n <= ROVIT_EVAL_BOOT_LDS_ROWS.  Above it each workgroup uses 2 n words of `workspace`
+ * (rovit_eval_bootstrap_workspace_bytes(n, num_resamples) bytes), and the grid is capped at ROVIT_EVAL_BOOT_WORKSPACE_GRID workgroups:
+ * 1 GiB at the row limit.  max_workgroups > 0 lowers the grid further (one workgroup then serves several replicates in turn).
+ * Limits: those of the finalise; 1 <= num_resamples <= ROVIT_EVAL_BOOT_MAX_RESAMPLES.  A bad descriptor is refused before any launch.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define ROVIT_EVAL_BOOT_STREAM 0x426F6F74u      /* "Boot": counter word 2, apart from the dropout and augmentation streams */
+#define ROVIT_EVAL_BOOT_LDS_ROWS 16384
+#define ROVIT_EVAL_BOOT_WORKSPACE_GRID 128
+#define ROVIT_EVAL_BOOT_MAX_RESAMPLES 65536
+enum {
+  ROVIT_EVAL_BOOT_ACCURACY = 0, ROVIT_EVAL_BOOT_MACRO_F1 = 1, ROVIT_EVAL_BOOT_WEIGHTED_F1 = 2, ROVIT_EVAL_BOOT_MAE = 3,
+  ROVIT_EVAL_BOOT_RHO = 4, ROVIT_EVAL_BOOT_BRIER = 5, ROVIT_EVAL_BOOT_ECE = 6, ROVIT_EVAL_BOOT_PRECISION = 7,
+  ROVIT_EVAL_BOOT_RECALL = 15, ROVIT_EVAL_BOOT_F1 = 23, ROVIT_EVAL_BOOT_COLS = 32
+};
+typedef struct rovit_eval_boot {
+  int n, num_classes, n_bins, num_resamples, max_workgroups;
+  unsigned long long seed;
+  const float* probs; const int* pred; const int* label; const float* sev_pred; const float* sev_true;
+  const double* bin_edges;          /* n_bins + 1 */
+  const unsigned int* rank_counts;  /* 4 n, as rovit_eval_finalize left it */
+  const int* perm;                  /* (n) or NULL */
+  const int* starts;                /* (C + 2) or NULL */
+  unsigned int* workspace;          /* required for n > ROVIT_EVAL_BOOT_LDS_ROWS */
+  size_t workspace_bytes;
+  double* table;                    /* (num_resamples, ROVIT_EVAL_BOOT_COLS) */
+  void* blocks;                     /* (num_resamples, ROVIT_EVAL_RESULT_WORDS) 8-byte words, or NULL */
+} rovit_eval_boot;
+size_t rovit_eval_bootstrap_workspace_bytes(int n, int num_resamples);
+int rovit_eval_bootstrap(const rovit_eval_boot* p, rovit_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Per-edge activation statistics of one KAN layer over a data set (kan_stats.hip): what the edge functions of models/kan.py:70-95 do
  * ON DATA, where KANLayer.plot_activation (:97-114) and explainability/kan_viz.py only draw a few of them over [-1, 1].
  * For the layer's n input rows x (n, in_f), with s_ij(v) = sum_k spline_w[i,j,k] B_k(tanh v), phi_ij(v) = lin_w[j,i] v + s_ij(v) and

@@ -2,7 +2,8 @@
 launch per batch records the predictions on the device, one launch per epoch reduces them, one device-to-host copy brings the result
 block back.  Same constructor, same returned dict, same printed table, same ``evaluation_results.txt``.  Figures are not drawn
 (SURVEY.md section 2); ``evaluate(return_arrays=True)`` hands back the arrays the reference's plots are made from.  A last batch of one
-sample works (the reference's ``squeeze()`` + ``np.concatenate`` raises there)."""
+sample works (the reference's ``squeeze()`` + ``np.concatenate`` raises there).  ``evaluate(bootstrap=R)`` adds percentile bootstrap
+intervals (``EvalAccumulator.bootstrap``) to the dict, the table and the file; with the default 0 all three are what they were."""
 from pathlib import Path
 from typing import Dict
 
@@ -33,16 +34,20 @@ class Evaluator:
                 acc.update(self.model(images.to(self.device)), class_labels, severity_labels)
         return acc
 
-    def evaluate(self, return_arrays: bool = False):
+    def evaluate(self, return_arrays: bool = False, bootstrap: int = 0, bootstrap_seed: int = 0):
         print(f'\n{RULE}\nRunning Evaluation on Test Set\n{RULE}\n')
         names = list(self.config.data.class_names)
         acc = self.collect()
+        ci = acc.bootstrap(bootstrap, seed=bootstrap_seed) if bootstrap else None          # brings the point block along in its one copy
         m = acc.compute()                                   # the loop's one synchronisation
         metrics = {k: m[k] for k in ('accuracy', 'macro_f1', 'weighted_f1', 'mae', 'spearman_rho', 'spearman', 'brier_score', 'ece')}
         metrics['fps'] = fps(self.model, (1, 3, 224, 224), self.device, n=100)
         metrics['params'] = count_params(self.model)
         metrics['params_m'] = metrics['params'] / 1e6
         metrics['per_class'] = class_table(m['per_class'], names)
+        if ci is not None:
+            ci['per_class'] = class_table(ci['per_class'], names)
+            metrics['confidence_intervals'] = ci
         self._print_results(metrics)
         self._save_results(metrics)
         return (metrics, acc.arrays()) if return_arrays else metrics
@@ -52,7 +57,14 @@ class Evaluator:
         rows = (('Accuracy:', f"{metrics['accuracy']:.2f}%"), ('Macro F1:', f"{metrics['macro_f1']:.2f}%"), ('MAE:', f"{metrics['mae']:.4f}"),
                 (rho_label, f"{metrics['spearman_rho']:.4f}"), ('Brier Score:', f"{metrics['brier_score']:.4f}"),
                 ('ECE:', f"{metrics['ece']:.4f}"), ('FPS:', f"{metrics['fps']:.1f}"), ('Parameters:', f"{metrics['params']:,}"))
-        return [f'{label:<16}{value}' for label, value in rows]
+        ci = metrics.get('confidence_intervals')
+        if ci is None:
+            return [f'{label:<16}{value}' for label, value in rows]
+        # the bootstrap column: standard error and percentile interval, in the digits of the value beside it
+        keys = ('accuracy', 'macro_f1', 'mae', 'spearman_rho', 'brier_score', 'ece', None, None)
+        column = ['' if k is None else (f"± {ci[k]['se']:.2f} [{ci[k]['lo']:.2f}, {ci[k]['hi']:.2f}]" if k in ('accuracy', 'macro_f1') else
+                                        f"± {ci[k]['se']:.4f} [{ci[k]['lo']:.4f}, {ci[k]['hi']:.4f}]") for k in keys]
+        return [f'{label:<16}{value:<12}{extra}'.rstrip() for (label, value), extra in zip(rows, column)]
 
     def _print_results(self, metrics: Dict) -> None:
         print('\n'.join(['', RULE, 'Evaluation Results', RULE] + self._summary(metrics, 'Spearman rho:') + [RULE, '']))

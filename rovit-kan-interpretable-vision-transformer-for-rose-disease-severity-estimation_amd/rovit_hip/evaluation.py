@@ -9,6 +9,10 @@ predicted and true severity, exp(0.5 log_var) and, optionally, the five loss val
 the host already knows.  ``compute`` launches ``rovit_eval_finalize`` and copies its 272-word result block to the host: the epoch's only
 synchronisation.  Everything reported is derived from that block on the host in fp64.
 
+``EvalAccumulator.bootstrap`` and ``paired_bootstrap`` put percentile intervals and a paired test on those numbers
+(``rovit_eval_bootstrap``: every resample's score card on the device, one copy for the whole call); ``bootstrap_reference`` is their
+numpy restatement.
+
 On CPU tensors the same class runs the plain torch / numpy fp64 restatement below (``result_block_from_arrays``), as
 ``JointLoss._forward_tensor_ops`` does: the host logic is testable without a GPU, and ``evaluation.metrics`` is built on it.
 """
@@ -197,6 +201,8 @@ class EvalAccumulator:
         self._cpu: List[Dict[str, torch.Tensor]] = []          # CPU path: the batches as they came
         self._cpu_losses: List[torch.Tensor] = []
         self._block: Optional[np.ndarray] = None
+        self._block_dev: Optional[torch.Tensor] = None         # the finalise's block and rank counts on the device: bootstrap() reads them
+        self._rank_counts: Optional[torch.Tensor] = None
 
     # -- device record arrays --
     _FIELDS = (('probs', torch.float32), ('pred', torch.int32), ('label', torch.int32), ('sev_pred', torch.float32),
@@ -245,7 +251,7 @@ class EvalAccumulator:
             self.device = logits.device
         elif logits.device != self.device:
             raise RovitHipError(f'EvalAccumulator.update: batch on {logits.device}, earlier batches on {self.device}; reset() first')
-        self._block = None
+        self._block = self._block_dev = self._rank_counts = None
         if lv is not None:
             self._has_uncertainty = True
         if not logits.is_cuda:
@@ -309,6 +315,14 @@ class EvalAccumulator:
             self._block = result_block_from_arrays(a['label'], a['pred'], a['probs'], a['sev_true'], a['sev_pred'], self.num_classes,
                                                    self.n_bins, rows)
             return self._block
+        self._block = self._finalize().cpu().numpy()     # the single device-to-host copy of the epoch
+        return self._block
+
+    def _finalize(self) -> torch.Tensor:
+        """Launch ``rovit_eval_finalize`` (once per set of rows) and return its result block on the device.  The block and the rank
+        counts stay alive until the next ``update`` or ``reset``: they are the bootstrap kernel's inputs."""
+        if self._block_dev is not None:
+            return self._block_dev
         dev = self.device
         if self._edges is None:
             self._edges = torch.from_numpy(bin_edges(self.n_bins)).to(dev, non_blocking=True)
@@ -322,8 +336,8 @@ class EvalAccumulator:
         d.loss_table = native.ptr(self._loss_table)
         d.bin_edges, d.rank_counts, d.partials, d.result = (native.ptr(t) for t in (self._edges, counts, partials, result))
         native.call('rovit_eval_finalize', ctypes.byref(d), native.stream_ptr())
-        self._block = result.cpu().numpy()               # the single device-to-host copy of the epoch
-        return self._block
+        self._block_dev, self._rank_counts = result, counts
+        return result
 
     def compute(self) -> Dict:
         return metrics_from_block(self.result_block(), self.num_classes, self.n_bins, self.n_loss_rows)
@@ -340,6 +354,228 @@ class EvalAccumulator:
         return {'y_true': a['label'].astype(np.int64), 'y_pred': a['pred'].astype(np.int64), 'y_probs': a['probs'],
                 'severity_true': a['sev_true'], 'severity_pred': a['sev_pred'],
                 'uncertainty': a['uncertainty'] if self._has_uncertainty else None}
+
+    # -- bootstrap --
+    def _bootstrap_launch(self, num_resamples: int, seed: int, stratified: bool, table: torch.Tensor, blocks: Optional[torch.Tensor],
+                          max_workgroups: int = 0) -> torch.Tensor:
+        """Device path: the finalise if it has not run on these rows, then ``rovit_eval_bootstrap`` into the caller's int64 views
+        (``table``: R * EVAL_BOOT_COLS words, ``blocks``: R * EVAL_RESULT_WORDS words or None).  Returns the point block on the
+        device.  Nothing here synchronises."""
+        block = self._finalize()
+        dev, n, C = self.device, self.n, self.num_classes
+        perm = starts = workspace = None
+        if stratified:
+            label = self._rec['label'][:n].long()
+            key = torch.where(label < 0, torch.full_like(label, C), label)           # bad labels: a last segment of their own
+            perm = torch.sort(key, stable=True)[1].int()
+            # the class counts by index_add_, not torch.bincount: bincount reads its output size back from the device
+            counts = torch.zeros(C + 1, dtype=torch.int64, device=dev).index_add_(0, key, torch.ones_like(key))
+            starts = torch.cat([counts.new_zeros(1), torch.cumsum(counts, 0)]).int()
+        ws_bytes = native.load().rovit_eval_bootstrap_workspace_bytes(n, num_resamples)
+        if ws_bytes:
+            workspace = torch.empty(ws_bytes // 4, dtype=torch.int32, device=dev)
+        d = native.EvalBoot()
+        d.n, d.num_classes, d.n_bins, d.num_resamples, d.max_workgroups, d.seed = n, C, self.n_bins, num_resamples, max_workgroups, seed
+        for k in ('probs', 'pred', 'label', 'sev_pred', 'sev_true'):
+            setattr(d, k, native.ptr(self._rec[k]))
+        d.bin_edges, d.rank_counts, d.perm, d.starts = (native.ptr(t) for t in (self._edges, self._rank_counts, perm, starts))
+        d.workspace, d.workspace_bytes = native.ptr(workspace), ws_bytes
+        d.table, d.blocks = native.ptr(table), native.ptr(blocks)
+        native.call('rovit_eval_bootstrap', ctypes.byref(d), native.stream_ptr())
+        return block
+
+    def bootstrap(self, num_resamples: int = 1000, seed: int = 0, confidence: float = 0.95, stratified: bool = False,
+                  return_table: bool = False, return_blocks: bool = False, _max_workgroups: int = 0) -> Dict:
+        """Percentile bootstrap of the score card: per metric ``{'value', 'mean', 'se', 'lo', 'hi'}`` -- the point estimate of
+        ``compute()``, the mean and the standard deviation (ddof = 1) over the replicates, and the ``confidence`` percentile interval
+        (``np.nanquantile``, linear); the per-class precision / recall / F1 under ``'per_class'``; the number of replicates whose rho
+        is NaN beside rho (``'n_nan'``).  ``stratified`` resamples inside each true class, so every replicate keeps the supports.
+        ``return_table`` adds the (R, EVAL_BOOT_COLS) metric table, ``return_blocks`` every replicate's result block (R, 272).
+        On the device the call makes ONE device-to-host copy; it brings the point block along when ``compute()`` has not run yet.
+        Class labels outside [0, C) raise, as in ``compute()``."""
+        R = _check_bootstrap_args(num_resamples, seed, confidence)
+        if self.n < 1:
+            raise RovitHipError('EvalAccumulator: nothing recorded yet')
+        W, COLS = native.EVAL_RESULT_WORDS, native.EVAL_BOOT_COLS
+        if self.device.type != 'cuda':
+            point = self.compute()
+            table, blocks = bootstrap_reference(self.arrays(), self.num_classes, self.n_bins, R, seed, stratified)
+        else:
+            out = torch.empty(W + R * COLS + (R * W if return_blocks else 0), dtype=torch.int64, device=self.device)
+            block = self._bootstrap_launch(R, seed, stratified, out[W:W + R * COLS], out[W + R * COLS:] if return_blocks else None,
+                                           _max_workgroups)
+            out[:W].copy_(block)
+            host = out.cpu().numpy()                         # the call's single device-to-host copy
+            if self._block is None:
+                self._block = host[:W].copy()
+            point = self.compute()
+            table = host[W:W + R * COLS].view(np.float64).reshape(R, COLS)
+            blocks = host[W + R * COLS:].reshape(R, W) if return_blocks else None
+        res = {name: _interval(table[:, col], point[name], confidence) for name, col in BOOT_METRICS}
+        res['spearman_rho']['n_nan'] = int(np.isnan(table[:, native.EVAL_BOOT_RHO]).sum())
+        res['per_class'] = [{k: _interval(table[:, col + c], point['per_class'][c][k], confidence) for k, col in BOOT_CLASS_METRICS}
+                            for c in range(self.num_classes)]
+        res.update(num_resamples=R, seed=seed, confidence=confidence, stratified=bool(stratified))
+        if return_table:
+            res['table'] = table
+        if return_blocks:
+            res['blocks'] = blocks
+        return res
+
+# ---- bootstrap: restatement and summaries ---------------------------------------------------------------------------------------
+
+BOOT_METRICS = (('accuracy', native.EVAL_BOOT_ACCURACY), ('macro_f1', native.EVAL_BOOT_MACRO_F1), ('weighted_f1', native.EVAL_BOOT_WEIGHTED_F1),
+                ('mae', native.EVAL_BOOT_MAE), ('spearman_rho', native.EVAL_BOOT_RHO), ('brier_score', native.EVAL_BOOT_BRIER),
+                ('ece', native.EVAL_BOOT_ECE))
+BOOT_CLASS_METRICS = (('precision', native.EVAL_BOOT_PRECISION), ('recall', native.EVAL_BOOT_RECALL), ('f1', native.EVAL_BOOT_F1))
+
+
+def _check_bootstrap_args(num_resamples, seed, confidence) -> int:
+    if not (isinstance(num_resamples, int) and 1 <= num_resamples <= native.EVAL_BOOT_MAX_RESAMPLES):
+        raise RovitHipError(f'bootstrap: num_resamples must be in 1..{native.EVAL_BOOT_MAX_RESAMPLES}, got {num_resamples!r}')
+    if not (isinstance(seed, int) and 0 <= seed < 1 << 64):
+        raise RovitHipError(f'bootstrap: seed must be an integer in [0, 2^64), got {seed!r}')
+    if not 0.0 < confidence < 1.0:
+        raise RovitHipError(f'bootstrap: confidence must lie in (0, 1), got {confidence!r}')
+    return num_resamples
+
+
+def stratification(y_true, num_classes: int):
+    """(perm, starts) of a stratified bootstrap: the rows in a stable order by true class with the bad labels last, and the C + 2
+    segment starts."""
+    y = np.asarray(y_true).astype(np.int64).reshape(-1)
+    key = np.where((y < 0) | (y >= num_classes), num_classes, y)
+    perm = np.argsort(key, kind='stable').astype(np.int64)
+    starts = np.concatenate([[0], np.cumsum(np.bincount(key, minlength=num_classes + 1))]).astype(np.int64)
+    return perm, starts
+
+
+def bootstrap_indices(n: int, r: int, seed: int, starts=None, perm=None) -> np.ndarray:
+    """The n rows replicate ``r`` draws, as ``rovit_eval_bootstrap`` draws them: Philox4x32-10 with key ``seed`` and counter
+    (j // 4, r, EVAL_BOOT_STREAM, 0); word j % 4 gives (word * n) >> 32.  With ``starts`` and ``perm`` (``stratification``) draw j stays
+    in the segment that contains j: perm[starts[s] + ((word * n_s) >> 32)]."""
+    from oracle.philox import philox4x32_10 as philox          # checker only, like the head-phase masks
+    j = np.arange(n, dtype=np.uint64)
+    words = philox([j >> np.uint64(2), np.full(n, r, np.uint64), np.full(n, native.EVAL_BOOT_STREAM, np.uint64), np.zeros(n, np.uint64)],
+                   [seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF])
+    word = np.stack(words, axis=1)[np.arange(n), (j & np.uint64(3)).astype(np.int64)]
+    if starts is None:
+        return ((word * np.uint64(n)) >> np.uint64(32)).astype(np.int64)
+    starts, perm = np.asarray(starts, dtype=np.int64), np.asarray(perm, dtype=np.int64)
+    seg = np.searchsorted(starts[:-1], np.arange(n), side='right') - 1
+    size = (starts[seg + 1] - starts[seg]).astype(np.uint64)
+    return perm[starts[seg] + ((word * size) >> np.uint64(32)).astype(np.int64)]
+
+
+def table_row_from_block(blk: np.ndarray, num_classes: int, n_bins: int) -> np.ndarray:
+    """One row of the bootstrap's metric table (EVAL_BOOT_* columns) from a result block, through ``metrics_from_block``."""
+    m = metrics_from_block(blk, num_classes, n_bins)
+    row = np.zeros(native.EVAL_BOOT_COLS, dtype=np.float64)
+    for name, col in BOOT_METRICS:
+        row[col] = m[name]
+    for k, col in BOOT_CLASS_METRICS:
+        row[col:col + num_classes] = [c[k] for c in m['per_class']]
+    return row
+
+
+def bootstrap_reference(arrays: Dict, num_classes: int, n_bins: int = 10, num_resamples: int = 1000, seed: int = 0,
+                        stratified: bool = False):
+    """The bootstrap on the host in fp64: ``arrays`` as ``EvalAccumulator.arrays()`` returns them; each replicate is a numpy resample
+    (``bootstrap_indices``) put through ``result_block_from_arrays`` and ``metrics_from_block``.  Returns (table (R, EVAL_BOOT_COLS)
+    float64, blocks (R, 272) int64): the oracle of the kernel, and what ``bootstrap()`` runs for CPU tensors."""
+    y_true, y_pred = np.asarray(arrays['y_true']), np.asarray(arrays['y_pred'])
+    probs, st, sp = np.asarray(arrays['y_probs']), np.asarray(arrays['severity_true']), np.asarray(arrays['severity_pred'])
+    n = len(y_true)
+    perm, starts = stratification(y_true, num_classes) if stratified else (None, None)
+    table = np.zeros((num_resamples, native.EVAL_BOOT_COLS), dtype=np.float64)
+    blocks = np.zeros((num_resamples, native.EVAL_RESULT_WORDS), dtype=np.int64)
+    for r in range(num_resamples):
+        idx = bootstrap_indices(n, r, seed, starts, perm)
+        blocks[r] = result_block_from_arrays(y_true[idx], y_pred[idx], probs[idx], st[idx], sp[idx], num_classes, n_bins)
+        table[r] = table_row_from_block(blocks[r], num_classes, n_bins)
+    return table, blocks
+
+
+def _interval(col: np.ndarray, value: float, confidence: float) -> Dict[str, float]:
+    """value, mean, se (ddof = 1) and the percentile interval of one column of the table; NaN replicates are left out."""
+    ok = col[~np.isnan(col)]
+    if ok.size == 0:
+        return {'value': value, 'mean': float('nan'), 'se': float('nan'), 'lo': float('nan'), 'hi': float('nan')}
+    lo, hi = np.quantile(ok, [(1.0 - confidence) / 2.0, (1.0 + confidence) / 2.0])          # = np.nanquantile(col, ...), linear
+    return {'value': value, 'mean': float(ok.mean()), 'se': float(ok.std(ddof=1)) if ok.size > 1 else float('nan'), 'lo': float(lo),
+            'hi': float(hi)}
+
+
+def mcnemar_exact(b01: int, b10: int) -> float:
+    """McNemar's exact two-sided test on the discordant counts: p = min(1, 2 P[X <= min(b01, b10)]), X ~ Binomial(b01 + b10, 1/2).
+    Exact integers up to 1024 discordant rows, log-gamma beyond."""
+    n, k = int(b01) + int(b10), min(int(b01), int(b10))
+    if n == 0:
+        return 1.0
+    if n <= 1024:
+        return min(1.0, 2 * sum(math.comb(n, i) for i in range(k + 1)) / 2 ** n)
+    i = torch.arange(k + 1, dtype=torch.float64)
+    logs = math.lgamma(n + 1) - torch.lgamma(i + 1) - torch.lgamma(n - i + 1) - n * math.log(2.0)
+    return min(1.0, 2.0 * float(torch.exp(torch.logsumexp(logs, 0))))
+
+
+def _paired(diffs: np.ndarray, a: float, b: float, confidence: float) -> Dict[str, float]:
+    """b - a with the percentile interval of the replicate differences and the two-sided bootstrap p-value
+    min(1, 2 min(#{d <= 0} + 1, #{d >= 0} + 1) / (R + 1)) over the replicates whose difference is a number."""
+    ok = diffs[~np.isnan(diffs)]
+    if ok.size == 0:
+        return {'a': a, 'b': b, 'diff': b - a, 'lo': float('nan'), 'hi': float('nan'), 'p_value': float('nan')}
+    lo, hi = np.quantile(ok, [(1.0 - confidence) / 2.0, (1.0 + confidence) / 2.0])
+    p = min(1.0, 2.0 * min(int((ok <= 0).sum()) + 1, int((ok >= 0).sum()) + 1) / (ok.size + 1))
+    return {'a': a, 'b': b, 'diff': b - a, 'lo': float(lo), 'hi': float(hi), 'p_value': p}
+
+
+def paired_bootstrap(acc_a: 'EvalAccumulator', acc_b: 'EvalAccumulator', num_resamples: int = 1000, seed: int = 0, confidence: float = 0.95,
+                     stratified: bool = False) -> Dict:
+    """Paired bootstrap of two models scored on the same test rows: both accumulators are resampled with the same seed, hence the same
+    rows, and each metric's replicate differences b - a give ``{'a', 'b', 'diff', 'lo', 'hi', 'p_value'}`` (per class under
+    ``'per_class'``).  ``'mcnemar'`` holds McNemar's exact two-sided test on the discordant counts (b01: a right and b wrong, b10 the
+    reverse).  Needs the same device, the same number of rows and the same class labels row for row (checked on the device: the flag
+    travels in the call's one device-to-host copy)."""
+    R = _check_bootstrap_args(num_resamples, seed, confidence)
+    for acc in (acc_a, acc_b):
+        if not isinstance(acc, EvalAccumulator) or acc.n < 1:
+            raise RovitHipError('paired_bootstrap: two EvalAccumulators with recorded rows are needed')
+    if acc_a.n != acc_b.n:
+        raise RovitHipError(f'paired_bootstrap: {acc_a.n} rows against {acc_b.n}: the models must be scored on the same test rows')
+    if (acc_a.num_classes, acc_a.n_bins) != (acc_b.num_classes, acc_b.n_bins) or acc_a.device != acc_b.device:
+        raise RovitHipError('paired_bootstrap: the accumulators differ in classes, calibration bins or device')
+    n, C, W, COLS = acc_a.n, acc_a.num_classes, native.EVAL_RESULT_WORDS, native.EVAL_BOOT_COLS
+    if acc_a.device.type != 'cuda':
+        arr = [acc.arrays() for acc in (acc_a, acc_b)]
+        differ = not np.array_equal(arr[0]['y_true'], arr[1]['y_true'])
+        right = [x['y_pred'] == x['y_true'] for x in arr]
+        b01, b10 = int((right[0] & ~right[1]).sum()), int((~right[0] & right[1]).sum())
+        tables = [None, None] if differ else [bootstrap_reference(x, C, acc_a.n_bins, R, seed, stratified)[0] for x in arr]
+    else:
+        out = torch.empty(2 * W + 2 * R * COLS + 3, dtype=torch.int64, device=acc_a.device)
+        for k, acc in enumerate((acc_a, acc_b)):
+            t0 = 2 * W + k * R * COLS
+            out[k * W:(k + 1) * W].copy_(acc._bootstrap_launch(R, seed, stratified, out[t0:t0 + R * COLS], None))
+        la, lb = acc_a._rec['label'][:n], acc_b._rec['label'][:n]
+        ra, rb = acc_a._rec['pred'][:n] == la, acc_b._rec['pred'][:n] == lb
+        out[-3:] = torch.stack([(la != lb).sum(), (ra & ~rb).sum(), (~ra & rb).sum()])
+        host = out.cpu().numpy()                             # the call's single device-to-host copy
+        for k, acc in enumerate((acc_a, acc_b)):
+            if acc._block is None:
+                acc._block = host[k * W:(k + 1) * W].copy()
+        differ, b01, b10 = bool(host[-3]), int(host[-2]), int(host[-1])
+        tables = [host[2 * W + k * R * COLS:2 * W + (k + 1) * R * COLS].view(np.float64).reshape(R, COLS) for k in range(2)]
+    if differ:
+        raise RovitHipError('paired_bootstrap: the class labels of the two accumulators differ: not the same test rows in the same order')
+    ma, mb = acc_a.compute(), acc_b.compute()
+    d = tables[1] - tables[0]
+    res = {name: _paired(d[:, col], ma[name], mb[name], confidence) for name, col in BOOT_METRICS}
+    res['per_class'] = [{k: _paired(d[:, col + c], ma['per_class'][c][k], mb['per_class'][c][k], confidence) for k, col in BOOT_CLASS_METRICS}
+                        for c in range(C)]
+    res['mcnemar'] = {'b01': b01, 'b10': b10, 'p_value': mcnemar_exact(b01, b10)}
+    res.update(num_resamples=R, seed=seed, confidence=confidence, stratified=bool(stratified))
+    return res
 
 
 def validate(model: torch.nn.Module, loader, loss_fn, n_bins: int = 10) -> Dict[str, float]:

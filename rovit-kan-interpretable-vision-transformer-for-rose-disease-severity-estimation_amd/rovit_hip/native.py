@@ -117,6 +117,8 @@ SIGNATURES = {
     'rovit_eval_partials_doubles': (_sz, [_i]),
     'rovit_eval_accumulate': (_i, [_vp, _vp]),
     'rovit_eval_finalize': (_i, [_vp, _vp]),
+    'rovit_eval_bootstrap_workspace_bytes': (_sz, [_i, _i]),
+    'rovit_eval_bootstrap': (_i, [_vp, _vp]),
     'rovit_kan_stats_words': (_sz, [_i, _i, _i]),
     'rovit_kan_stats_partials_doubles': (_sz, [_i, _i, _i, _i]),
     'rovit_kan_edge_stats': (_i, [_vp, _vp]),
@@ -167,6 +169,21 @@ class EvalFinal(C.Structure):
 EVAL_CONFUSION, EVAL_BIN_COUNT, EVAL_BIN_CORRECT, EVAL_RANK, EVAL_NONFINITE, EVAL_BAD_LABELS, EVAL_N = 0, 64, 128, 192, 195, 197, 198
 EVAL_BIN_CONF, EVAL_BRIER, EVAL_ABS_ERR, EVAL_LOSS, EVAL_RESULT_WORDS = 200, 264, 265, 266, 272
 EVAL_MAX_CLASSES, EVAL_MAX_BINS, EVAL_MAX_ROWS = 8, 64, 1 << 20
+
+
+class EvalBoot(C.Structure):
+    """``rovit_eval_boot`` of include/rovit_hip.h, field for field."""
+    _fields_ = [('n', _i), ('num_classes', _i), ('n_bins', _i), ('num_resamples', _i), ('max_workgroups', _i), ('seed', C.c_ulonglong),
+                ('probs', _vp), ('pred', _vp), ('label', _vp), ('sev_pred', _vp), ('sev_true', _vp), ('bin_edges', _vp),
+                ('rank_counts', _vp), ('perm', _vp), ('starts', _vp), ('workspace', _vp), ('workspace_bytes', _sz), ('table', _vp),
+                ('blocks', _vp)]
+
+
+# rovit_eval_bootstrap: the Philox stream word, the row threshold between H in LDS and H in the workspace, the workspace path's grid
+# cap, the resample limit and the metric table's columns (the ROVIT_EVAL_BOOT_* constants of include/rovit_hip.h)
+EVAL_BOOT_STREAM, EVAL_BOOT_LDS_ROWS, EVAL_BOOT_WORKSPACE_GRID, EVAL_BOOT_MAX_RESAMPLES = 0x426F6F74, 16384, 128, 65536
+EVAL_BOOT_ACCURACY, EVAL_BOOT_MACRO_F1, EVAL_BOOT_WEIGHTED_F1, EVAL_BOOT_MAE, EVAL_BOOT_RHO, EVAL_BOOT_BRIER, EVAL_BOOT_ECE = range(7)
+EVAL_BOOT_PRECISION, EVAL_BOOT_RECALL, EVAL_BOOT_F1, EVAL_BOOT_COLS = 7, 15, 23, 32
 
 
 class TrainLoss(C.Structure):
