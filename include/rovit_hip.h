@@ -692,6 +692,60 @@ size_t rovit_eval_bootstrap_workspace_bytes(int n, int num_resamples);
 int rovit_eval_bootstrap(const rovit_eval_boot* p, rovit_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Selective prediction on that record (selective.hip): does the model know which rows it gets wrong?  The reference collects
+ * all_uncertainties (evaluation/evaluator.py:35,64-65) and drops them; rovit_eval_selective is the first reader of the `uncertainty`
+ * column.  It scores S score columns u (higher = less certain) against K risk columns l >= 0 of the same n rows, all fp32:
+ *   scores  ROVIT_EVAL_SEL_CONFIDENCE 1 - max_c p (one IEEE subtraction)   _ENTROPY -sum_c p logf(p), a term of 0 at p == 0
+ *           _SIGMA the recorded uncertainty   _SCORE_COLUMN score_column[s], n floats of the caller's
+ *   risks   ROVIT_EVAL_SEL_ERROR 1.0f where pred != label   _ABS_ERR |sev_true - sev_pred| in fp32   _RISK_COLUMN risk_column[k]
+ * Order: rows by ascending u; rows with equal u (==, so -0 equals +0) form a tie group [g, g + m) of sorted slots, and every row of a
+ *   group counts with the group's mean risk (the expectation over random tie-breaking: the result cannot depend on the row order).
+ *   With Pref[k] the fp64 sum of the first k sorted risks (ties in row order), the selective risk at k kept rows, g < k <= g + m, is
+ *   r_k = (Pref[g] + (k - g) (Pref[g + m] - Pref[g]) / m) / k.
+ * Ranks are counted, not sorted, every one of the S + K columns once: less_i = #{x_j < x_i}, eq_i = #{x_j == x_i},
+ *   before_i = #{j < i : x_j == x_i}; row i sits in sorted slot less_i + before_i and its group is [less_i, less_i + eq_i).
+ * result, ROVIT_EVAL_SEL_WORDS(S, K, P) 8-byte words with P = num_coverages and k_p = ceil(p n / P) in integers, p = 1..P:
+ *   int64  [ROVIT_EVAL_SEL_NONFINITE_KEYS] non-finite score values   [_NONFINITE_RISKS], [_NEGATIVE_RISKS] of the risk values
+ *          [_BAD_LABELS] recorded labels of -1   [_N]   (words up to ROVIT_EVAL_SEL_HEADER are 0)
+ *   double per risk k at ROVIT_EVAL_SEL_HEADER + k (2 + P): mean = r_n, oracle_aurc (the risk ordered by itself), oracle_curve[P]
+ *          per (score s, risk k) behind the risks at (s K + k)(1 + P): aurc = (1/n) sum_k r_k, curve[p] = r_{k_p}
+ *          per score s behind the pairs at s P: thresholds[p] = the score value in sorted slot k_p - 1, widened
+ * keys_out (S, n) and risks_out (K, n), when not NULL, receive the fp32 columns that were ranked.
+ * Integers are added with integer atomics; the prefix sums and sum_k r_k run over 256-slot chunks in a fixed tree inside and across
+ * chunks, and no floating-point atomic is used: the block is bit-identical from run to run, for every split of the rows into batches
+ * and for every grid (max_workgroups > 0 caps the grid of every kernel; a workgroup then serves several work items in turn).
+ * The whole block is zeroed first.  workspace: rovit_eval_selective_workspace_bytes(n, S, K) bytes, 16-byte aligned (0 for sizes
+ * outside the limits).  With a non-finite key the order is undefined; the counters say so and the other words are then meaningless.
+ * Limits: 1 <= n <= ROVIT_EVAL_MAX_ROWS, 1 <= S <= 8, 1 <= K <= 4, 1 <= P <= 256.  A bad descriptor is refused before any launch.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define ROVIT_EVAL_SEL_MAX_SCORES 8
+#define ROVIT_EVAL_SEL_MAX_RISKS 4
+#define ROVIT_EVAL_SEL_MAX_COVERAGES 256
+enum { ROVIT_EVAL_SEL_CONFIDENCE = 0, ROVIT_EVAL_SEL_ENTROPY = 1, ROVIT_EVAL_SEL_SIGMA = 2, ROVIT_EVAL_SEL_SCORE_COLUMN = 3 };
+enum { ROVIT_EVAL_SEL_ERROR = 0, ROVIT_EVAL_SEL_ABS_ERR = 1, ROVIT_EVAL_SEL_RISK_COLUMN = 2 };
+enum {
+  ROVIT_EVAL_SEL_NONFINITE_KEYS = 0, ROVIT_EVAL_SEL_NONFINITE_RISKS = 1, ROVIT_EVAL_SEL_NEGATIVE_RISKS = 2, ROVIT_EVAL_SEL_BAD_LABELS = 3,
+  ROVIT_EVAL_SEL_N = 4, ROVIT_EVAL_SEL_HEADER = 8
+};
+#define ROVIT_EVAL_SEL_WORDS(S, K, P) \
+  ((size_t)ROVIT_EVAL_SEL_HEADER + (size_t)(K) * (2 + (P)) + (size_t)(S) * (K) * (1 + (P)) + (size_t)(S) * (P))
+typedef struct rovit_eval_sel {
+  int n, num_classes, num_scores, num_risks, num_coverages, max_workgroups;
+  int score_kind[ROVIT_EVAL_SEL_MAX_SCORES];
+  int risk_kind[ROVIT_EVAL_SEL_MAX_RISKS];
+  const float* score_column[ROVIT_EVAL_SEL_MAX_SCORES];   /* (n) each; read for ROVIT_EVAL_SEL_SCORE_COLUMN only */
+  const float* risk_column[ROVIT_EVAL_SEL_MAX_RISKS];     /* (n) each; read for ROVIT_EVAL_SEL_RISK_COLUMN only */
+  const float* probs; const int* pred; const int* label; const float* sev_pred; const float* sev_true; const float* uncertainty;
+  void* workspace;
+  size_t workspace_bytes;
+  void* result;                      /* ROVIT_EVAL_SEL_WORDS(S, K, P) 8-byte words */
+  float* keys_out;                   /* (S, n) or NULL */
+  float* risks_out;                  /* (K, n) or NULL */
+} rovit_eval_sel;
+size_t rovit_eval_selective_workspace_bytes(int n, int num_scores, int num_risks);
+int rovit_eval_selective(const rovit_eval_sel* p, rovit_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Per-edge activation statistics of one KAN layer over a data set (kan_stats.hip): what the edge functions of models/kan.py:70-95 do
  * ON DATA, where KANLayer.plot_activation (:97-114) and explainability/kan_viz.py only draw a few of them over [-1, 1].
  * For the layer's n input rows x (n, in_f), with s_ij(v) = sum_k spline_w[i,j,k] B_k(tanh v), phi_ij(v) = lin_w[j,i] v + s_ij(v) and

@@ -3,14 +3,16 @@ launch per batch records the predictions on the device, one launch per epoch red
 block back.  Same constructor, same returned dict, same printed table, same ``evaluation_results.txt``.  Figures are not drawn
 (SURVEY.md section 2); ``evaluate(return_arrays=True)`` hands back the arrays the reference's plots are made from.  A last batch of one
 sample works (the reference's ``squeeze()`` + ``np.concatenate`` raises there).  ``evaluate(bootstrap=R)`` adds percentile bootstrap
-intervals (``EvalAccumulator.bootstrap``) to the dict, the table and the file; with the default 0 all three are what they were."""
+intervals (``EvalAccumulator.bootstrap``) to the dict, the table and the file; with the default 0 all three are what they were.
+``evaluate(selective=True)`` adds the selective-prediction score card (``EvalAccumulator.selective``: AURC, E-AURC and the risk left at
+80 % and 90 % coverage for every uncertainty score) in the same way."""
 from pathlib import Path
 from typing import Dict
 
 import torch
 
 from evaluation.metrics import count_params, fps
-from rovit_hip.evaluation import EvalAccumulator, class_table
+from rovit_hip.evaluation import EvalAccumulator, RovitHipError, class_table
 
 RULE = '=' * 60
 
@@ -25,19 +27,41 @@ class Evaluator:
         self.model.eval()
         self.accumulator = None
 
-    def collect(self) -> EvalAccumulator:
-        """The collection loop alone: one forward and one record launch per batch, nothing copied to the host."""
+    MC_COLUMNS = ('predictive_entropy_mc', 'mutual_information', 'epistemic_var', 'uncertainty_std')
+
+    def collect(self, selective: bool = False, mc_samples: int = 0, mc_seed: int = 0) -> EvalAccumulator:
+        """The collection loop alone: one forward and one record launch per batch, nothing copied to the host.  ``selective`` also
+        records the uncertainty head's ``mu`` as an extra column when the model returns one; ``mc_samples = T > 0`` adds the MC-dropout
+        columns of ``model.predict_mc(images, num_samples=T, seed=mc_seed, offset=batch index)``, a SECOND backbone pass per batch."""
+        if mc_samples and not selective:
+            raise RovitHipError('Evaluator: mc_samples records columns for the selective score card; pass selective=True with it')
         acc = self.accumulator = EvalAccumulator(len(self.config.data.class_names))
         self.model.eval()
         with torch.no_grad():
-            for images, class_labels, severity_labels in self.test_loader:
-                acc.update(self.model(images.to(self.device)), class_labels, severity_labels)
+            for index, (images, class_labels, severity_labels) in enumerate(self.test_loader):
+                images = images.to(self.device)
+                outputs = self.model(images)
+                extra = {}
+                if selective and outputs.get('mu') is not None:
+                    extra['mu'] = outputs['mu']
+                if selective and mc_samples:
+                    mc = self.model.predict_mc(images, num_samples=mc_samples, seed=mc_seed, offset=index)
+                    extra['predictive_entropy_mc'], extra['mutual_information'] = mc['predictive_entropy'], mc['mutual_information']
+                    if 'epistemic_var' in mc:                 # from curriculum stage 3
+                        extra['epistemic_var'], extra['uncertainty_std'] = mc['epistemic_var'], mc['uncertainty_std']
+                acc.update(outputs, class_labels, severity_labels, extra=extra or None)
         return acc
 
-    def evaluate(self, return_arrays: bool = False, bootstrap: int = 0, bootstrap_seed: int = 0):
+    def evaluate(self, return_arrays: bool = False, bootstrap: int = 0, bootstrap_seed: int = 0, selective: bool = False,
+                 mc_samples: int = 0, mc_seed: int = 0):
+        """``selective=True`` adds ``metrics['selective']`` (``EvalAccumulator.selective`` with 20 coverages: the built-in scores, and
+        with ``mc_samples = T > 0`` the MC-dropout scores predictive_entropy_mc and mutual_information, from curriculum stage 3 also
+        epistemic_var and uncertainty_std) and a "Selective prediction" section in the table and the file.  The MC columns cost a
+        second backbone pass per batch, and they depend on the batch split (the dropout masks are drawn per batch position); the
+        kernel's determinism holds for given columns."""
         print(f'\n{RULE}\nRunning Evaluation on Test Set\n{RULE}\n')
         names = list(self.config.data.class_names)
-        acc = self.collect()
+        acc = self.collect(selective, mc_samples, mc_seed)
         ci = acc.bootstrap(bootstrap, seed=bootstrap_seed) if bootstrap else None          # brings the point block along in its one copy
         m = acc.compute()                                   # the loop's one synchronisation
         metrics = {k: m[k] for k in ('accuracy', 'macro_f1', 'weighted_f1', 'mae', 'spearman_rho', 'spearman', 'brier_score', 'ece')}
@@ -48,6 +72,10 @@ class Evaluator:
         if ci is not None:
             ci['per_class'] = class_table(ci['per_class'], names)
             metrics['confidence_intervals'] = ci
+        if selective:
+            have = acc._extra_names or ()
+            scores = ['confidence', 'entropy'] + (['sigma'] if acc._has_uncertainty else []) + [c for c in self.MC_COLUMNS if c in have]
+            metrics['selective'] = acc.selective(scores=scores, risks=['error', 'abs_err'] + (['mu_abs_err'] if 'mu' in have else []))
         self._print_results(metrics)
         self._save_results(metrics)
         return (metrics, acc.arrays()) if return_arrays else metrics
@@ -66,8 +94,27 @@ class Evaluator:
                                         f"± {ci[k]['se']:.4f} [{ci[k]['lo']:.4f}, {ci[k]['hi']:.4f}]") for k in keys]
         return [f'{label:<16}{value:<12}{extra}'.rstrip() for (label, value), extra in zip(rows, column)]
 
+    @staticmethod
+    def _selective_lines(metrics: Dict):
+        """One line per score and risk: AURC, E-AURC, normalized E-AURC and the risk left at 80 % and 90 % coverage (the curve points
+        whose actual coverage k_p / n is the first at or above them)."""
+        sel = metrics.get('selective')
+        if sel is None:
+            return []
+        cov = sel['coverages']
+        at = [min(int((cov < c - 1e-12).sum()), len(cov) - 1) for c in (0.8, 0.9)]
+        lines = ['Selective prediction:', f"{'Score':<24}{'Risk':<12}{'AURC':>10}{'E-AURC':>10}{'Norm.':>8}{'Risk@80%':>10}{'Risk@90%':>10}", '-' * 84]
+        for score, entry in sel['scores'].items():
+            for risk in sel['risks']:
+                e = entry[risk]
+                lines.append(f"{score:<24}{risk:<12}{e['aurc']:>10.4f}{e['e_aurc']:>10.4f}{e['normalized']:>8.3f}"
+                             f"{e['curve'][at[0]]:>10.4f}{e['curve'][at[1]]:>10.4f}")
+        return lines + ['']
+
     def _print_results(self, metrics: Dict) -> None:
         print('\n'.join(['', RULE, 'Evaluation Results', RULE] + self._summary(metrics, 'Spearman rho:') + [RULE, '']))
+        if 'selective' in metrics:
+            print('\n'.join(self._selective_lines(metrics)))
         print('Per-Class Metrics:')
         print(f"{'Class':<20} {'Precision':<12} {'Recall':<12} {'F1-Score':<12} {'Support':<10}")
         print('-' * 70)
@@ -85,6 +132,7 @@ class Evaluator:
         for name, c in metrics['per_class'].items():
             lines += [f'{name}:', f"  Precision: {c['precision']:.2f}%", f"  Recall:    {c['recall']:.2f}%", f"  F1-Score:  {c['f1']:.2f}%",
                       f"  Support:   {c['support']}", '']
+        lines += self._selective_lines(metrics)
         path = results_dir / 'evaluation_results.txt'
         path.write_text('\n'.join(lines) + '\n', encoding='utf-8')
         print(f'Results saved to {path}')

@@ -179,11 +179,13 @@ class RoViTKAN(nn.Module):
                 pred['kan_severity'] = out['kan_severity']
             return pred
 
-    def predict_mc(self, x: torch.Tensor, num_samples: int = 30, seed=None, return_samples: bool = False) -> Dict[str, torch.Tensor]:
+    def predict_mc(self, x: torch.Tensor, num_samples: int = 30, seed=None, return_samples: bool = False, *,
+                   offset: int = 0) -> Dict[str, torch.Tensor]:
         """Extension (not in the reference): Monte-Carlo dropout over the heads -- one backbone forward and one launch for every
-        sample (rovit_hip.mc_dropout.mc_dropout_predict).  Unlike predict(), leaves every module's training flag as it found it."""
+        sample (rovit_hip.mc_dropout.mc_dropout_predict).  Unlike predict(), leaves every module's training flag as it found it.
+        ``offset`` (with an explicit ``seed``) moves the Philox counter, so the batches of one pass draw different masks."""
         from rovit_hip import mc_dropout
-        return mc_dropout.mc_dropout_predict(self, x, num_samples, seed, return_samples)
+        return mc_dropout.mc_dropout_predict(self, x, num_samples, seed, return_samples, offset=offset)
 
     def _head_dropouts(self):
         return (self.classification_head.dropout, self.ordinal_head.dropout, self.uncertainty_head.dropout)

@@ -13,6 +13,9 @@ synchronisation.  Everything reported is derived from that block on the host in 
 (``rovit_eval_bootstrap``: every resample's score card on the device, one copy for the whole call); ``bootstrap_reference`` is their
 numpy restatement.
 
+``EvalAccumulator.selective`` scores the uncertainty estimates (``rovit_eval_selective``): risk-coverage curves, AURC, E-AURC and the
+accept thresholds of every (score, risk) pair, one copy for the whole call; ``selective_reference`` states the definitions in numpy fp64.
+
 On CPU tensors the same class runs the plain torch / numpy fp64 restatement below (``result_block_from_arrays``), as
 ``JointLoss._forward_tensor_ops`` does: the host logic is testable without a GPU, and ``evaluation.metrics`` is built on it.
 """
@@ -203,6 +206,8 @@ class EvalAccumulator:
         self._block: Optional[np.ndarray] = None
         self._block_dev: Optional[torch.Tensor] = None         # the finalise's block and rank counts on the device: bootstrap() reads them
         self._rank_counts: Optional[torch.Tensor] = None
+        self._extra_names: Optional[tuple] = None              # fixed by the first update that passes ``extra``
+        self._extra: Dict[str, torch.Tensor] = {}              # device path: growable fp32 columns beside the record
 
     # -- device record arrays --
     _FIELDS = (('probs', torch.float32), ('pred', torch.int32), ('label', torch.int32), ('sev_pred', torch.float32),
@@ -223,6 +228,9 @@ class EvalAccumulator:
         for k, t in self._rec.items():
             new[k][:self.n].copy_(t[:self.n])             # device-to-device, stream-ordered: no synchronisation
         self._rec = new
+        for k, t in self._extra.items():
+            self._extra[k] = torch.empty(new_cap, dtype=torch.float32, device=self.device)
+            self._extra[k][:self.n].copy_(t[:self.n])
 
     def _reserve_losses(self, rows: int) -> None:
         cap = self._loss_table.shape[0] if self._loss_table is not None else 0
@@ -234,9 +242,11 @@ class EvalAccumulator:
         self._loss_table = new
 
     def update(self, outputs: Dict[str, Optional[torch.Tensor]], class_labels: torch.Tensor, severity_labels: torch.Tensor,
-               losses=None) -> None:
+               losses=None, extra: Optional[Dict[str, torch.Tensor]] = None) -> None:
         """Record one batch: the model's output dict, the class labels and the severity labels (host or device tensors), and
-        optionally the dict ``JointLoss`` returned (or a 5-vector [cls, ord, unc, kan, total])."""
+        optionally the dict ``JointLoss`` returned (or a 5-vector [cls, ord, unc, kan, total]).  ``extra``: named per-row (B,) or (B, 1)
+        tensors (``{'mu': outputs['mu'], 'mutual_information': mc['mutual_information']}``) kept as fp32 columns beside the record for
+        ``selective``; the first ``update`` that passes one fixes the set of names, and it must be the accumulator's first batch."""
         logits = outputs['cls_logits'].detach()
         if logits.dim() != 2 or logits.shape[1] != self.num_classes or logits.shape[0] < 1:
             raise RovitHipError(f'EvalAccumulator.update: cls_logits must be (B >= 1, {self.num_classes}), got {tuple(logits.shape)}')
@@ -247,6 +257,10 @@ class EvalAccumulator:
         for name, t in (('kan_severity', kan), ('log_var', lv), ('class_labels', class_labels), ('severity_labels', severity_labels)):
             if t is not None and t.numel() != B:
                 raise RovitHipError(f'EvalAccumulator.update: {name} has {t.numel()} values for a batch of {B}')
+        if extra is not None:
+            extra = self._check_extra(extra, B)
+        elif self._extra_names is not None:
+            raise RovitHipError(f'EvalAccumulator.update: earlier batches carried the extra columns {sorted(self._extra_names)}, this one none')
         if self.device is None:
             self.device = logits.device
         elif logits.device != self.device:
@@ -257,7 +271,10 @@ class EvalAccumulator:
         if not logits.is_cuda:
             self._cpu.append({'logits': logits.float(), 'kan': None if kan is None else kan.detach().float().reshape(-1),
                               'lv': None if lv is None else lv.detach().float().reshape(-1),
-                              'label': class_labels.detach().long().reshape(-1).cpu(), 'sev': severity_labels.detach().reshape(-1).cpu()})
+                              'label': class_labels.detach().long().reshape(-1).cpu(), 'sev': severity_labels.detach().reshape(-1).cpu(),
+                              'extra': {} if extra is None else {k: t.detach().float().reshape(-1).cpu() for k, t in extra.items()}})
+            if extra is not None:
+                self._extra_names = tuple(extra)
             if losses is not None:
                 self._cpu_losses.append(_loss_vector(losses).cpu())
                 self.n_loss_rows += 1
@@ -285,9 +302,30 @@ class EvalAccumulator:
             setattr(d, k, native.ptr(self._rec[k]))
         d.loss_table = native.ptr(self._loss_table)
         native.call('rovit_eval_accumulate', ctypes.byref(d), native.stream_ptr())
+        if extra is not None:
+            self._extra_names = tuple(extra)
+            for k, t in extra.items():
+                if k not in self._extra:
+                    self._extra[k] = torch.empty(self._rec['pred'].shape[0], dtype=torch.float32, device=dev)
+                self._extra[k][self.n:self.n + B].copy_(t.detach().reshape(-1), non_blocking=True)          # stream-ordered, converts to fp32
         self.n += B
         if lvec is not None:
             self.n_loss_rows += 1
+
+    def _check_extra(self, extra, B: int) -> Dict[str, torch.Tensor]:
+        if not isinstance(extra, dict) or not extra:
+            raise RovitHipError('EvalAccumulator.update: extra must be a non-empty dict of per-row tensors')
+        for k, t in extra.items():
+            if not isinstance(k, str) or k in SELECTIVE_BUILTIN:
+                raise RovitHipError(f'EvalAccumulator.update: {k!r} cannot name an extra column (a string other than {sorted(SELECTIVE_BUILTIN)})')
+            if not isinstance(t, torch.Tensor) or t.numel() != B or t.dim() > 2:
+                raise RovitHipError(f'EvalAccumulator.update: extra column {k!r} must be a (B,) or (B, 1) tensor for a batch of {B}')
+        if self._extra_names is None and self.n > 0:
+            raise RovitHipError(f'EvalAccumulator.update: {self.n} rows were recorded without extra columns; pass them from the first batch on')
+        if self._extra_names is not None and set(extra) != set(self._extra_names):
+            raise RovitHipError(f'EvalAccumulator.update: extra columns {sorted(extra)} differ from the {sorted(self._extra_names)} of the '
+                                'first batch')
+        return extra
 
     # -- results --
     def _cpu_arrays(self):
@@ -355,6 +393,89 @@ class EvalAccumulator:
                 'severity_true': a['sev_true'], 'severity_pred': a['sev_pred'],
                 'uncertainty': a['uncertainty'] if self._has_uncertainty else None}
 
+    # -- selective prediction --
+    def _selective_names(self, scores, risks, coverages):
+        extras = self._extra_names or ()
+        if scores is None:
+            scores = ['confidence', 'entropy'] + (['sigma'] if self._has_uncertainty else [])
+        if risks is None:
+            risks = ['error', 'abs_err']
+        if isinstance(scores, str) or isinstance(risks, str):
+            raise RovitHipError('selective: scores and risks are sequences of names')
+        scores, risks = list(scores), list(risks)
+        if not (isinstance(coverages, int) and not isinstance(coverages, bool) and 1 <= coverages <= native.EVAL_SEL_MAX_COVERAGES):
+            raise RovitHipError(f'selective: coverages must be an int in 1..{native.EVAL_SEL_MAX_COVERAGES}, got {coverages!r}')
+        for what, names, limit, builtin in (('score', scores, native.EVAL_SEL_MAX_SCORES, SELECTIVE_SCORES),
+                                            ('risk', risks, native.EVAL_SEL_MAX_RISKS, tuple(SELECTIVE_RISKS) + ('mu_abs_err',))):
+            if not 1 <= len(names) <= limit or len(set(names)) != len(names):
+                raise RovitHipError(f'selective: 1..{limit} distinct {what} names are needed, got {names!r}')
+            for name in names:
+                if name not in builtin and name not in extras:
+                    raise RovitHipError(f'selective: unknown {what} {name!r} (known: {sorted(builtin)} and the extra columns {sorted(extras)})')
+        if 'sigma' in scores and not self._has_uncertainty:
+            raise RovitHipError("selective: the score 'sigma' needs batches that carried mu and log_var (no uncertainty head was recorded)")
+        if 'mu_abs_err' in risks and 'mu' not in extras:
+            raise RovitHipError("selective: the risk 'mu_abs_err' needs the extra column 'mu' (update(..., extra={'mu': outputs['mu']}))")
+        return scores, risks
+
+    def selective(self, scores: Optional[Sequence[str]] = None, risks: Optional[Sequence[str]] = None, coverages: int = 20,
+                  return_keys: bool = False, _max_workgroups: int = 0) -> Dict:
+        """Selective-prediction score card: does each uncertainty score know which rows the model gets wrong?
+
+        ``scores`` (higher = less certain): ``'confidence'`` 1 - max p, ``'entropy'`` of the recorded probabilities, ``'sigma'`` the
+        recorded exp(0.5 log_var), or the name of an ``extra`` column; default confidence and entropy, plus sigma when a batch carried mu
+        and log_var.  ``risks`` (>= 0): ``'error'`` 1 where the prediction is wrong, ``'abs_err'`` |sev_true - sev_pred|, ``'mu_abs_err'``
+        |sev_true - mu| (needs the extra column ``'mu'``), or an extra column; default error and abs_err.  The definitions are those
+        of ``selective_reference``.  Returns ``{'n', 'coverages' (the actual k_p / n), 'risks': {risk: {'mean', 'oracle_aurc',
+        'oracle_curve'}}, 'scores': {score: {'thresholds', risk: {'aurc', 'e_aurc', 'normalized', 'curve'}}}}``; ``thresholds[p]`` is the
+        score value up to which rows are accepted to keep the fraction ``coverages[p]``.  ``return_keys`` adds ``'keys'`` (S, n) and
+        ``'risk_values'`` (K, n), the fp32 columns that were ranked, and ``'block'``, the result block as int64 words.  On the device the call makes ONE device-to-host copy, and non-finite
+        scores, non-finite or negative risks and class labels outside [0, C) raise after it."""
+        if self.n < 1:
+            raise RovitHipError('EvalAccumulator: nothing recorded yet')
+        scores, risks = self._selective_names(scores, risks, coverages)
+        S, K, P, n = len(scores), len(risks), coverages, self.n
+        if self.device.type != 'cuda':
+            extras = {k: torch.cat([b['extra'][k] for b in self._cpu]).numpy() for k in (self._extra_names or ())}
+            keys, values = selective_columns(self._cpu_arrays(), extras, scores, risks)
+            block = selective_block(keys, values, P, bad_labels=int((self._cpu_arrays()['label'] < 0).sum()))
+        else:
+            off = native.eval_selective_offsets(S, K, P)
+            W = off['words']
+            out = torch.empty(W + ((S + K) * n + 1) // 2 * int(bool(return_keys)), dtype=torch.int64, device=self.device)
+            ws_bytes = native.load().rovit_eval_selective_workspace_bytes(n, S, K)
+            workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
+            d = native.EvalSel()
+            d.n, d.num_classes, d.num_scores, d.num_risks, d.num_coverages, d.max_workgroups = n, self.num_classes, S, K, P, _max_workgroups
+            keep = []                                            # columns made for this call stay alive until it is enqueued
+            for i, name in enumerate(scores):
+                d.score_kind[i] = SELECTIVE_SCORES.get(name, native.EVAL_SEL_SCORE_COLUMN)
+                if name not in SELECTIVE_SCORES:
+                    d.score_column[i] = native.ptr(self._extra[name])
+            for i, name in enumerate(risks):
+                d.risk_kind[i] = SELECTIVE_RISKS.get(name, native.EVAL_SEL_RISK_COLUMN)
+                if name == 'mu_abs_err':
+                    keep.append((self._rec['sev_true'][:n] - self._extra['mu'][:n]).abs())
+                    d.risk_column[i] = native.ptr(keep[-1])
+                elif name not in SELECTIVE_RISKS:
+                    d.risk_column[i] = native.ptr(self._extra[name])
+            for k, _ in self._FIELDS:
+                setattr(d, k, native.ptr(self._rec[k]))
+            d.workspace, d.workspace_bytes, d.result = native.ptr(workspace), ws_bytes, native.ptr(out)
+            if return_keys:
+                f = out[W:].view(torch.float32)
+                d.keys_out, d.risks_out = native.ptr(f), native.ptr(f[S * n:])
+            native.call('rovit_eval_selective', ctypes.byref(d), native.stream_ptr())
+            host = out.cpu().numpy()                             # the call's single device-to-host copy
+            block = host[:W]
+            if return_keys:
+                f = host[W:].view(np.float32)
+                keys, values = f[:S * n].reshape(S, n), f[S * n:(S + K) * n].reshape(K, n)
+        res = selective_from_block(block, scores, risks, P, self.num_classes)
+        if return_keys:
+            res['keys'], res['risk_values'], res['block'] = keys, values, block
+        return res
+
     # -- bootstrap --
     def _bootstrap_launch(self, num_resamples: int, seed: int, stratified: bool, table: torch.Tensor, blocks: Optional[torch.Tensor],
                           max_workgroups: int = 0) -> torch.Tensor:
@@ -421,6 +542,136 @@ class EvalAccumulator:
         if return_blocks:
             res['blocks'] = blocks
         return res
+
+# ---- selective prediction: restatement and summaries ---------------------------------------------------------------------------
+
+SELECTIVE_SCORES = {'confidence': native.EVAL_SEL_CONFIDENCE, 'entropy': native.EVAL_SEL_ENTROPY, 'sigma': native.EVAL_SEL_SIGMA}
+SELECTIVE_RISKS = {'error': native.EVAL_SEL_ERROR, 'abs_err': native.EVAL_SEL_ABS_ERR}
+SELECTIVE_BUILTIN = frozenset(SELECTIVE_SCORES) | frozenset(SELECTIVE_RISKS) | {'mu_abs_err'}
+
+
+def coverage_counts(n: int, coverages: int) -> np.ndarray:
+    """k_p = ceil(p n / P) for p = 1..P, in integers: the rows kept at curve point p."""
+    p = np.arange(1, coverages + 1, dtype=np.int64)
+    return (p * n + coverages - 1) // coverages
+
+
+def selective_risks(u, l) -> np.ndarray:
+    """r_1..r_n of one score column ``u`` (fp32) and one risk column ``l``: the rows by ascending u (stable, so ties keep the row order),
+    Pref the fp64 running sum of the sorted risks, and for a tie group in slots [g, g + m) and g < k <= g + m
+    r_k = (Pref[g] + (k - g) (Pref[g + m] - Pref[g]) / m) / k: every row of a group counts with the group's mean risk."""
+    u = np.asarray(u, dtype=np.float32).reshape(-1)
+    l = np.asarray(l, dtype=np.float64).reshape(-1)
+    n = u.shape[0]
+    order = np.argsort(u, kind='stable')
+    us = u[order]
+    pref = np.concatenate([[0.0], np.cumsum(l[order])])
+    g = np.searchsorted(us, us, side='left')
+    m = np.searchsorted(us, us, side='right') - g
+    k = np.arange(1, n + 1)
+    return (pref[g] + (k - g) * (pref[g + m] - pref[g]) / m) / k
+
+
+def selective_reference(keys, risks, coverages: int = 20) -> Dict[str, np.ndarray]:
+    """The definitions of the selective-prediction score card in numpy fp64: ``keys`` (S, n) fp32 score columns (higher = less
+    certain), ``risks`` (K, n) fp32 risk columns >= 0.  Returns ``n``, ``k`` (k_p), ``coverages`` (k_p / n), per risk ``mean`` (K,) = r_n,
+    ``oracle_aurc`` (K,) and ``oracle_curve`` (K, P) (the risk ordered by itself), per pair ``aurc`` (S, K) = (1/n) sum_k r_k and
+    ``curve`` (S, K, P) = r_{k_p}, and per score ``thresholds`` (S, P): the score in sorted slot k_p - 1, widened.  The oracle of the
+    kernel, and what ``selective()`` runs for CPU tensors."""
+    keys = np.atleast_2d(np.asarray(keys, dtype=np.float32))
+    risks = np.atleast_2d(np.asarray(risks, dtype=np.float32))
+    (S, n), K, P = keys.shape, risks.shape[0], int(coverages)
+    if risks.shape[1] != n or n < 1 or P < 1:
+        raise RovitHipError(f'selective_reference: keys {keys.shape} and risks {risks.shape} must share n >= 1 rows, coverages >= 1')
+    kp = coverage_counts(n, P)
+    out = {'n': n, 'k': kp, 'coverages': kp / n, 'mean': np.zeros(K), 'oracle_aurc': np.zeros(K), 'oracle_curve': np.zeros((K, P)),
+           'aurc': np.zeros((S, K)), 'curve': np.zeros((S, K, P)), 'thresholds': np.zeros((S, P))}
+    for k in range(K):
+        r = selective_risks(risks[k], risks[k])
+        out['mean'][k], out['oracle_aurc'][k], out['oracle_curve'][k] = r[n - 1], r.sum() / n, r[kp - 1]
+        for s in range(S):
+            r = selective_risks(keys[s], risks[k])
+            out['aurc'][s, k], out['curve'][s, k] = r.sum() / n, r[kp - 1]
+    for s in range(S):
+        out['thresholds'][s] = np.sort(keys[s], kind='stable')[kp - 1].astype(np.float64)
+    return out
+
+
+def selective_block(keys, risks, coverages: int = 20, bad_labels: int = 0) -> np.ndarray:
+    """The result block of ``rovit_eval_selective`` (include/rovit_hip.h) from the ranked columns, on the host: int64 words with the
+    fp64 section stored bit for bit, through ``selective_reference`` (skipped when a counter makes the order meaningless)."""
+    keys = np.atleast_2d(np.asarray(keys, dtype=np.float32))
+    risks = np.atleast_2d(np.asarray(risks, dtype=np.float32))
+    (S, n), K, P = keys.shape, risks.shape[0], int(coverages)
+    off = native.eval_selective_offsets(S, K, P)
+    blk = np.zeros(off['words'], dtype=np.int64)
+    f = blk.view(np.float64)
+    blk[native.EVAL_SEL_NONFINITE_KEYS] = int((~np.isfinite(keys)).sum())
+    blk[native.EVAL_SEL_NONFINITE_RISKS] = int((~np.isfinite(risks)).sum())
+    blk[native.EVAL_SEL_NEGATIVE_RISKS] = int((risks < 0).sum())
+    blk[native.EVAL_SEL_BAD_LABELS] = bad_labels
+    blk[native.EVAL_SEL_N] = n
+    if blk[:native.EVAL_SEL_NEGATIVE_RISKS + 1].any():
+        return blk
+    ref = selective_reference(keys, risks, P)
+    for k in range(K):
+        at = off['risks'] + k * (2 + P)
+        f[at], f[at + 1], f[at + 2:at + 2 + P] = ref['mean'][k], ref['oracle_aurc'][k], ref['oracle_curve'][k]
+        for s in range(S):
+            at = off['pairs'] + (s * K + k) * (1 + P)
+            f[at], f[at + 1:at + 1 + P] = ref['aurc'][s, k], ref['curve'][s, k]
+    for s in range(S):
+        f[off['thresholds'] + s * P:off['thresholds'] + (s + 1) * P] = ref['thresholds'][s]
+    return blk
+
+
+def selective_columns(arrays: Dict[str, np.ndarray], extras: Dict[str, np.ndarray], scores: Sequence[str], risks: Sequence[str]):
+    """The (S, n) score and (K, n) risk columns in fp32 from recorded arrays (keys probs, pred, label, sev_pred, sev_true, uncertainty)
+    and extra columns, as the kernel's prepare stage builds them: numpy float32 for confidence and abs_err, fp64 rounded to fp32 for
+    entropy."""
+    probs = np.asarray(arrays['probs'], dtype=np.float32)
+    st, sp = np.asarray(arrays['sev_true'], dtype=np.float32), np.asarray(arrays['sev_pred'], dtype=np.float32)
+
+    def entropy():
+        p = probs.astype(np.float64)
+        with np.errstate(divide='ignore', invalid='ignore'):
+            return (-np.where(p == 0, 0.0, p * np.log(p)).sum(axis=1)).astype(np.float32)
+    make = {'confidence': lambda: np.float32(1.0) - probs.max(axis=1), 'entropy': entropy,
+            'sigma': lambda: np.asarray(arrays['uncertainty'], dtype=np.float32),
+            'error': lambda: (np.asarray(arrays['pred']) != np.asarray(arrays['label'])).astype(np.float32),
+            'abs_err': lambda: np.abs(st - sp), 'mu_abs_err': lambda: np.abs(st - np.asarray(extras['mu'], dtype=np.float32))}
+    column = lambda name, kinds: make[name]() if name in kinds else np.asarray(extras[name], dtype=np.float32)
+    return (np.stack([column(s, ('confidence', 'entropy', 'sigma')) for s in scores]),
+            np.stack([column(r, ('error', 'abs_err', 'mu_abs_err')) for r in risks]))
+
+
+def selective_from_block(blk: np.ndarray, scores: Sequence[str], risks: Sequence[str], coverages: int, num_classes: int) -> Dict:
+    """The dict ``EvalAccumulator.selective`` returns from one result block; raises on its counters."""
+    S, K, P = len(scores), len(risks), int(coverages)
+    off = native.eval_selective_offsets(S, K, P)
+    blk = np.asarray(blk, dtype=np.int64)
+    f = blk.view(np.float64)
+    n = int(blk[native.EVAL_SEL_N])
+    for word, text in ((native.EVAL_SEL_BAD_LABELS, f'class labels outside [0, {num_classes})'),
+                       (native.EVAL_SEL_NONFINITE_KEYS, 'non-finite score values'), (native.EVAL_SEL_NONFINITE_RISKS, 'non-finite risk values'),
+                       (native.EVAL_SEL_NEGATIVE_RISKS, 'negative risk values')):
+        if int(blk[word]):
+            raise RovitHipError(f'selective: {int(blk[word])} {text}')
+    res = {'n': n, 'coverages': coverage_counts(n, P) / n, 'risks': {}, 'scores': {}}
+    for k, risk in enumerate(risks):
+        at = off['risks'] + k * (2 + P)
+        res['risks'][risk] = {'mean': float(f[at]), 'oracle_aurc': float(f[at + 1]), 'oracle_curve': f[at + 2:at + 2 + P].copy()}
+    for s, score in enumerate(scores):
+        entry = {'thresholds': f[off['thresholds'] + s * P:off['thresholds'] + (s + 1) * P].copy()}
+        for k, risk in enumerate(risks):
+            at = off['pairs'] + (s * K + k) * (1 + P)
+            aurc, mean, oracle = float(f[at]), res['risks'][risk]['mean'], res['risks'][risk]['oracle_aurc']
+            e_aurc = aurc - oracle
+            entry[risk] = {'aurc': aurc, 'e_aurc': e_aurc, 'normalized': e_aurc / (mean - oracle) if mean != oracle else float('nan'),
+                           'curve': f[at + 1:at + 1 + P].copy()}
+        res['scores'][score] = entry
+    return res
+
 
 # ---- bootstrap: restatement and summaries ---------------------------------------------------------------------------------------
 

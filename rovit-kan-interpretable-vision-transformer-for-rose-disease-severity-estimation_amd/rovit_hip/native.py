@@ -119,6 +119,8 @@ SIGNATURES = {
     'rovit_eval_finalize': (_i, [_vp, _vp]),
     'rovit_eval_bootstrap_workspace_bytes': (_sz, [_i, _i]),
     'rovit_eval_bootstrap': (_i, [_vp, _vp]),
+    'rovit_eval_selective_workspace_bytes': (_sz, [_i, _i, _i]),
+    'rovit_eval_selective': (_i, [_vp, _vp]),
     'rovit_kan_stats_words': (_sz, [_i, _i, _i]),
     'rovit_kan_stats_partials_doubles': (_sz, [_i, _i, _i, _i]),
     'rovit_kan_edge_stats': (_i, [_vp, _vp]),
@@ -184,6 +186,30 @@ class EvalBoot(C.Structure):
 EVAL_BOOT_STREAM, EVAL_BOOT_LDS_ROWS, EVAL_BOOT_WORKSPACE_GRID, EVAL_BOOT_MAX_RESAMPLES = 0x426F6F74, 16384, 128, 65536
 EVAL_BOOT_ACCURACY, EVAL_BOOT_MACRO_F1, EVAL_BOOT_WEIGHTED_F1, EVAL_BOOT_MAE, EVAL_BOOT_RHO, EVAL_BOOT_BRIER, EVAL_BOOT_ECE = range(7)
 EVAL_BOOT_PRECISION, EVAL_BOOT_RECALL, EVAL_BOOT_F1, EVAL_BOOT_COLS = 7, 15, 23, 32
+
+
+# rovit_eval_selective: limits, score and risk kinds, and the result block's layout (the ROVIT_EVAL_SEL_* names of include/rovit_hip.h)
+EVAL_SEL_MAX_SCORES, EVAL_SEL_MAX_RISKS, EVAL_SEL_MAX_COVERAGES = 8, 4, 256
+EVAL_SEL_CONFIDENCE, EVAL_SEL_ENTROPY, EVAL_SEL_SIGMA, EVAL_SEL_SCORE_COLUMN = 0, 1, 2, 3
+EVAL_SEL_ERROR, EVAL_SEL_ABS_ERR, EVAL_SEL_RISK_COLUMN = 0, 1, 2
+EVAL_SEL_NONFINITE_KEYS, EVAL_SEL_NONFINITE_RISKS, EVAL_SEL_NEGATIVE_RISKS, EVAL_SEL_BAD_LABELS, EVAL_SEL_N, EVAL_SEL_HEADER = 0, 1, 2, 3, 4, 8
+
+
+class EvalSel(C.Structure):
+    """``rovit_eval_sel`` of include/rovit_hip.h, field for field."""
+    _fields_ = [('n', _i), ('num_classes', _i), ('num_scores', _i), ('num_risks', _i), ('num_coverages', _i), ('max_workgroups', _i),
+                ('score_kind', _i * EVAL_SEL_MAX_SCORES), ('risk_kind', _i * EVAL_SEL_MAX_RISKS),
+                ('score_column', _vp * EVAL_SEL_MAX_SCORES), ('risk_column', _vp * EVAL_SEL_MAX_RISKS),
+                ('probs', _vp), ('pred', _vp), ('label', _vp), ('sev_pred', _vp), ('sev_true', _vp), ('uncertainty', _vp),
+                ('workspace', _vp), ('workspace_bytes', _sz), ('result', _vp), ('keys_out', _vp), ('risks_out', _vp)]
+
+
+def eval_selective_offsets(S: int, K: int, P: int) -> dict:
+    """Word offsets inside rovit_eval_selective's result block; ``words`` equals ROVIT_EVAL_SEL_WORDS(S, K, P)."""
+    risks = EVAL_SEL_HEADER
+    pairs = risks + K * (2 + P)
+    thresholds = pairs + S * K * (1 + P)
+    return {'risks': risks, 'pairs': pairs, 'thresholds': thresholds, 'words': thresholds + S * P}
 
 
 class TrainLoss(C.Structure):
