@@ -746,6 +746,72 @@ size_t rovit_eval_selective_workspace_bytes(int n, int num_scores, int num_risks
 int rovit_eval_selective(const rovit_eval_sel* p, rovit_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Post-hoc calibration on that record (calibrate.hip): the first code here that ACTS on the score card.  rovit_eval_calibrate fits
+ * one temperature for the classifier (Guo et al. 2017) and one scale for the Gaussian head's sigma (Levi et al. 2019; Laves et al.
+ * 2020) on the n recorded rows, and counts the observed coverage of the central Gaussian intervals (Kuleshov et al. 2018).
+ * Log-probabilities: l[i,c] = max(log((double)probs[i,c]), ROVIT_EVAL_CAL_LOG_FLOOR = ln 2^-100); the clamp is part of the definition
+ *   (a bf16 model records exact zeros).  Rows with label -1 are left out of the classification part and counted.
+ * Temperature: with beta = 1/T, u = ln beta, w = softmax(beta l[i,:]) the fit is a root search on
+ *   g(u) = sum_i (sum_c w[i,c] l[i,c] - l[i,y_i]), non-decreasing in u (the NLL's derivative in beta), over T in [1/32, 32]:
+ *   ROVIT_EVAL_CAL_ROUNDS rounds of ROVIT_EVAL_CAL_CANDIDATES candidates u_j = lo + (hi - lo) (j / 63), u_63 = hi exactly; round 0 spans
+ *   [-ln 32, ln 32]; there g(u_0) >= 0 ends the search at T = 32 (_AT_MAX) and no g(u_j) >= 0 at T = 1/32 (_AT_MIN); otherwise, and in
+ *   every later round, j* is the first j >= 1 with g(u_j) >= 0 (63 if none) and the next bracket is [u_{j*-1}, u_{j*}].  u* is the secant
+ *   point of the last bracket (lo when both g are equal), _INTERIOR.  The bracket's g values are the bits an earlier round computed
+ *   at the same u, so g(lo) < 0 <= g(hi) holds in every round and u* lies inside a bracket 2 ln 32 / 63^4 wide.
+ * Sigma scale: rows with a non-finite or non-positive sigma, or a non-finite mu or sev_true, are left out and counted; for the rest
+ *   d = (double)sev_true - (double)mu, z = d / sigma; the block holds sum z^2 and sum ln sigma (s = sqrt(mean z^2) is the host's).
+ * Coverage: count[k] = #{|d| <= half_widths[k] * (double)sigma}, one subtraction, one multiplication, one compare: exact integers.
+ * result, ROVIT_EVAL_CAL_WORDS(L) 8-byte words, L = num_levels:
+ *   int64  [ROVIT_EVAL_CAL_N_VALID] rows with a label in [0, C)   [_BAD_LABELS]   [_N_REG] rows of the regression part   [_BAD_SIGMA]
+ *          [_STATUS]   [_N]   [ROVIT_EVAL_CAL_COVERAGE + k] coverage counts
+ *   double [_U] u* = -ln T*   [_NLL] sum_i NLL_i at T = 1   [_NLL_CAL] at T*   [_G_LO], [_G_HI] g at the ends of the last bracket
+ *          [_U_LO], [_U_HI] the last bracket   [_SUM_Z2]   [_SUM_LOG_SIGMA]
+ * The search kernel gives every lane of a wave one candidate: a workgroup stages a 256-row chunk as fp64 l plus the label in LDS
+ * (16 KB at 8 classes), each of its four waves walks 64 of those rows, every lane reads the same LDS address (a broadcast) and keeps
+ * its own candidate's fp64 sum; waves, then chunks, are folded in a fixed order by a one-workgroup step kernel that applies the
+ * bracket rule to a device-resident state the next round's launch reads.  The NLLs come from a fifth launch of the same row code.
+ * Chunks depend on n alone, integers are added with integer atomics and no floating-point atomic is used: the block is bit-identical
+ * from run to run, for every split of the rows into batches and for every grid (max_workgroups > 0 caps it).  No cooperative launch:
+ * rounds are separate launches, and their number does not depend on the data.  The whole block is zeroed first.
+ * mu and uncertainty both NULL: no regression part (its words stay 0).  workspace: rovit_eval_calibrate_workspace_bytes(n, C) bytes,
+ * 16-byte aligned (0 for sizes outside the limits).  Limits: those of the finalise; 0 <= L <= ROVIT_EVAL_CAL_MAX_LEVELS.
+ * rovit_eval_recalibrate applies a calibration in ONE elementwise launch: probs_out = fp32(softmax(beta l)) with the l above,
+ * uncertainty_out = fp32(sigma_scale * (double)uncertainty) (both NULL: not touched).  A bad descriptor is refused before any launch.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define ROVIT_EVAL_CAL_ROUNDS 4
+#define ROVIT_EVAL_CAL_CANDIDATES 64
+#define ROVIT_EVAL_CAL_MAX_LEVELS 64
+#define ROVIT_EVAL_CAL_LOG_FLOOR (-69.314718055994530942)    /* ln 2^-100 */
+#define ROVIT_EVAL_CAL_U_MAX 3.4657359027997265471           /* ln 32 */
+enum { ROVIT_EVAL_CAL_INTERIOR = 0, ROVIT_EVAL_CAL_AT_MIN = 1, ROVIT_EVAL_CAL_AT_MAX = 2 };
+enum {
+  ROVIT_EVAL_CAL_N_VALID = 0, ROVIT_EVAL_CAL_BAD_LABELS = 1, ROVIT_EVAL_CAL_N_REG = 2, ROVIT_EVAL_CAL_BAD_SIGMA = 3,
+  ROVIT_EVAL_CAL_STATUS = 4, ROVIT_EVAL_CAL_N = 5,
+  ROVIT_EVAL_CAL_U = 8, ROVIT_EVAL_CAL_NLL = 9, ROVIT_EVAL_CAL_NLL_CAL = 10, ROVIT_EVAL_CAL_G_LO = 11, ROVIT_EVAL_CAL_G_HI = 12,
+  ROVIT_EVAL_CAL_U_LO = 13, ROVIT_EVAL_CAL_U_HI = 14, ROVIT_EVAL_CAL_SUM_Z2 = 15, ROVIT_EVAL_CAL_SUM_LOG_SIGMA = 16,
+  ROVIT_EVAL_CAL_COVERAGE = 24
+};
+#define ROVIT_EVAL_CAL_WORDS(L) ((size_t)ROVIT_EVAL_CAL_COVERAGE + (size_t)(L))
+typedef struct rovit_eval_cal {
+  int n, num_classes, num_levels, max_workgroups;
+  const float* probs; const int* label; const float* sev_true; const float* uncertainty;
+  const float* mu;                   /* (n), or NULL together with uncertainty */
+  const double* half_widths;         /* (num_levels) on the device; required when num_levels > 0 and the regression part exists */
+  void* workspace;
+  size_t workspace_bytes;
+  void* result;                      /* ROVIT_EVAL_CAL_WORDS(num_levels) 8-byte words */
+} rovit_eval_cal;
+typedef struct rovit_eval_recal {
+  int n, num_classes;
+  double beta, sigma_scale;
+  const float* probs; const float* uncertainty;
+  float* probs_out; float* uncertainty_out;
+} rovit_eval_recal;
+size_t rovit_eval_calibrate_workspace_bytes(int n, int num_classes);
+int rovit_eval_calibrate(const rovit_eval_cal* p, rovit_stream_t stream);
+int rovit_eval_recalibrate(const rovit_eval_recal* p, rovit_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Per-edge activation statistics of one KAN layer over a data set (kan_stats.hip): what the edge functions of models/kan.py:70-95 do
  * ON DATA, where KANLayer.plot_activation (:97-114) and explainability/kan_viz.py only draw a few of them over [-1, 1].
  * For the layer's n input rows x (n, in_f), with s_ij(v) = sum_k spline_w[i,j,k] B_k(tanh v), phi_ij(v) = lin_w[j,i] v + s_ij(v) and

@@ -34,6 +34,8 @@ void rovit_set_error(const char* fmt, ...) {
 // (rovit_joint_loss_mixed and rovit_train_finalize were added at 440 the same way: the CutMix / MixUp loss with a per-batch record and the
 // per-epoch reduction, train_epoch.hip.)
 // (rovit_adamw_ema_flat_multi and rovit_swap_flat_multi were added at 440 the same way: weight EMA inside the AdamW launch, optim.hip.)
+// (rovit_eval_calibrate_workspace_bytes, rovit_eval_calibrate and rovit_eval_recalibrate were added at 440 the same way: temperature and
+// sigma scaling of the evaluation record, calibrate.hip.)
 extern "C" int rovit_version(void) { return 440; }
 extern "C" const char* rovit_last_error_string(void) { return g_err; }
 

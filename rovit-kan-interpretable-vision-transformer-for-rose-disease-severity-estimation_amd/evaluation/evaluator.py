@@ -5,7 +5,9 @@ block back.  Same constructor, same returned dict, same printed table, same ``ev
 sample works (the reference's ``squeeze()`` + ``np.concatenate`` raises there).  ``evaluate(bootstrap=R)`` adds percentile bootstrap
 intervals (``EvalAccumulator.bootstrap``) to the dict, the table and the file; with the default 0 all three are what they were.
 ``evaluate(selective=True)`` adds the selective-prediction score card (``EvalAccumulator.selective``: AURC, E-AURC and the risk left at
-80 % and 90 % coverage for every uncertainty score) in the same way."""
+80 % and 90 % coverage for every uncertainty score) in the same way.  ``fit_calibration(val_loader)`` fits a temperature and a sigma
+scale on another split (``EvalAccumulator.calibrate``); ``evaluate(calibration=cal)`` reports NLL, ECE, Brier score, Gaussian NLL and
+interval coverage of the test set before and after applying it, beside the raw model's headline metrics."""
 from pathlib import Path
 from typing import Dict
 
@@ -26,23 +28,36 @@ class Evaluator:
         self.device = torch.device(device)
         self.model.eval()
         self.accumulator = None
+        self.calibration = None
 
     MC_COLUMNS = ('predictive_entropy_mc', 'mutual_information', 'epistemic_var', 'uncertainty_std')
 
-    def collect(self, selective: bool = False, mc_samples: int = 0, mc_seed: int = 0) -> EvalAccumulator:
-        """The collection loop alone: one forward and one record launch per batch, nothing copied to the host.  ``selective`` also
-        records the uncertainty head's ``mu`` as an extra column when the model returns one; ``mc_samples = T > 0`` adds the MC-dropout
-        columns of ``model.predict_mc(images, num_samples=T, seed=mc_seed, offset=batch index)``, a SECOND backbone pass per batch."""
+    def collect(self, selective: bool = False, mc_samples: int = 0, mc_seed: int = 0, record_mu: bool = False) -> EvalAccumulator:
+        """The collection loop alone: one forward and one record launch per batch, nothing copied to the host.  ``selective`` (or
+        ``record_mu``) also records the uncertainty head's ``mu`` as an extra column when the model returns one; ``mc_samples = T > 0``
+        adds the MC-dropout columns of ``model.predict_mc(images, num_samples=T, seed=mc_seed, offset=batch index)``, a SECOND backbone
+        pass per batch."""
         if mc_samples and not selective:
             raise RovitHipError('Evaluator: mc_samples records columns for the selective score card; pass selective=True with it')
-        acc = self.accumulator = EvalAccumulator(len(self.config.data.class_names))
+        acc = self.accumulator = self._collect(self.test_loader, selective, mc_samples, mc_seed, record_mu)
+        return acc
+
+    def fit_calibration(self, loader):
+        """Fit a post-hoc calibration on another split, normally the validation loader: the collection loop with ``mu`` recorded, then
+        ONE ``EvalAccumulator.calibrate`` call (one device-to-host copy).  The ``Calibration`` is returned and kept on
+        ``self.calibration``; pass it to ``evaluate(calibration=...)``."""
+        self.calibration = self._collect(loader, False, 0, 0, True).calibrate()
+        return self.calibration
+
+    def _collect(self, loader, selective: bool, mc_samples: int, mc_seed: int, record_mu: bool) -> EvalAccumulator:
+        acc = EvalAccumulator(len(self.config.data.class_names))
         self.model.eval()
         with torch.no_grad():
-            for index, (images, class_labels, severity_labels) in enumerate(self.test_loader):
+            for index, (images, class_labels, severity_labels) in enumerate(loader):
                 images = images.to(self.device)
                 outputs = self.model(images)
                 extra = {}
-                if selective and outputs.get('mu') is not None:
+                if (selective or record_mu) and outputs.get('mu') is not None:
                     extra['mu'] = outputs['mu']
                 if selective and mc_samples:
                     mc = self.model.predict_mc(images, num_samples=mc_samples, seed=mc_seed, offset=index)
@@ -53,15 +68,21 @@ class Evaluator:
         return acc
 
     def evaluate(self, return_arrays: bool = False, bootstrap: int = 0, bootstrap_seed: int = 0, selective: bool = False,
-                 mc_samples: int = 0, mc_seed: int = 0):
+                 mc_samples: int = 0, mc_seed: int = 0, calibration=None):
         """``selective=True`` adds ``metrics['selective']`` (``EvalAccumulator.selective`` with 20 coverages: the built-in scores, and
         with ``mc_samples = T > 0`` the MC-dropout scores predictive_entropy_mc and mutual_information, from curriculum stage 3 also
         epistemic_var and uncertainty_std) and a "Selective prediction" section in the table and the file.  The MC columns cost a
         second backbone pass per batch, and they depend on the batch split (the dropout masks are drawn per batch position); the
-        kernel's determinism holds for given columns."""
+        kernel's determinism holds for given columns.
+
+        ``calibration`` (a ``Calibration``, normally ``fit_calibration(val_loader)``) adds ``metrics['calibration']``: ``temperature``,
+        ``sigma_scale``, ``status`` and the dicts ``before`` / ``after`` with ``nll``, ``ece``, ``brier_score``, ``gaussian_nll``, ``coverage``
+        and ``sigma_scale_refit`` of the test rows as recorded and after ``calibration.apply``; ``after`` comes from the applied
+        accumulator's own ``compute()`` and ``calibrate()``.  The headline metrics stay those of the raw model.  With ``selective=True``
+        the selective card of the applied accumulator is added under ``metrics['calibration']['selective']``."""
         print(f'\n{RULE}\nRunning Evaluation on Test Set\n{RULE}\n')
         names = list(self.config.data.class_names)
-        acc = self.collect(selective, mc_samples, mc_seed)
+        acc = self.collect(selective, mc_samples, mc_seed, record_mu=calibration is not None)
         ci = acc.bootstrap(bootstrap, seed=bootstrap_seed) if bootstrap else None          # brings the point block along in its one copy
         m = acc.compute()                                   # the loop's one synchronisation
         metrics = {k: m[k] for k in ('accuracy', 'macro_f1', 'weighted_f1', 'mae', 'spearman_rho', 'spearman', 'brier_score', 'ece')}
@@ -75,7 +96,14 @@ class Evaluator:
         if selective:
             have = acc._extra_names or ()
             scores = ['confidence', 'entropy'] + (['sigma'] if acc._has_uncertainty else []) + [c for c in self.MC_COLUMNS if c in have]
-            metrics['selective'] = acc.selective(scores=scores, risks=['error', 'abs_err'] + (['mu_abs_err'] if 'mu' in have else []))
+            risks = ['error', 'abs_err'] + (['mu_abs_err'] if 'mu' in have else [])
+            metrics['selective'] = acc.selective(scores=scores, risks=risks)
+        if calibration is not None:
+            applied = calibration.apply(acc)
+            metrics['calibration'] = {'temperature': calibration.temperature, 'sigma_scale': calibration.sigma_scale, 'status': calibration.status,
+                                      'before': self._calibration_card(acc, m), 'after': self._calibration_card(applied, applied.compute())}
+            if selective:
+                metrics['calibration']['selective'] = applied.selective(scores=scores, risks=risks)
         self._print_results(metrics)
         self._save_results(metrics)
         return (metrics, acc.arrays()) if return_arrays else metrics
@@ -93,6 +121,35 @@ class Evaluator:
         column = ['' if k is None else (f"± {ci[k]['se']:.2f} [{ci[k]['lo']:.2f}, {ci[k]['hi']:.2f}]" if k in ('accuracy', 'macro_f1') else
                                         f"± {ci[k]['se']:.4f} [{ci[k]['lo']:.4f}, {ci[k]['hi']:.4f}]") for k in keys]
         return [f'{label:<16}{value:<12}{extra}'.rstrip() for (label, value), extra in zip(rows, column)]
+
+    @staticmethod
+    def _calibration_card(acc: EvalAccumulator, m: Dict) -> Dict:
+        """What calibration is judged by, of one accumulator: its own ``compute()`` (``m``) and a ``calibrate()`` on its rows, whose
+        diagnostics at T = 1 and s = 1 describe the record as it is and whose refitted sigma scale says how far sigma is from calibrated."""
+        fit = acc.calibrate()
+        d = fit.diagnostics
+        return {'nll': d['nll'], 'ece': m['ece'], 'brier_score': m['brier_score'], 'gaussian_nll': d['gaussian_nll'], 'coverage': d['coverage'],
+                'levels': d['levels'], 'sigma_scale_refit': fit.sigma_scale}
+
+    @staticmethod
+    def _calibration_lines(metrics: Dict):
+        """Before / after lines of NLL, ECE, Brier score, Gaussian NLL and the refitted sigma scale, then the interval coverage."""
+        cal = metrics.get('calibration')
+        if cal is None:
+            return []
+        num = lambda v, spec: format(v, spec) if v is not None else format('n/a', f'>{spec.split(".")[0].lstrip(">")}')
+        scale = 'none' if cal['sigma_scale'] is None else f"{cal['sigma_scale']:.4f}"
+        lines = [f"Calibration (temperature {cal['temperature']:.4f}, sigma scale {scale}, {cal['status']}):",
+                 f"{'':<10}{'NLL':>10}{'ECE':>10}{'Brier':>10}{'Gauss. NLL':>12}{'s refit':>10}", '-' * 62]
+        for side in ('before', 'after'):
+            c = cal[side]
+            lines.append(f"{side:<10}{c['nll']:>10.4f}{c['ece']:>10.4f}{c['brier_score']:>10.4f}{num(c['gaussian_nll'], '>12.4f')}"
+                         f"{num(c['sigma_scale_refit'], '>10.4f')}")
+        if cal['before']['coverage'] is not None:
+            lines.append('Interval coverage (nominal / before / after):')
+            for side, values in (('nominal', cal['before']['levels']), ('before', cal['before']['coverage']), ('after', cal['after']['coverage'])):
+                lines.append(f'{side:<10}' + ''.join(f'{v:>7.3f}' for v in values))
+        return lines + ['']
 
     @staticmethod
     def _selective_lines(metrics: Dict):
@@ -115,6 +172,8 @@ class Evaluator:
         print('\n'.join(['', RULE, 'Evaluation Results', RULE] + self._summary(metrics, 'Spearman rho:') + [RULE, '']))
         if 'selective' in metrics:
             print('\n'.join(self._selective_lines(metrics)))
+        if 'calibration' in metrics:
+            print('\n'.join(self._calibration_lines(metrics)))
         print('Per-Class Metrics:')
         print(f"{'Class':<20} {'Precision':<12} {'Recall':<12} {'F1-Score':<12} {'Support':<10}")
         print('-' * 70)
@@ -132,7 +191,7 @@ class Evaluator:
         for name, c in metrics['per_class'].items():
             lines += [f'{name}:', f"  Precision: {c['precision']:.2f}%", f"  Recall:    {c['recall']:.2f}%", f"  F1-Score:  {c['f1']:.2f}%",
                       f"  Support:   {c['support']}", '']
-        lines += self._selective_lines(metrics)
+        lines += self._selective_lines(metrics) + self._calibration_lines(metrics)
         path = results_dir / 'evaluation_results.txt'
         path.write_text('\n'.join(lines) + '\n', encoding='utf-8')
         print(f'Results saved to {path}')

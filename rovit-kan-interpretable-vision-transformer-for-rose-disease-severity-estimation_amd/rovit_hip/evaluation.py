@@ -16,6 +16,11 @@ numpy restatement.
 ``EvalAccumulator.selective`` scores the uncertainty estimates (``rovit_eval_selective``): risk-coverage curves, AURC, E-AURC and the
 accept thresholds of every (score, risk) pair, one copy for the whole call; ``selective_reference`` states the definitions in numpy fp64.
 
+``EvalAccumulator.calibrate`` acts on the score card (``rovit_eval_calibrate``): one temperature for the classifier, one scale for the
+Gaussian head's sigma and the observed coverage of its central intervals, fitted on the recorded rows (normally the validation split)
+with a fixed number of launches and one copy; ``Calibration.apply`` (``rovit_eval_recalibrate``) gives the calibrated record as a new
+accumulator, ``Calibration.transform`` rescales a model's output dict for deployment; ``calibration_reference`` is the numpy statement.
+
 On CPU tensors the same class runs the plain torch / numpy fp64 restatement below (``result_block_from_arrays``), as
 ``JointLoss._forward_tensor_ops`` does: the host logic is testable without a GPU, and ``evaluation.metrics`` is built on it.
 """
@@ -476,6 +481,44 @@ class EvalAccumulator:
             res['keys'], res['risk_values'], res['block'] = keys, values, block
         return res
 
+    # -- post-hoc calibration --
+    def _extra_column(self, name: str) -> np.ndarray:
+        if self.device.type == 'cuda':
+            return self._extra[name][:self.n].cpu().numpy()
+        return torch.cat([b['extra'][name] for b in self._cpu]).numpy()
+
+    def calibrate(self, levels: int = 9, return_block: bool = False, _max_workgroups: int = 0) -> 'Calibration':
+        """Fit a post-hoc calibration on the recorded rows (normally those of the validation split): the temperature T that minimises
+        the NLL of softmax(log p / T) over T in [1/32, 32], and, when the batches carried mu and log_var and the extra column ``'mu'``
+        was recorded, the scale s = sqrt(mean z^2) of sigma with z = (sev_true - mu) / sigma, plus the observed coverage of the
+        central Gaussian intervals at the ``levels`` nominal levels k / (levels + 1).  The definitions are those of
+        ``calibration_reference``.  Rows whose class label is outside [0, C) are left out of the temperature and counted
+        (``bad_labels``); rows with a non-finite or non-positive sigma or a non-finite mu or sev_true are left out of the regression
+        part and counted (``bad_sigma``).  ``return_block`` keeps the raw result block (int64 words) on the result.  On the device the
+        call makes ONE device-to-host copy, and it raises after it when no row has a valid label."""
+        if not (isinstance(levels, int) and not isinstance(levels, bool) and 1 <= levels <= native.EVAL_CAL_MAX_LEVELS):
+            raise RovitHipError(f'calibrate: levels must be an int in 1..{native.EVAL_CAL_MAX_LEVELS}, got {levels!r}')
+        if self.n < 1:
+            raise RovitHipError('EvalAccumulator: nothing recorded yet')
+        has_reg = self._has_uncertainty and 'mu' in (self._extra_names or ())
+        n, L = self.n, levels
+        if self.device.type != 'cuda':
+            block = calibration_block(self._cpu_arrays(), {'mu': self._extra_column('mu')} if has_reg else {}, self.num_classes, L)
+        else:
+            ws_bytes = native.load().rovit_eval_calibrate_workspace_bytes(n, self.num_classes)
+            workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
+            out = torch.empty(native.EVAL_CAL_COVERAGE + L, dtype=torch.int64, device=self.device)
+            widths = torch.tensor(coverage_half_widths(L), dtype=torch.float64).to(self.device, non_blocking=True) if has_reg else None
+            d = native.EvalCal()
+            d.n, d.num_classes, d.num_levels, d.max_workgroups = n, self.num_classes, L, _max_workgroups
+            d.probs, d.label, d.sev_true = (native.ptr(self._rec[k]) for k in ('probs', 'label', 'sev_true'))
+            if has_reg:
+                d.uncertainty, d.mu, d.half_widths = native.ptr(self._rec['uncertainty']), native.ptr(self._extra['mu']), native.ptr(widths)
+            d.workspace, d.workspace_bytes, d.result = native.ptr(workspace), ws_bytes, native.ptr(out)
+            native.call('rovit_eval_calibrate', ctypes.byref(d), native.stream_ptr())
+            block = out.cpu().numpy()                            # the call's single device-to-host copy
+        return calibration_from_block(block, L, has_reg, self.num_classes, keep_block=return_block)
+
     # -- bootstrap --
     def _bootstrap_launch(self, num_resamples: int, seed: int, stratified: bool, table: torch.Tensor, blocks: Optional[torch.Tensor],
                           max_workgroups: int = 0) -> torch.Tensor:
@@ -542,6 +585,229 @@ class EvalAccumulator:
         if return_blocks:
             res['blocks'] = blocks
         return res
+
+# ---- post-hoc calibration: restatement, result and application -------------------------------------------------------------------
+
+CALIBRATION_STATUS = {native.EVAL_CAL_INTERIOR: 'interior', native.EVAL_CAL_AT_MIN: 'at_min', native.EVAL_CAL_AT_MAX: 'at_max'}
+
+
+def coverage_levels(levels: int) -> List[float]:
+    """The nominal levels a_k = k / (L + 1), k = 1..L."""
+    return [k / (levels + 1) for k in range(1, levels + 1)]
+
+
+def coverage_half_widths(levels: int) -> List[float]:
+    """q_k = Phi^-1(1/2 + a_k / 2): the central interval of level a_k is mu +- q_k sigma."""
+    from statistics import NormalDist
+    return [NormalDist().inv_cdf(0.5 + a / 2.0) for a in coverage_levels(levels)]
+
+
+def calibration_log_probs(probs) -> np.ndarray:
+    """l = max(log p, ln 2^-100) with the fp32 probabilities promoted to fp64; the clamp is part of the definition."""
+    p = np.asarray(probs, dtype=np.float32).astype(np.float64)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return np.fmax(np.log(p), native.EVAL_CAL_LOG_FLOOR)
+
+
+def calibration_g(l: np.ndarray, y: np.ndarray, u: float) -> float:
+    """g(u) = sum_i (sum_c w[i,c] l[i,c] - l[i,y_i]) with w = softmax(beta l[i,:]), beta = exp(u): the NLL's derivative in beta."""
+    if not len(y):
+        return 0.0
+    e = np.exp(math.exp(u) * (l - l.max(axis=1, keepdims=True)))
+    return float(((e * l).sum(axis=1) / e.sum(axis=1) - l[np.arange(len(y)), y]).sum())
+
+
+def calibration_nll_sum(l: np.ndarray, y: np.ndarray, u: float) -> float:
+    """sum_i (logsumexp_c(beta l[i,c]) - beta l[i,y_i]) with beta = exp(u)."""
+    if not len(y):
+        return 0.0
+    beta, m = math.exp(u), l.max(axis=1)
+    return float((beta * m + np.log(np.exp(beta * (l - m[:, None])).sum(axis=1)) - beta * l[np.arange(len(y)), y]).sum())
+
+
+def calibration_candidates(lo: float, hi: float) -> List[float]:
+    """u_j = lo + (hi - lo) (j / 63) for j < 63 and u_63 = hi exactly."""
+    M = native.EVAL_CAL_CANDIDATES
+    return [lo + (hi - lo) * (j / (M - 1)) for j in range(M - 1)] + [hi]
+
+
+def _record_columns(arrays: Dict, extras: Optional[Dict]):
+    """probs, label (-1 or outside [0, C): bad), sev_true, sigma and mu from either naming: ``_cpu_arrays`` / ``selective_columns``
+    (probs, label, sev_true, uncertainty) or ``arrays()`` (y_probs, y_true, severity_true, uncertainty)."""
+    pick = lambda *keys: next((arrays[k] for k in keys if k in arrays), None)
+    mu = (extras or {}).get('mu')
+    return pick('probs', 'y_probs'), pick('label', 'y_true'), pick('sev_true', 'severity_true'), arrays.get('uncertainty'), mu
+
+
+def calibration_reference(arrays: Dict, extras: Optional[Dict], num_classes: int, levels: int = 9) -> Dict:
+    """The definitions of the post-hoc calibration in numpy fp64: ``arrays`` as ``EvalAccumulator.arrays()`` returns them (or with the
+    keys ``selective_columns`` reads), ``extras`` the extra columns (``{'mu': ...}``; without it, or with ``uncertainty`` None, there is
+    no regression part).
+
+    Temperature: a root search on g (``calibration_g``), which is non-decreasing in u = -ln T because the NLL is convex in beta = 1/T:
+    4 rounds of 64 candidates (``calibration_candidates``); round 0 spans [-ln 32, ln 32], where g(u_0) >= 0 ends the search at T = 32
+    ('at_max') and no g(u_j) >= 0 at T = 1/32 ('at_min'); otherwise j* is the first j >= 1 with g(u_j) >= 0 (63 if none), the next
+    bracket is [u_{j*-1}, u_{j*}], and u* is the secant point of the last one (lo when both g are equal).
+    Sigma scale: over the rows with a finite sigma > 0 and finite mu and sev_true, z = (sev_true - mu) / sigma, sum z^2 and sum ln sigma.
+    Coverage: count[k] = #{|sev_true - mu| <= q_k sigma} with ``coverage_half_widths``.
+    Returns the words of the result block by name; the oracle of the kernel, and what ``calibrate()`` runs for CPU tensors."""
+    C, L = int(num_classes), int(levels)
+    probs, label, st, sigma, mu = _record_columns(arrays, extras)
+    label = np.asarray(label).astype(np.int64).reshape(-1)
+    n = len(label)
+    ok = (label >= 0) & (label < C)
+    l, y = calibration_log_probs(np.asarray(probs).reshape(n, C))[ok], label[ok]
+    lo, hi, status = -native.EVAL_CAL_U_MAX, native.EVAL_CAL_U_MAX, native.EVAL_CAL_INTERIOR
+    for r in range(native.EVAL_CAL_ROUNDS):
+        us = calibration_candidates(lo, hi)
+        g = [calibration_g(l, y, u) for u in us]
+        first = next((j for j in range(1, len(us)) if g[j] >= 0.0), None)
+        if r == 0 and g[0] >= 0.0:
+            status, lo, hi, g_lo, g_hi = native.EVAL_CAL_AT_MAX, us[0], us[0], g[0], g[0]
+            break
+        if r == 0 and first is None:
+            status, lo, hi, g_lo, g_hi = native.EVAL_CAL_AT_MIN, us[-1], us[-1], g[-1], g[-1]
+            break
+        j = len(us) - 1 if first is None else first
+        lo, hi, g_lo, g_hi = us[j - 1], us[j], g[j - 1], g[j]
+    u = lo if g_hi == g_lo else lo - (hi - lo) * (g_lo / (g_hi - g_lo))          # the ratio lies in [-1, 0]: no overflow
+    out = {'n': n, 'n_valid': int(ok.sum()), 'bad_labels': int((~ok).sum()), 'status': status, 'u': u, 'u_lo': lo, 'u_hi': hi, 'g_lo': g_lo,
+           'g_hi': g_hi, 'nll_sum': calibration_nll_sum(l, y, 0.0), 'nll_calibrated_sum': calibration_nll_sum(l, y, u),
+           'n_reg': 0, 'bad_sigma': 0, 'sum_z2': 0.0, 'sum_log_sigma': 0.0, 'coverage_counts': np.zeros(L, dtype=np.int64),
+           'has_regression': sigma is not None and mu is not None}
+    if out['has_regression']:
+        sg = np.asarray(sigma, dtype=np.float32).astype(np.float64).reshape(-1)
+        m = np.asarray(mu, dtype=np.float32).astype(np.float64).reshape(-1)
+        t = np.asarray(st, dtype=np.float32).astype(np.float64).reshape(-1)
+        with np.errstate(invalid='ignore'):
+            good = np.isfinite(sg) & (sg > 0) & np.isfinite(m) & np.isfinite(t)
+        sg, d = sg[good], (t - m)[good]
+        z = d / sg
+        out.update(n_reg=int(good.sum()), bad_sigma=int((~good).sum()), sum_z2=float((z * z).sum()), sum_log_sigma=float(np.log(sg).sum()),
+                   coverage_counts=np.array([int((np.abs(d) <= q * sg).sum()) for q in coverage_half_widths(L)], dtype=np.int64))
+    return out
+
+
+def calibration_block(arrays: Dict, extras: Optional[Dict], num_classes: int, levels: int = 9) -> np.ndarray:
+    """The result block of ``rovit_eval_calibrate`` (include/rovit_hip.h) from recorded arrays, on the host, through
+    ``calibration_reference``: int64 words with the fp64 values stored bit for bit."""
+    ref = calibration_reference(arrays, extras, num_classes, levels)
+    blk = np.zeros(native.EVAL_CAL_COVERAGE + int(levels), dtype=np.int64)
+    f = blk.view(np.float64)
+    for word, key in ((native.EVAL_CAL_N_VALID, 'n_valid'), (native.EVAL_CAL_BAD_LABELS, 'bad_labels'), (native.EVAL_CAL_N_REG, 'n_reg'),
+                      (native.EVAL_CAL_BAD_SIGMA, 'bad_sigma'), (native.EVAL_CAL_STATUS, 'status'), (native.EVAL_CAL_N, 'n')):
+        blk[word] = ref[key]
+    for word, key in ((native.EVAL_CAL_U, 'u'), (native.EVAL_CAL_NLL, 'nll_sum'), (native.EVAL_CAL_NLL_CAL, 'nll_calibrated_sum'),
+                      (native.EVAL_CAL_G_LO, 'g_lo'), (native.EVAL_CAL_G_HI, 'g_hi'), (native.EVAL_CAL_U_LO, 'u_lo'), (native.EVAL_CAL_U_HI, 'u_hi'),
+                      (native.EVAL_CAL_SUM_Z2, 'sum_z2'), (native.EVAL_CAL_SUM_LOG_SIGMA, 'sum_log_sigma')):
+        f[word] = ref[key]
+    blk[native.EVAL_CAL_COVERAGE:] = ref['coverage_counts']
+    return blk
+
+
+class Calibration:
+    """A fitted post-hoc calibration: ``temperature`` T (probabilities become softmax(log p / T)), ``status`` ('interior', or 'at_min' /
+    'at_max' when the fit stopped at T = 1/32 / 32), ``sigma_scale`` s (sigma becomes s sigma; None without a regression part), the row
+    counts ``n``, ``bad_labels``, ``bad_sigma`` and ``diagnostics``: ``nll`` and ``nll_calibrated`` (mean NLL of the fitted rows at T = 1
+    and at T), ``gaussian_nll`` and ``gaussian_nll_calibrated`` (mean of ln sigma + z^2 / 2 before and after; None without the regression
+    part), ``levels`` (nominal) and ``coverage`` (the observed fractions of the rows it was fitted on, before scaling)."""
+
+    def __init__(self, temperature: float, status: str = 'interior', sigma_scale: Optional[float] = None, n: int = 0, bad_labels: int = 0,
+                 bad_sigma: int = 0, diagnostics: Optional[Dict] = None, block: Optional[np.ndarray] = None):
+        if not (isinstance(temperature, float) and 0.0 < temperature < math.inf):
+            raise RovitHipError(f'Calibration: the temperature must be a positive finite float, got {temperature!r}')
+        if sigma_scale is not None and not (isinstance(sigma_scale, float) and 0.0 < sigma_scale < math.inf):
+            raise RovitHipError(f'Calibration: sigma_scale must be None or a positive finite float, got {sigma_scale!r}')
+        if status not in CALIBRATION_STATUS.values():
+            raise RovitHipError(f'Calibration: unknown status {status!r}')
+        self.temperature, self.status, self.sigma_scale = temperature, status, sigma_scale
+        self.n, self.bad_labels, self.bad_sigma = int(n), int(bad_labels), int(bad_sigma)
+        self.diagnostics = dict(diagnostics or {})
+        self.block = block
+
+    def __repr__(self) -> str:
+        return f'Calibration(temperature={self.temperature!r}, status={self.status!r}, sigma_scale={self.sigma_scale!r}, n={self.n})'
+
+    def to_dict(self) -> Dict:
+        """Plain floats, ints, strings and lists of them: ``json.dumps`` takes it, ``from_dict`` restores it."""
+        plain = lambda v: [float(x) for x in v] if isinstance(v, (list, tuple, np.ndarray)) else (None if v is None else float(v))
+        return {'temperature': self.temperature, 'status': self.status, 'sigma_scale': self.sigma_scale, 'n': self.n,
+                'bad_labels': self.bad_labels, 'bad_sigma': self.bad_sigma, 'diagnostics': {k: plain(v) for k, v in self.diagnostics.items()}}
+
+    @classmethod
+    def from_dict(cls, d: Dict) -> 'Calibration':
+        scale = d.get('sigma_scale')
+        return cls(float(d['temperature']), d.get('status', 'interior'), None if scale is None else float(scale), d.get('n', 0),
+                   d.get('bad_labels', 0), d.get('bad_sigma', 0), d.get('diagnostics'))
+
+    def transform(self, outputs: Dict) -> Dict:
+        """A model's output dict for deployment: ``cls_logits / T`` and, with a sigma scale, ``log_var + 2 ln s`` (so exp(0.5 log_var)
+        becomes s sigma), in torch; every other key holds the same tensor."""
+        out = dict(outputs)
+        out['cls_logits'] = outputs['cls_logits'] / self.temperature
+        if self.sigma_scale is not None and outputs.get('log_var') is not None:
+            out['log_var'] = outputs['log_var'] + 2.0 * math.log(self.sigma_scale)
+        return out
+
+    def apply(self, acc: 'EvalAccumulator') -> 'EvalAccumulator':
+        """The calibrated record as a NEW accumulator on the same device (``acc`` is left untouched): p' = softmax(log p / T) and
+        sigma' = s sigma in fp32 (``rovit_eval_recalibrate``, one launch); the predicted class is carried over (the argmax does not
+        change for T > 0), and the labels, the severities, the loss rows and every extra column are copied.  ``compute``, ``selective``,
+        ``bootstrap`` and ``calibrate`` work on the result.  On CPU tensors the stored logits are divided by T and ``log_var`` gets
+        + 2 ln s, as ``transform`` does."""
+        if not isinstance(acc, EvalAccumulator) or acc.n < 1:
+            raise RovitHipError('Calibration.apply: an EvalAccumulator with recorded rows is needed')
+        new = EvalAccumulator(acc.num_classes, acc.n_bins, acc._capacity0)
+        new.n, new.n_loss_rows, new.device, new._has_uncertainty, new._extra_names = acc.n, acc.n_loss_rows, acc.device, acc._has_uncertainty, acc._extra_names
+        shift = None if self.sigma_scale is None else 2.0 * math.log(self.sigma_scale)
+        if acc.device.type != 'cuda':
+            for b in acc._cpu:
+                c = dict(b)
+                c['logits'] = b['logits'] / self.temperature
+                if shift is not None and b['lv'] is not None:
+                    c['lv'] = b['lv'] + shift
+                new._cpu.append(c)
+            new._cpu_losses = list(acc._cpu_losses)
+            return new
+        n = acc.n
+        new._rec = new._alloc(n)
+        for k in ('pred', 'label', 'sev_pred', 'sev_true') + (() if shift is not None else ('uncertainty',)):
+            new._rec[k].copy_(acc._rec[k][:n])                   # device-to-device, stream-ordered
+        new._extra = {k: t[:n].clone() for k, t in acc._extra.items()}
+        if acc._loss_table is not None:
+            new._loss_table = acc._loss_table[:max(acc.n_loss_rows, 1)].clone()
+        d = native.EvalRecal()
+        d.n, d.num_classes, d.beta, d.sigma_scale = n, acc.num_classes, 1.0 / self.temperature, 1.0 if shift is None else self.sigma_scale
+        d.probs, d.probs_out = native.ptr(acc._rec['probs']), native.ptr(new._rec['probs'])
+        if shift is not None:
+            d.uncertainty, d.uncertainty_out = native.ptr(acc._rec['uncertainty']), native.ptr(new._rec['uncertainty'])
+        native.call('rovit_eval_recalibrate', ctypes.byref(d), native.stream_ptr())
+        return new
+
+
+def calibration_from_block(blk: np.ndarray, levels: int, has_regression: bool, num_classes: int, keep_block: bool = False) -> Calibration:
+    """The ``Calibration`` that ``EvalAccumulator.calibrate`` returns from one result block; T, s and the Gaussian NLLs are derived here
+    in fp64.  Raises when no row has a valid label."""
+    blk = np.asarray(blk, dtype=np.int64)
+    f = blk.view(np.float64)
+    n, n_valid, n_reg = (int(blk[w]) for w in (native.EVAL_CAL_N, native.EVAL_CAL_N_VALID, native.EVAL_CAL_N_REG))
+    if n_valid < 1:
+        raise RovitHipError(f'calibrate: none of the {n} recorded rows has a class label in [0, {num_classes})')
+    status = CALIBRATION_STATUS[int(blk[native.EVAL_CAL_STATUS])]
+    temperature = {'at_min': 1.0 / 32.0, 'at_max': 32.0}.get(status, math.exp(-float(f[native.EVAL_CAL_U])))
+    diag = {'nll': float(f[native.EVAL_CAL_NLL]) / n_valid, 'nll_calibrated': float(f[native.EVAL_CAL_NLL_CAL]) / n_valid, 'gaussian_nll': None,
+            'gaussian_nll_calibrated': None, 'levels': coverage_levels(levels), 'coverage': None}
+    scale = None
+    if has_regression and n_reg >= 1:
+        z2, ls = float(f[native.EVAL_CAL_SUM_Z2]), float(f[native.EVAL_CAL_SUM_LOG_SIGMA])
+        diag['coverage'] = [int(c) / n_reg for c in blk[native.EVAL_CAL_COVERAGE:native.EVAL_CAL_COVERAGE + levels]]
+        diag['gaussian_nll'] = (ls + 0.5 * z2) / n_reg
+        if 0.0 < z2 < math.inf:
+            scale = math.sqrt(z2 / n_reg)
+            diag['gaussian_nll_calibrated'] = (ls + n_reg * math.log(scale) + 0.5 * z2 / (scale * scale)) / n_reg
+    return Calibration(temperature, status, scale, n, int(blk[native.EVAL_CAL_BAD_LABELS]), int(blk[native.EVAL_CAL_BAD_SIGMA]) if has_regression else 0,
+                       diag, blk.copy() if keep_block else None)
+
 
 # ---- selective prediction: restatement and summaries ---------------------------------------------------------------------------
 

@@ -121,6 +121,9 @@ SIGNATURES = {
     'rovit_eval_bootstrap': (_i, [_vp, _vp]),
     'rovit_eval_selective_workspace_bytes': (_sz, [_i, _i, _i]),
     'rovit_eval_selective': (_i, [_vp, _vp]),
+    'rovit_eval_calibrate_workspace_bytes': (_sz, [_i, _i]),
+    'rovit_eval_calibrate': (_i, [_vp, _vp]),
+    'rovit_eval_recalibrate': (_i, [_vp, _vp]),
     'rovit_kan_stats_words': (_sz, [_i, _i, _i]),
     'rovit_kan_stats_partials_doubles': (_sz, [_i, _i, _i, _i]),
     'rovit_kan_edge_stats': (_i, [_vp, _vp]),
@@ -210,6 +213,29 @@ def eval_selective_offsets(S: int, K: int, P: int) -> dict:
     pairs = risks + K * (2 + P)
     thresholds = pairs + S * K * (1 + P)
     return {'risks': risks, 'pairs': pairs, 'thresholds': thresholds, 'words': thresholds + S * P}
+
+
+# rovit_eval_calibrate: the search's shape, the limits, the clamp of the log-probabilities, the statuses and the result block's layout
+# (the ROVIT_EVAL_CAL_* names of include/rovit_hip.h)
+EVAL_CAL_ROUNDS, EVAL_CAL_CANDIDATES, EVAL_CAL_MAX_LEVELS = 4, 64, 64
+EVAL_CAL_LOG_FLOOR, EVAL_CAL_U_MAX = -69.314718055994530942, 3.4657359027997265471          # ln 2^-100, ln 32
+EVAL_CAL_INTERIOR, EVAL_CAL_AT_MIN, EVAL_CAL_AT_MAX = 0, 1, 2
+EVAL_CAL_N_VALID, EVAL_CAL_BAD_LABELS, EVAL_CAL_N_REG, EVAL_CAL_BAD_SIGMA, EVAL_CAL_STATUS, EVAL_CAL_N = 0, 1, 2, 3, 4, 5
+EVAL_CAL_U, EVAL_CAL_NLL, EVAL_CAL_NLL_CAL, EVAL_CAL_G_LO, EVAL_CAL_G_HI, EVAL_CAL_U_LO, EVAL_CAL_U_HI = 8, 9, 10, 11, 12, 13, 14
+EVAL_CAL_SUM_Z2, EVAL_CAL_SUM_LOG_SIGMA, EVAL_CAL_COVERAGE = 15, 16, 24
+
+
+class EvalCal(C.Structure):
+    """``rovit_eval_cal`` of include/rovit_hip.h, field for field."""
+    _fields_ = [('n', _i), ('num_classes', _i), ('num_levels', _i), ('max_workgroups', _i), ('probs', _vp), ('label', _vp),
+                ('sev_true', _vp), ('uncertainty', _vp), ('mu', _vp), ('half_widths', _vp), ('workspace', _vp), ('workspace_bytes', _sz),
+                ('result', _vp)]
+
+
+class EvalRecal(C.Structure):
+    """``rovit_eval_recal`` of include/rovit_hip.h, field for field."""
+    _fields_ = [('n', _i), ('num_classes', _i), ('beta', C.c_double), ('sigma_scale', C.c_double), ('probs', _vp), ('uncertainty', _vp),
+                ('probs_out', _vp), ('uncertainty_out', _vp)]
 
 
 class TrainLoss(C.Structure):
