@@ -886,6 +886,101 @@ int rovit_augment_batch(const unsigned char* src, int n_images, int src_h, int s
                         const float* params, float* params_out, const rovit_augment_config* config, unsigned long long seed,
                         unsigned long long epoch, float* out, int out_h, int out_w, rovit_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Feature-space density (density.hip): is a feature row anything like the training features?  Every score of the score card above reads
+ * the heads; these three entries read outputs['features'] (models/rovit_kan.py) alone.  Mahalanobis distance to class-conditional
+ * Gaussians with a tied covariance (Lee et al., NeurIPS 2018), its relative form (Ren et al. 2021), and the AUROC / AUPR / FPR@TPR of
+ * an in-distribution against an out-of-distribution score population.  All matrix work is exact fp32 (v_mfma_f32_32x32x2_f32).
+ *
+ * rovit_density_moments: features (n, E) fp32 row-major, labels (n) int32, C classes.  A row whose label lies outside [0, C) is left out
+ * and counted in BAD_LABELS; a row with a label inside and a non-finite feature is left out and counted in BAD_ROWS; the others are the
+ * n_valid valid rows.  result, ROVIT_DENSITY_WORDS(E, C) 8-byte words:
+ *   int64  [ROVIT_DENSITY_N]  [_N_VALID]  [_BAD_LABELS]  [_BAD_ROWS]  [_COUNTS + c] valid rows of class c (words up to _HEADER are 0)
+ *   double at _HEADER: mean[c][e] (C, E), 0 for an empty class; then the mean of the valid rows (E); then the pooled within-class
+ *          scatter S_w[a][b] = sum_i (f_ia - mu32[y_i][a]) (f_ib - mu32[y_i][b]) (E, E), mu32 the class mean rounded to fp32, exactly
+ *          symmetric (the upper tile triangle is computed and mirrored)
+ * A chunk is R = ROVIT_DENSITY_CHUNK_ROWS * ceil(n / (256 ROVIT_DENSITY_CHUNK_ROWS)) consecutive rows: 256 rows up to n = 65536, never more
+ * than 256 chunks.  Sums: fp64 in row order inside a chunk, chunks in order.  Scatter: fp32 centring (one subtraction), per chunk and
+ * element one fp32 fma chain over the chunk's rows in order on the matrix instruction, chunk partials added in fp64 in chunk order.  No
+ * floating-point atomic: the block is bit-identical from run to run, for every way the rows arrived and for every grid (max_workgroups
+ * > 0 caps the grid of every kernel; a workgroup then serves several chunks in turn).  Every word of the block is written.
+ * workspace: rovit_density_workspace_bytes(n, E, C) bytes, 16-byte aligned (0 for sizes outside the limits).
+ * Limits: E a multiple of 32 in 32..256, 2 <= C <= ROVIT_EVAL_MAX_CLASSES, 1 <= n <= ROVIT_KAN_STATS_MAX_ROWS; features 16-byte aligned.
+ *
+ * rovit_density_score: for the rows f of features (B, E), any B >= 1, with z = W f and z0 = W0 f (W = whitening, W0 =
+ * background_whitening, both (E, E) row-major and LOWER-TRIANGULAR: the tiles of 32 x 32 right of the diagonal tile are never read and
+ * the entries above the diagonal inside the diagonal tile must be zero), M = class_means (C, E) and m0 = background_mean (E) in the
+ * whitened space:
+ *   class_distances (B, C) d_c = ||z - M_c||^2   background_distance (B) d0 = ||z0 - m0||^2   mahalanobis (B) min_c d_c
+ *   nearest_class (B) int32, the lowest index on a tie   relative_mahalanobis (B) min_c (d_c - d0)
+ *   with cls_logits (B, C) not NULL: energy (B) = -logsumexp(l) and max_prob_score (B) = 1 - max softmax(l), evaluated in fp64 as
+ *   -(m + log1p(r)) and r / (1 + r), m the first maximum and r the sum of exp(l_c - m) over the other classes, then rounded to fp32
+ * One launch; a workgroup owns ROVIT_DENSITY_SCORE_TILE rows (the last tile may be partial), z never goes to memory.  z_a is one fp32
+ * fma chain over k in a fixed order, d_c one fp32 fma chain over a in a fixed order: the same bits from run to run and for every grid.
+ * Limits: E and C as above.  features and both whitening matrices 16-byte aligned.
+ *
+ * rovit_ood_metrics: scores_in (n_in) and scores_out (n_out) fp32, higher = more anomalous.  Ranks are counted, not sorted: for every row
+ * x of either population less_in = #{in < x}, eq_in = #{in == x}, less_out, eq_out.  result, ROVIT_OOD_WORDS 8-byte words, zeroed first:
+ *   int64  [ROVIT_OOD_N_IN]  [_N_OUT]  [_BAD] non-finite scores (the other words are then meaningless)
+ *          [_TWO_U] sum over the out rows of 2 less_in + eq_in: AUROC = TWO_U / (2 n_in n_out) exactly
+ *          [_K + l] k_l = min(max(ceil(tpr_levels[l] * n_in), 1), n_in), the product and ceil in fp64
+ *          [_OUT_BELOW + l] #{out <= t_l}: FPR at TPR level l = OUT_BELOW / n_out
+ *   double [_THRESHOLD + l] t_l, the k_l-th smallest in-distribution score (the in row with less_in < k_l <= less_in + eq_in), widened,
+ *          -0 as +0
+ *          [_AP_OUT_SUM] sum over the out rows of ge_out / (ge_out + ge_in), ge_* = #{* >= x}: AUPR with out as the positives = sum / n_out
+ *          [_AP_IN_SUM] sum over the in rows of le_in / (le_in + le_out), le_* = #{* <= x}: AUPR with in as the positives = sum / n_in
+ * Integers are added with integer atomics; the two fp64 sums run over 256-row chunks of the concatenation (in, out) in a fixed tree, the
+ * chunk sums in a fixed order: bit-identical from run to run and for every grid (max_workgroups as above).
+ * workspace: rovit_ood_metrics_workspace_bytes(n_in, n_out) bytes, 16-byte aligned (0 outside the limits).
+ * Limits: n_in, n_out >= 1, n_in + n_out <= ROVIT_EVAL_MAX_ROWS, 0 <= num_levels <= ROVIT_OOD_MAX_LEVELS, 0 < level <= 1.
+ * A bad descriptor is refused before any launch, by all three.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define ROVIT_DENSITY_CHUNK_ROWS 256
+#define ROVIT_DENSITY_SCORE_TILE 64
+enum {
+  ROVIT_DENSITY_N = 0, ROVIT_DENSITY_N_VALID = 1, ROVIT_DENSITY_BAD_LABELS = 2, ROVIT_DENSITY_BAD_ROWS = 3, ROVIT_DENSITY_COUNTS = 4,
+  ROVIT_DENSITY_HEADER = 16
+};
+#define ROVIT_DENSITY_WORDS(E, C) ((size_t)ROVIT_DENSITY_HEADER + ((size_t)(C) + 1) * (E) + (size_t)(E) * (E))
+typedef struct rovit_density_fit {
+  int n, embed, num_classes, max_workgroups;
+  const float* features;             /* (n, embed) */
+  const int* labels;                 /* (n) */
+  void* workspace;
+  size_t workspace_bytes;
+  void* result;                      /* ROVIT_DENSITY_WORDS(embed, num_classes) 8-byte words */
+} rovit_density_fit;
+typedef struct rovit_density_scores {
+  int batch, embed, num_classes, max_workgroups;
+  const float* features;             /* (batch, embed) */
+  const float* whitening;            /* (embed, embed), lower-triangular */
+  const float* class_means;          /* (num_classes, embed), whitened */
+  const float* background_whitening; /* (embed, embed), lower-triangular */
+  const float* background_mean;      /* (embed), whitened */
+  const float* cls_logits;           /* (batch, num_classes) or NULL */
+  float* class_distances;            /* (batch, num_classes) */
+  float* background_distance; float* mahalanobis; int* nearest_class; float* relative_mahalanobis;   /* (batch) each */
+  float* energy; float* max_prob_score;                                                               /* (batch) each; with cls_logits */
+} rovit_density_scores;
+#define ROVIT_OOD_MAX_LEVELS 8
+enum {
+  ROVIT_OOD_N_IN = 0, ROVIT_OOD_N_OUT = 1, ROVIT_OOD_BAD = 2, ROVIT_OOD_TWO_U = 3, ROVIT_OOD_K = 4, ROVIT_OOD_THRESHOLD = 12,
+  ROVIT_OOD_OUT_BELOW = 20, ROVIT_OOD_AP_OUT_SUM = 28, ROVIT_OOD_AP_IN_SUM = 29, ROVIT_OOD_WORDS = 32
+};
+typedef struct rovit_ood {
+  int n_in, n_out, num_levels, max_workgroups;
+  double tpr_levels[ROVIT_OOD_MAX_LEVELS];
+  const float* scores_in; const float* scores_out;
+  void* workspace;
+  size_t workspace_bytes;
+  void* result;                      /* ROVIT_OOD_WORDS 8-byte words */
+} rovit_ood;
+size_t rovit_density_workspace_bytes(int n, int embed, int num_classes);
+int rovit_density_moments(const rovit_density_fit* p, rovit_stream_t stream);
+int rovit_density_score(const rovit_density_scores* p, rovit_stream_t stream);
+size_t rovit_ood_metrics_workspace_bytes(int n_in, int n_out);
+int rovit_ood_metrics(const rovit_ood* p, rovit_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,6 +36,9 @@ void rovit_set_error(const char* fmt, ...) {
 // (rovit_adamw_ema_flat_multi and rovit_swap_flat_multi were added at 440 the same way: weight EMA inside the AdamW launch, optim.hip.)
 // (rovit_eval_calibrate_workspace_bytes, rovit_eval_calibrate and rovit_eval_recalibrate were added at 440 the same way: temperature and
 // sigma scaling of the evaluation record, calibrate.hip.)
+// (rovit_density_workspace_bytes, rovit_density_moments, rovit_density_score, rovit_ood_metrics_workspace_bytes and rovit_ood_metrics were
+// added at 440 the same way: feature-space density and OOD metrics, density.hip.  The number stays: no argument list changed, and
+// tests/test_evaluation_cpu.py and tests/test_mc_dropout_cpu.py pin 440.)
 extern "C" int rovit_version(void) { return 440; }
 extern "C" const char* rovit_last_error_string(void) { return g_err; }
 

@@ -7,7 +7,10 @@ intervals (``EvalAccumulator.bootstrap``) to the dict, the table and the file; w
 ``evaluate(selective=True)`` adds the selective-prediction score card (``EvalAccumulator.selective``: AURC, E-AURC and the risk left at
 80 % and 90 % coverage for every uncertainty score) in the same way.  ``fit_calibration(val_loader)`` fits a temperature and a sigma
 scale on another split (``EvalAccumulator.calibrate``); ``evaluate(calibration=cal)`` reports NLL, ECE, Brier score, Gaussian NLL and
-interval coverage of the test set before and after applying it, beside the raw model's headline metrics."""
+interval coverage of the test set before and after applying it, beside the raw model's headline metrics.
+``fit_density(train_loader)`` fits the feature-space density of ``rovit_hip.density``; ``evaluate(density=fd)`` records each row's
+Mahalanobis and relative Mahalanobis distance as extra columns (two more scores of the selective card), and ``evaluate_ood(ood_loader)``
+scores the test set against an out-of-distribution loader: AUROC, AUPR and FPR at 95 % TPR of every uncertainty score."""
 from pathlib import Path
 from typing import Dict
 
@@ -29,18 +32,29 @@ class Evaluator:
         self.model.eval()
         self.accumulator = None
         self.calibration = None
+        self.density = None
 
     MC_COLUMNS = ('predictive_entropy_mc', 'mutual_information', 'epistemic_var', 'uncertainty_std')
 
-    def collect(self, selective: bool = False, mc_samples: int = 0, mc_seed: int = 0, record_mu: bool = False) -> EvalAccumulator:
+    DENSITY_COLUMNS = ('mahalanobis', 'relative_mahalanobis')
+    OOD_LEVEL = 0.95
+
+    def collect(self, selective: bool = False, mc_samples: int = 0, mc_seed: int = 0, record_mu: bool = False, density=None) -> EvalAccumulator:
         """The collection loop alone: one forward and one record launch per batch, nothing copied to the host.  ``selective`` (or
         ``record_mu``) also records the uncertainty head's ``mu`` as an extra column when the model returns one; ``mc_samples = T > 0``
         adds the MC-dropout columns of ``model.predict_mc(images, num_samples=T, seed=mc_seed, offset=batch index)``, a SECOND backbone
         pass per batch."""
         if mc_samples and not selective:
             raise RovitHipError('Evaluator: mc_samples records columns for the selective score card; pass selective=True with it')
-        acc = self.accumulator = self._collect(self.test_loader, selective, mc_samples, mc_seed, record_mu)
+        acc = self.accumulator = self._collect(self.test_loader, selective, mc_samples, mc_seed, record_mu, density)
         return acc
+
+    def fit_density(self, loader, shrinkage: float = 1e-3):
+        """Fit the feature-space density (``RoViTKAN.fit_feature_density``) on another split, normally the training loader: one backbone
+        pass, the moments on the GPU, one device-to-host copy.  The ``FeatureDensity`` is returned and kept on ``self.density``; pass it
+        to ``evaluate(density=...)`` or ``evaluate_ood(..., density=...)``."""
+        self.density = self.model.fit_feature_density(loader, shrinkage=shrinkage)
+        return self.density
 
     def fit_calibration(self, loader):
         """Fit a post-hoc calibration on another split, normally the validation loader: the collection loop with ``mu`` recorded, then
@@ -49,7 +63,7 @@ class Evaluator:
         self.calibration = self._collect(loader, False, 0, 0, True).calibrate()
         return self.calibration
 
-    def _collect(self, loader, selective: bool, mc_samples: int, mc_seed: int, record_mu: bool) -> EvalAccumulator:
+    def _collect(self, loader, selective: bool, mc_samples: int, mc_seed: int, record_mu: bool, density=None) -> EvalAccumulator:
         acc = EvalAccumulator(len(self.config.data.class_names))
         self.model.eval()
         with torch.no_grad():
@@ -64,11 +78,15 @@ class Evaluator:
                     extra['predictive_entropy_mc'], extra['mutual_information'] = mc['predictive_entropy'], mc['mutual_information']
                     if 'epistemic_var' in mc:                 # from curriculum stage 3
                         extra['epistemic_var'], extra['uncertainty_std'] = mc['epistemic_var'], mc['uncertainty_std']
+                if density is not None:
+                    d = density.score(outputs['features'])
+                    for k in self.DENSITY_COLUMNS:
+                        extra[k] = d[k]
                 acc.update(outputs, class_labels, severity_labels, extra=extra or None)
         return acc
 
     def evaluate(self, return_arrays: bool = False, bootstrap: int = 0, bootstrap_seed: int = 0, selective: bool = False,
-                 mc_samples: int = 0, mc_seed: int = 0, calibration=None):
+                 mc_samples: int = 0, mc_seed: int = 0, calibration=None, density=None):
         """``selective=True`` adds ``metrics['selective']`` (``EvalAccumulator.selective`` with 20 coverages: the built-in scores, and
         with ``mc_samples = T > 0`` the MC-dropout scores predictive_entropy_mc and mutual_information, from curriculum stage 3 also
         epistemic_var and uncertainty_std) and a "Selective prediction" section in the table and the file.  The MC columns cost a
@@ -79,10 +97,14 @@ class Evaluator:
         ``sigma_scale``, ``status`` and the dicts ``before`` / ``after`` with ``nll``, ``ece``, ``brier_score``, ``gaussian_nll``, ``coverage``
         and ``sigma_scale_refit`` of the test rows as recorded and after ``calibration.apply``; ``after`` comes from the applied
         accumulator's own ``compute()`` and ``calibrate()``.  The headline metrics stay those of the raw model.  With ``selective=True``
-        the selective card of the applied accumulator is added under ``metrics['calibration']['selective']``."""
+        the selective card of the applied accumulator is added under ``metrics['calibration']['selective']``.
+
+        ``density`` (a fitted ``FeatureDensity``, normally ``fit_density(train_loader)``) records ``mahalanobis`` and
+        ``relative_mahalanobis`` of every row as extra columns (one more launch per batch); with ``selective=True`` they are two more
+        scores of the card: does distance from the training features know which rows the model gets wrong?"""
         print(f'\n{RULE}\nRunning Evaluation on Test Set\n{RULE}\n')
         names = list(self.config.data.class_names)
-        acc = self.collect(selective, mc_samples, mc_seed, record_mu=calibration is not None)
+        acc = self.collect(selective, mc_samples, mc_seed, record_mu=calibration is not None, density=density)
         ci = acc.bootstrap(bootstrap, seed=bootstrap_seed) if bootstrap else None          # brings the point block along in its one copy
         m = acc.compute()                                   # the loop's one synchronisation
         metrics = {k: m[k] for k in ('accuracy', 'macro_f1', 'weighted_f1', 'mae', 'spearman_rho', 'spearman', 'brier_score', 'ece')}
@@ -95,7 +117,7 @@ class Evaluator:
             metrics['confidence_intervals'] = ci
         if selective:
             have = acc._extra_names or ()
-            scores = ['confidence', 'entropy'] + (['sigma'] if acc._has_uncertainty else []) + [c for c in self.MC_COLUMNS if c in have]
+            scores = ['confidence', 'entropy'] + (['sigma'] if acc._has_uncertainty else []) + [c for c in self.MC_COLUMNS + self.DENSITY_COLUMNS if c in have]
             risks = ['error', 'abs_err'] + (['mu_abs_err'] if 'mu' in have else [])
             metrics['selective'] = acc.selective(scores=scores, risks=risks)
         if calibration is not None:
@@ -107,6 +129,42 @@ class Evaluator:
         self._print_results(metrics)
         self._save_results(metrics)
         return (metrics, acc.arrays()) if return_arrays else metrics
+
+    def _ood_columns(self, loader, density) -> Dict[str, torch.Tensor]:
+        """The anomaly scores of every image of a loader as device columns: nothing is copied to the host."""
+        cols: Dict[str, list] = {}
+        self.model.eval()
+        with torch.no_grad():
+            for batch in loader:
+                images = (batch[0] if isinstance(batch, (tuple, list)) else batch).to(self.device)
+                out = self.model(images)
+                logp = torch.log_softmax(out['cls_logits'].float(), dim=1)
+                p = logp.exp()
+                row = {'max_prob': 1.0 - p.max(dim=1).values, 'entropy': -(p * logp).sum(dim=1),
+                       'energy': -torch.logsumexp(out['cls_logits'].float(), dim=1)}
+                if out.get('log_var') is not None:
+                    row['sigma'] = torch.exp(0.5 * out['log_var'].float()).reshape(-1)
+                if density is not None:
+                    d = density.score(out['features'])
+                    row.update({k: d[k] for k in self.DENSITY_COLUMNS})
+                for k, v in row.items():
+                    cols.setdefault(k, []).append(v)
+        return {k: torch.cat(v) for k, v in cols.items()}
+
+    def evaluate_ood(self, ood_loader, density=None) -> Dict[str, Dict]:
+        """Extension (not in the reference): how well each uncertainty score tells the test set (in-distribution) from ``ood_loader``
+        (out-of-distribution; batches of images, or tuples whose first element is the images).  One ``rovit_hip.density.ood_metrics``
+        card per score (AUROC, AUPR both ways, FPR at 95 % TPR; one device-to-host copy each): ``max_prob`` = 1 - max p, ``entropy``,
+        ``energy`` = -logsumexp, ``sigma`` when the model returns log_var, and with a fitted ``density`` ``mahalanobis`` and
+        ``relative_mahalanobis``.  Printed as a table; higher = more anomalous for every score."""
+        from rovit_hip.density import ood_metrics
+        inside, outside = self._ood_columns(self.test_loader, density), self._ood_columns(ood_loader, density)
+        cards = {k: ood_metrics(inside[k], outside[k], tpr_levels=(self.OOD_LEVEL,)) for k in inside if k in outside}
+        lines = ['', 'Out-of-distribution detection:', f"{'Score':<24}{'AUROC':>10}{'AUPR-out':>10}{'AUPR-in':>10}{'FPR@95%TPR':>12}", '-' * 66]
+        for k, c in cards.items():
+            lines.append(f"{k:<24}{c['auroc']:>10.4f}{c['aupr_out']:>10.4f}{c['aupr_in']:>10.4f}{c['fpr_at_tpr'][self.OOD_LEVEL]:>12.4f}")
+        print('\n'.join(lines + ['']))
+        return cards
 
     @staticmethod
     def _summary(metrics: Dict, rho_label: str):

@@ -258,6 +258,25 @@ class RoViTKAN(nn.Module):
         stats = kan_stats.model_edge_stats(self, x_or_loader, chunk)
         return {'stats': stats, **kan_stats.kan_attribution(stats)}
 
+    def fit_feature_density(self, x_or_loader, labels=None, shrinkage: float = 1e-3, chunk: int = 256):
+        """Extension (not in the reference): a fitted ``rovit_hip.density.FeatureDensity`` of this model's backbone features over images
+        (a (B,3,224,224) tensor with ``labels``, or an iterable of batches ``(images, class_labels, ...)``): class-conditional Gaussians
+        with a tied, shrunk covariance, the moments on the GPU."""
+        from rovit_hip import density
+        return density.fit_model_density(self, x_or_loader, labels, shrinkage, chunk)
+
+    def ood_scores(self, x: torch.Tensor, density) -> Dict[str, torch.Tensor]:
+        """Extension (not in the reference): the forward plus ``density.score(features, cls_logits)``: Mahalanobis and relative
+        Mahalanobis distance of every image's features from the fitted training features, with energy and 1 - max p beside them."""
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                out = self(x)
+        finally:
+            self.train(was_training)
+        return density.score(out['features'], out['cls_logits'])
+
     def count_parameters(self) -> Dict[str, int]:
         def n(m):
             return sum(p.numel() for p in m.parameters() if p.requires_grad)

@@ -128,6 +128,11 @@ SIGNATURES = {
     'rovit_kan_stats_partials_doubles': (_sz, [_i, _i, _i, _i]),
     'rovit_kan_edge_stats': (_i, [_vp, _vp]),
     'rovit_kan_curves': (_i, [_vp] * 5 + [_i] * 4 + [_vp]),
+    'rovit_density_workspace_bytes': (_sz, [_i, _i, _i]),
+    'rovit_density_moments': (_i, [_vp, _vp]),
+    'rovit_density_score': (_i, [_vp, _vp]),
+    'rovit_ood_metrics_workspace_bytes': (_sz, [_i, _i]),
+    'rovit_ood_metrics': (_i, [_vp, _vp]),
     'rovit_augment_batch': (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, C.c_ulonglong, C.c_ulonglong, _vp, _i, _i, _vp]),
 }
 
@@ -277,6 +282,47 @@ def kan_stats_offsets(in_f: int, out_f: int, n_knots: int) -> dict:
     occ = abs_in + in_f
     bad = occ + in_f * n_knots
     return {'edge': 0, 'pre': pre, 'abs_in': abs_in, 'occupancy': occ, 'nonfinite': bad, 'n': bad + 1, 'words': bad + 2}
+
+
+# rovit_density_moments / rovit_density_score / rovit_ood_metrics: limits, tile sizes and the result blocks' layouts (the ROVIT_DENSITY_* and
+# ROVIT_OOD_* names of include/rovit_hip.h)
+DENSITY_CHUNK_ROWS, DENSITY_SCORE_TILE, DENSITY_MAX_CHUNKS = 256, 64, 256
+DENSITY_N, DENSITY_N_VALID, DENSITY_BAD_LABELS, DENSITY_BAD_ROWS, DENSITY_COUNTS, DENSITY_HEADER = 0, 1, 2, 3, 4, 16
+OOD_MAX_LEVELS = 8
+OOD_N_IN, OOD_N_OUT, OOD_BAD, OOD_TWO_U, OOD_K, OOD_THRESHOLD, OOD_OUT_BELOW, OOD_AP_OUT_SUM, OOD_AP_IN_SUM, OOD_WORDS = 0, 1, 2, 3, 4, 12, 20, 28, 29, 32
+
+
+class DensityFit(C.Structure):
+    """``rovit_density_fit`` of include/rovit_hip.h, field for field."""
+    _fields_ = [('n', _i), ('embed', _i), ('num_classes', _i), ('max_workgroups', _i), ('features', _vp), ('labels', _vp),
+                ('workspace', _vp), ('workspace_bytes', _sz), ('result', _vp)]
+
+
+class DensityScores(C.Structure):
+    """``rovit_density_scores`` of include/rovit_hip.h, field for field."""
+    _fields_ = [('batch', _i), ('embed', _i), ('num_classes', _i), ('max_workgroups', _i), ('features', _vp), ('whitening', _vp),
+                ('class_means', _vp), ('background_whitening', _vp), ('background_mean', _vp), ('cls_logits', _vp),
+                ('class_distances', _vp), ('background_distance', _vp), ('mahalanobis', _vp), ('nearest_class', _vp),
+                ('relative_mahalanobis', _vp), ('energy', _vp), ('max_prob_score', _vp)]
+
+
+class Ood(C.Structure):
+    """``rovit_ood`` of include/rovit_hip.h, field for field."""
+    _fields_ = [('n_in', _i), ('n_out', _i), ('num_levels', _i), ('max_workgroups', _i), ('tpr_levels', C.c_double * OOD_MAX_LEVELS),
+                ('scores_in', _vp), ('scores_out', _vp), ('workspace', _vp), ('workspace_bytes', _sz), ('result', _vp)]
+
+
+def density_chunk_rows(n: int) -> int:
+    """Rows of one chunk of rovit_density_moments: 256 up to 65536 rows, then as many as keep the chunks at 256."""
+    return DENSITY_CHUNK_ROWS * max(1, -(-n // (DENSITY_CHUNK_ROWS * DENSITY_MAX_CHUNKS)))
+
+
+def density_offsets(E: int, C: int) -> dict:
+    """Word offsets inside rovit_density_moments' result block; ``words`` equals ROVIT_DENSITY_WORDS(E, C)."""
+    means = DENSITY_HEADER
+    mean = means + C * E
+    scatter = mean + E
+    return {'means': means, 'mean': mean, 'scatter': scatter, 'words': scatter + E * E}
 
 
 class AugmentConfigC(C.Structure):
