@@ -981,6 +981,76 @@ int rovit_density_score(const rovit_density_scores* p, rovit_stream_t stream);
 size_t rovit_ood_metrics_workspace_bytes(int n_in, int n_out);
 int rovit_ood_metrics(const rovit_ood* p, rovit_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Split conformal prediction on the evaluation record (conformal.hip; the score functions live in conformal_device.h and are shared
+ * by the fit and the application).  rovit_eval_conformal fits the thresholds of M nonconformity scores at A levels for G groups
+ * (G = 1: all rows with a label in [0, C); class_conditional: G = 1 + C, group 1 + c the rows of true class c).
+ * Scores (fp32, every one normalised with v + 0.0f so that -0 becomes +0):
+ *   _LAC 1 - p_y   _APS fma(-u, p_y, cum(y))   _RAPS fma(lambda, max(0, r(y) - raps_k), aps)   _KAN_ABS |sev_true - sev_pred|
+ *   _MU_ABS |sev_true - mu|   _MU_SCALED |sev_true - mu| / sigma   _COLUMN score_column[m][i]
+ *   The classes are ordered by p descending, ties by lower index first (an insertion sort in registers); r(c) is the 1-based rank,
+ *   cum(c) the fp32 running sum in rank order up to and including c; a NaN probability makes the row's aps and raps NaN.
+ *   u = 0 unless randomized; then w = word 0 of Philox4x32-10 with key = seed and counter (row_offset + i, 0, ROVIT_EVAL_CONF_STREAM, 0)
+ *   and u = ((float)(w >> 8) + 0.5f) * 2^-24, two IEEE fp32 operations (the addition rounds to even from w >> 8 >= 2^23 on).
+ * A row is valid for column m when its label is in [0, C), its score is finite and, for _MU_SCALED, sigma is finite and positive.
+ * For entry e = (m G + g) A + a with n_g valid rows: k = n_g + 1 - floor((n_g + 1) alpha_num[a] / alpha_den[a]) in 64-bit integers
+ * on the device; the threshold is the k-th smallest valid score of the group, an element of the column; k > n_g: +inf, trivial.
+ * The select is a most-significant-byte-first radix select over the key b ^ (b >> 31 ? 0xFFFFFFFF : 0x80000000): four rounds of a
+ * histogram kernel (LDS histograms [group][level][256], integer atomics) and a one-wave-per-entry step kernel; the launch count
+ * does not depend on the data, only integer atomics are used, and work items are walked with a stride of the grid: the block is
+ * bit-identical from run to run, for every batch split and every grid (max_workgroups > 0 caps it).
+ * result, ROVIT_EVAL_CONF_WORDS(M, G, A) 8-byte integer words:
+ *   [ROVIT_EVAL_CONF_N]   [_BAD_LABELS]   [_N_LABELLED] rows with a label in [0, C)   [_BAD_ROWS + m] labelled rows left out of column m
+ *   per entry at ROVIT_EVAL_CONF_ENTRIES + 6 e: n_g, k, less = #{valid < threshold}, equal = #{valid == threshold}, the threshold's
+ *   fp32 bits (zero-extended), trivial (0 / 1; then less = n_g, equal = 0, threshold +inf)
+ * scores_out (M, n) and u_out (n), both optional, leave the columns and the drawn u behind.
+ * rovit_eval_conformal_apply scores the rows of another record against thresholds (M, G, A) on the device: one thread per row.
+ * result, ROVIT_EVAL_CONF_APPLY_WORDS(M, A) words; per score at ROVIT_EVAL_CONF_APPLY_SCORES + m (16 + 32 A):
+ *   [0] valid rows   [1] labelled rows left out   [2] double: sum of sigma over the valid rows (_MU_SCALED only)   [8 + c] valid rows of
+ *   class c (class scores); per level at + 16 + 32 a: [0..8] set-size histogram, [9..17] covered rows by set size, [18..25] covered rows
+ *   by class (class scores), [26] covered rows (every kind).  A class c is in the set iff s(c) <= threshold[m][g][a] with g = 1 + c
+ *   under class_conditional and 0 otherwise; the other kinds use group 0.  Integer tallies go through LDS and integer atomics; the sum
+ *   of sigma is one fixed tree per 256-row chunk and the chunk sums in a fixed order.  member_out (n, M_cls, A) bytes, optional: bit c
+ *   of the byte says whether class c is in the set (M_cls counts the class scores, in descriptor order).  label == NULL: no tallies
+ *   (result and workspace may be NULL, every score must be a class score): the deployment path.
+ * Limits: those of the finalise; 1 <= M <= 8, 1 <= A <= 8, 0 < num < den <= 2^20.  A bad descriptor is refused before any launch.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define ROVIT_EVAL_CONF_MAX_SCORES 8
+#define ROVIT_EVAL_CONF_MAX_LEVELS 8
+#define ROVIT_EVAL_CONF_MAX_DEN (1u << 20)
+#define ROVIT_EVAL_CONF_STREAM 0x436F6E66u      /* "Conf": counter word 2, apart from the other Philox streams */
+enum {
+  ROVIT_EVAL_CONF_LAC = 0, ROVIT_EVAL_CONF_APS = 1, ROVIT_EVAL_CONF_RAPS = 2, ROVIT_EVAL_CONF_KAN_ABS = 3, ROVIT_EVAL_CONF_MU_ABS = 4,
+  ROVIT_EVAL_CONF_MU_SCALED = 5, ROVIT_EVAL_CONF_COLUMN = 6
+};
+enum {
+  ROVIT_EVAL_CONF_N = 0, ROVIT_EVAL_CONF_BAD_LABELS = 1, ROVIT_EVAL_CONF_N_LABELLED = 2, ROVIT_EVAL_CONF_BAD_ROWS = 8,
+  ROVIT_EVAL_CONF_ENTRIES = 16, ROVIT_EVAL_CONF_ENTRY_WORDS = 6, ROVIT_EVAL_CONF_APPLY_SCORES = 8
+};
+#define ROVIT_EVAL_CONF_WORDS(M, G, A) ((size_t)ROVIT_EVAL_CONF_ENTRIES + (size_t)ROVIT_EVAL_CONF_ENTRY_WORDS * (M) * (G) * (A))
+#define ROVIT_EVAL_CONF_APPLY_WORDS(M, A) ((size_t)ROVIT_EVAL_CONF_APPLY_SCORES + (size_t)(M) * (16 + 32 * (size_t)(A)))
+typedef struct rovit_eval_conf {
+  int n, num_classes, num_scores, num_levels, class_conditional, randomized, raps_k, max_workgroups;
+  float raps_lambda;
+  unsigned row_offset;               /* the index of row 0 in the Philox counter */
+  unsigned long long seed;
+  int score_kind[ROVIT_EVAL_CONF_MAX_SCORES];
+  unsigned alpha_num[ROVIT_EVAL_CONF_MAX_LEVELS], alpha_den[ROVIT_EVAL_CONF_MAX_LEVELS];      /* the fit only */
+  const float* score_column[ROVIT_EVAL_CONF_MAX_SCORES];   /* (n) each; read for ROVIT_EVAL_CONF_COLUMN only */
+  const float* probs; const int* label; const float* sev_pred; const float* sev_true; const float* uncertainty;
+  const float* mu;                   /* (n); required by _MU_ABS and _MU_SCALED */
+  const float* thresholds;           /* the application only: (M, G, A) fp32 on the device */
+  void* workspace;
+  size_t workspace_bytes;
+  void* result;
+  float* scores_out; float* u_out;   /* the fit only; or NULL */
+  unsigned char* member_out;         /* the application only; or NULL */
+} rovit_eval_conf;
+size_t rovit_eval_conformal_workspace_bytes(int n, int num_scores, int num_groups, int num_levels);
+int rovit_eval_conformal(const rovit_eval_conf* p, rovit_stream_t stream);
+size_t rovit_eval_conformal_apply_workspace_bytes(int n, int num_scores);
+int rovit_eval_conformal_apply(const rovit_eval_conf* p, rovit_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,6 +39,8 @@ void rovit_set_error(const char* fmt, ...) {
 // (rovit_density_workspace_bytes, rovit_density_moments, rovit_density_score, rovit_ood_metrics_workspace_bytes and rovit_ood_metrics were
 // added at 440 the same way: feature-space density and OOD metrics, density.hip.  The number stays: no argument list changed, and
 // tests/test_evaluation_cpu.py and tests/test_mc_dropout_cpu.py pin 440.)
+// (rovit_eval_conformal_workspace_bytes, rovit_eval_conformal, rovit_eval_conformal_apply_workspace_bytes and rovit_eval_conformal_apply
+// were added at 440 the same way: split conformal prediction on the evaluation record, conformal.hip.)
 extern "C" int rovit_version(void) { return 440; }
 extern "C" const char* rovit_last_error_string(void) { return g_err; }
 

@@ -10,7 +10,10 @@ scale on another split (``EvalAccumulator.calibrate``); ``evaluate(calibration=c
 interval coverage of the test set before and after applying it, beside the raw model's headline metrics.
 ``fit_density(train_loader)`` fits the feature-space density of ``rovit_hip.density``; ``evaluate(density=fd)`` records each row's
 Mahalanobis and relative Mahalanobis distance as extra columns (two more scores of the selective card), and ``evaluate_ood(ood_loader)``
-scores the test set against an out-of-distribution loader: AUROC, AUPR and FPR at 95 % TPR of every uncertainty score."""
+scores the test set against an out-of-distribution loader: AUROC, AUPR and FPR at 95 % TPR of every uncertainty score.
+``fit_conformal(val_loader)`` fits split-conformal thresholds on another split (``EvalAccumulator.conformal``);
+``evaluate(conformal=cp)`` reports the coverage and size of the label sets and the coverage and width of the severity intervals on the
+test set (``Conformal.evaluate``)."""
 from pathlib import Path
 from typing import Dict
 
@@ -33,6 +36,7 @@ class Evaluator:
         self.accumulator = None
         self.calibration = None
         self.density = None
+        self.conformal = None
 
     MC_COLUMNS = ('predictive_entropy_mc', 'mutual_information', 'epistemic_var', 'uncertainty_std')
 
@@ -63,6 +67,13 @@ class Evaluator:
         self.calibration = self._collect(loader, False, 0, 0, True).calibrate()
         return self.calibration
 
+    def fit_conformal(self, loader, **kw):
+        """Fit split-conformal thresholds on another split, normally the validation loader: the collection loop with ``mu`` recorded,
+        then ONE ``EvalAccumulator.conformal(**kw)`` call (one device-to-host copy).  The ``Conformal`` is returned and kept on
+        ``self.conformal``; pass it to ``evaluate(conformal=...)``."""
+        self.conformal = self._collect(loader, False, 0, 0, True).conformal(**kw)
+        return self.conformal
+
     def _collect(self, loader, selective: bool, mc_samples: int, mc_seed: int, record_mu: bool, density=None) -> EvalAccumulator:
         acc = EvalAccumulator(len(self.config.data.class_names))
         self.model.eval()
@@ -86,7 +97,7 @@ class Evaluator:
         return acc
 
     def evaluate(self, return_arrays: bool = False, bootstrap: int = 0, bootstrap_seed: int = 0, selective: bool = False,
-                 mc_samples: int = 0, mc_seed: int = 0, calibration=None, density=None):
+                 mc_samples: int = 0, mc_seed: int = 0, calibration=None, density=None, conformal=None):
         """``selective=True`` adds ``metrics['selective']`` (``EvalAccumulator.selective`` with 20 coverages: the built-in scores, and
         with ``mc_samples = T > 0`` the MC-dropout scores predictive_entropy_mc and mutual_information, from curriculum stage 3 also
         epistemic_var and uncertainty_std) and a "Selective prediction" section in the table and the file.  The MC columns cost a
@@ -101,10 +112,14 @@ class Evaluator:
 
         ``density`` (a fitted ``FeatureDensity``, normally ``fit_density(train_loader)``) records ``mahalanobis`` and
         ``relative_mahalanobis`` of every row as extra columns (one more launch per batch); with ``selective=True`` they are two more
-        scores of the card: does distance from the training features know which rows the model gets wrong?"""
+        scores of the card: does distance from the training features know which rows the model gets wrong?
+
+        ``conformal`` (a ``Conformal``, normally ``fit_conformal(val_loader)``) adds ``metrics['conformal']``, what
+        ``Conformal.evaluate`` returns for the test rows (one more device-to-host copy), and a "Conformal prediction" section in the
+        table and the file."""
         print(f'\n{RULE}\nRunning Evaluation on Test Set\n{RULE}\n')
         names = list(self.config.data.class_names)
-        acc = self.collect(selective, mc_samples, mc_seed, record_mu=calibration is not None, density=density)
+        acc = self.collect(selective, mc_samples, mc_seed, record_mu=calibration is not None or conformal is not None, density=density)
         ci = acc.bootstrap(bootstrap, seed=bootstrap_seed) if bootstrap else None          # brings the point block along in its one copy
         m = acc.compute()                                   # the loop's one synchronisation
         metrics = {k: m[k] for k in ('accuracy', 'macro_f1', 'weighted_f1', 'mae', 'spearman_rho', 'spearman', 'brier_score', 'ece')}
@@ -126,6 +141,8 @@ class Evaluator:
                                       'before': self._calibration_card(acc, m), 'after': self._calibration_card(applied, applied.compute())}
             if selective:
                 metrics['calibration']['selective'] = applied.selective(scores=scores, risks=risks)
+        if conformal is not None:
+            metrics['conformal'] = conformal.evaluate(acc)
         self._print_results(metrics)
         self._save_results(metrics)
         return (metrics, acc.arrays()) if return_arrays else metrics
@@ -210,6 +227,21 @@ class Evaluator:
         return lines + ['']
 
     @staticmethod
+    def _conformal_lines(metrics: Dict):
+        """One line per score and level: the target 1 - alpha, the observed coverage, and the mean set size with the share of
+        singletons (class scores) or the mean interval width (severity scores)."""
+        card = metrics.get('conformal')
+        if card is None:
+            return []
+        lines = ['Conformal prediction:', f"{'Score':<16}{'Target':>8}{'Coverage':>10}{'Mean size':>11}{'Singletons':>12}{'Mean width':>12}", '-' * 69]
+        for score, entry in card['scores'].items():
+            for alpha, lv in entry['levels'].items():
+                size = f"{lv['mean_set_size']:>11.3f}{lv['singleton_rate']:>12.3f}" if 'mean_set_size' in lv else f"{'':>23}"
+                width = f"{lv['mean_width']:>12.4f}" if 'mean_width' in lv else ''
+                lines.append(f"{score:<16}{1.0 - alpha:>8.3f}{lv['coverage']:>10.4f}{size}{width}".rstrip())
+        return lines + ['']
+
+    @staticmethod
     def _selective_lines(metrics: Dict):
         """One line per score and risk: AURC, E-AURC, normalized E-AURC and the risk left at 80 % and 90 % coverage (the curve points
         whose actual coverage k_p / n is the first at or above them)."""
@@ -232,6 +264,8 @@ class Evaluator:
             print('\n'.join(self._selective_lines(metrics)))
         if 'calibration' in metrics:
             print('\n'.join(self._calibration_lines(metrics)))
+        if 'conformal' in metrics:
+            print('\n'.join(self._conformal_lines(metrics)))
         print('Per-Class Metrics:')
         print(f"{'Class':<20} {'Precision':<12} {'Recall':<12} {'F1-Score':<12} {'Support':<10}")
         print('-' * 70)
@@ -249,7 +283,7 @@ class Evaluator:
         for name, c in metrics['per_class'].items():
             lines += [f'{name}:', f"  Precision: {c['precision']:.2f}%", f"  Recall:    {c['recall']:.2f}%", f"  F1-Score:  {c['f1']:.2f}%",
                       f"  Support:   {c['support']}", '']
-        lines += self._selective_lines(metrics) + self._calibration_lines(metrics)
+        lines += self._selective_lines(metrics) + self._calibration_lines(metrics) + self._conformal_lines(metrics)
         path = results_dir / 'evaluation_results.txt'
         path.write_text('\n'.join(lines) + '\n', encoding='utf-8')
         print(f'Results saved to {path}')

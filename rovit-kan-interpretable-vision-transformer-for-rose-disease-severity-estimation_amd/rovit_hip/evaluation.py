@@ -21,6 +21,12 @@ Gaussian head's sigma and the observed coverage of its central intervals, fitted
 with a fixed number of launches and one copy; ``Calibration.apply`` (``rovit_eval_recalibrate``) gives the calibrated record as a new
 accumulator, ``Calibration.transform`` rescales a model's output dict for deployment; ``calibration_reference`` is the numpy statement.
 
+``EvalAccumulator.conformal`` turns the recorded rows (normally the validation split) into distribution-free guarantees
+(``rovit_eval_conformal``): split-conformal thresholds of label-set scores (LAC, APS, RAPS) and severity residuals, each ONE order
+statistic found by an O(n) radix select, one copy for the whole call; ``Conformal.evaluate`` scores test rows against them
+(``rovit_eval_conformal_apply``), ``Conformal.predict`` gives label sets and severity intervals for deployment;
+``conformal_reference`` is the numpy statement.
+
 On CPU tensors the same class runs the plain torch / numpy fp64 restatement below (``result_block_from_arrays``), as
 ``JointLoss._forward_tensor_ops`` does: the host logic is testable without a GPU, and ``evaluation.metrics`` is built on it.
 """
@@ -519,6 +525,96 @@ class EvalAccumulator:
             block = out.cpu().numpy()                            # the call's single device-to-host copy
         return calibration_from_block(block, L, has_reg, self.num_classes, keep_block=return_block)
 
+    # -- split conformal prediction --
+    def _conformal_names(self, scores) -> List[str]:
+        extras = self._extra_names or ()
+        if scores is None:
+            scores = ['lac', 'aps', 'raps', 'kan_abs'] + (['mu_abs'] if 'mu' in extras else []) + \
+                (['mu_scaled'] if 'mu' in extras and self._has_uncertainty else [])
+        if isinstance(scores, str):
+            raise RovitHipError('conformal: scores is a sequence of names')
+        scores = list(scores)
+        if not 1 <= len(scores) <= native.EVAL_CONF_MAX_SCORES or len(set(scores)) != len(scores):
+            raise RovitHipError(f'conformal: 1..{native.EVAL_CONF_MAX_SCORES} distinct score names are needed, got {scores!r}')
+        for name in scores:
+            if name not in CONFORMAL_KINDS and name not in extras:
+                raise RovitHipError(f'conformal: unknown score {name!r} (known: {sorted(CONFORMAL_KINDS)} and the extra columns {sorted(extras)})')
+            if name in ('mu_abs', 'mu_scaled') and 'mu' not in extras:
+                raise RovitHipError(f"conformal: the score {name!r} needs the extra column 'mu' (update(..., extra={{'mu': outputs['mu']}}))")
+            if name == 'mu_scaled' and not self._has_uncertainty:
+                raise RovitHipError("conformal: the score 'mu_scaled' needs batches that carried mu and log_var (no uncertainty head was recorded)")
+        return scores
+
+    def _conformal_descriptor(self, scores: Sequence[str], num_levels: int, p: Dict) -> 'native.EvalConf':
+        """The part of ``rovit_eval_conf`` the fit and the application share, for this accumulator's device record."""
+        d = native.EvalConf()
+        d.n, d.num_classes, d.num_scores, d.num_levels = self.n, self.num_classes, len(scores), num_levels
+        d.class_conditional, d.randomized, d.raps_k, d.raps_lambda = int(p['class_conditional']), int(p['randomized']), p['raps_k'], p['raps_lambda']
+        d.seed, d.row_offset = p['seed'], 0
+        for i, name in enumerate(scores):
+            d.score_kind[i] = CONFORMAL_KINDS.get(name, native.EVAL_CONF_COLUMN)
+            if name not in CONFORMAL_KINDS:
+                d.score_column[i] = native.ptr(self._extra[name])
+        for k in ('probs', 'label', 'sev_pred', 'sev_true', 'uncertainty'):
+            setattr(d, k, native.ptr(self._rec[k]))
+        if 'mu' in self._extra:
+            d.mu = native.ptr(self._extra['mu'])
+        return d
+
+    def _host_columns(self):
+        """(arrays, extras) of a CPU accumulator, as the numpy statements read them."""
+        return self._cpu_arrays(), {k: self._extra_column(k) for k in (self._extra_names or ())}
+
+    def conformal(self, alphas: Sequence[float] = (0.1,), scores: Optional[Sequence[str]] = None, class_conditional: bool = False,
+                  randomized: bool = True, seed: int = 0, raps_lambda: float = 0.01, raps_k: int = 1, return_scores: bool = False,
+                  _max_workgroups: int = 0) -> 'Conformal':
+        """Fit split-conformal thresholds on the recorded rows (normally those of the validation split; the record
+        ``Calibration.apply`` returns works too).  ``scores`` names 1..8 nonconformity scores: ``'lac'`` 1 - p_y, ``'aps'``
+        cum(y) - u p_y, ``'raps'`` aps + lambda max(0, r(y) - raps_k), ``'kan_abs'`` |sev_true - sev_pred|, ``'mu_abs'`` |sev_true - mu|,
+        ``'mu_scaled'`` |sev_true - mu| / sigma, or the name of an ``extra`` column (taken as it is); default the first four, plus the mu
+        scores the record allows.  For every score, level alpha and group (all labelled rows; with ``class_conditional`` also the
+        rows of each true class) the threshold is the k-th smallest valid score, k = n_g + 1 - floor((n_g + 1) alpha), +inf
+        ('trivial') when k > n_g.  The definitions are those of ``conformal_reference``.  Rows with a class label outside [0, C) are
+        left out and counted (``bad_labels``), rows whose score is non-finite (or whose sigma is not positive and finite, for
+        ``'mu_scaled'``) are left out of that score and counted (``bad_rows``).  ``return_scores`` keeps the (M, n) fp32 score columns,
+        the drawn ``u`` and the raw result block on the result.  On the device the call makes ONE device-to-host copy, and it raises
+        after it when a score has no valid row."""
+        if self.n < 1:
+            raise RovitHipError('EvalAccumulator: nothing recorded yet')
+        scores = self._conformal_names(scores)
+        alphas, fractions = _check_conformal_args(alphas, seed, raps_lambda, raps_k, self.num_classes)
+        p = {'class_conditional': bool(class_conditional), 'randomized': bool(randomized), 'seed': seed, 'raps_lambda': float(raps_lambda),
+             'raps_k': raps_k}
+        M, A, G, n = len(scores), len(alphas), 1 + self.num_classes * int(bool(class_conditional)), self.n
+        columns = u = None
+        if self.device.type != 'cuda':
+            arrays, extras = self._host_columns()
+            ref = conformal_reference(arrays, extras, self.num_classes, alphas, scores, **p)
+            block, columns, u = ref['block'], ref['columns'], ref['u']
+        else:
+            W = native.eval_conformal_words(M, G, A)
+            out = torch.empty(W + ((M + 1) * n + 1) // 2 * int(bool(return_scores)), dtype=torch.int64, device=self.device)
+            ws_bytes = native.load().rovit_eval_conformal_workspace_bytes(n, M, G, A)
+            workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
+            d = self._conformal_descriptor(scores, A, p)
+            d.max_workgroups = _max_workgroups
+            for i, fr in enumerate(fractions):
+                d.alpha_num[i], d.alpha_den[i] = fr.numerator, fr.denominator
+            d.workspace, d.workspace_bytes, d.result = native.ptr(workspace), ws_bytes, native.ptr(out)
+            if return_scores:
+                f = out[W:].view(torch.float32)
+                d.scores_out, d.u_out = native.ptr(f), native.ptr(f[M * n:])
+            native.call('rovit_eval_conformal', ctypes.byref(d), native.stream_ptr())
+            host = out.cpu().numpy()                             # the call's single device-to-host copy
+            block = host[:W]
+            if return_scores:
+                f = host[W:].view(np.float32)
+                columns, u = f[:M * n].reshape(M, n), f[M * n:(M + 1) * n]
+        res = conformal_from_block(block, alphas, scores, self.num_classes, **p)
+        if return_scores:
+            res.score_columns, res.u, res.block = columns, u, np.array(block)
+        return res
+
     # -- bootstrap --
     def _bootstrap_launch(self, num_resamples: int, seed: int, stratified: bool, table: torch.Tensor, blocks: Optional[torch.Tensor],
                           max_workgroups: int = 0) -> torch.Tensor:
@@ -807,6 +903,456 @@ def calibration_from_block(blk: np.ndarray, levels: int, has_regression: bool, n
             diag['gaussian_nll_calibrated'] = (ls + n_reg * math.log(scale) + 0.5 * z2 / (scale * scale)) / n_reg
     return Calibration(temperature, status, scale, n, int(blk[native.EVAL_CAL_BAD_LABELS]), int(blk[native.EVAL_CAL_BAD_SIGMA]) if has_regression else 0,
                        diag, blk.copy() if keep_block else None)
+
+
+# ---- split conformal prediction: restatement, result and application ----------------------------------------------------------------
+
+CONFORMAL_KINDS = {'lac': native.EVAL_CONF_LAC, 'aps': native.EVAL_CONF_APS, 'raps': native.EVAL_CONF_RAPS, 'kan_abs': native.EVAL_CONF_KAN_ABS,
+                   'mu_abs': native.EVAL_CONF_MU_ABS, 'mu_scaled': native.EVAL_CONF_MU_SCALED}
+CONFORMAL_CLASS_SCORES = ('lac', 'aps', 'raps')
+
+
+def conformal_fraction(alpha):
+    """alpha as the rational num / den the device computes k with: ``Fraction(str(alpha)).limit_denominator(2^20)``, 0 < alpha < 1."""
+    from fractions import Fraction
+    try:
+        fr = Fraction(str(alpha)).limit_denominator(native.EVAL_CONF_MAX_DEN)
+    except (ValueError, ZeroDivisionError):
+        raise RovitHipError(f'conformal: the level {alpha!r} is not a number') from None
+    if not 0 < fr < 1:
+        raise RovitHipError(f'conformal: a level must lie in (0, 1), got {alpha!r}')
+    return fr
+
+
+def conformal_rank(n_g: int, fraction) -> int:
+    """k = n_g + 1 - floor((n_g + 1) alpha) in integers; k > n_g means the threshold is +inf ('trivial')."""
+    return n_g + 1 - ((n_g + 1) * fraction.numerator) // fraction.denominator
+
+
+def _check_conformal_args(alphas, seed, raps_lambda, raps_k, num_classes):
+    if isinstance(alphas, (int, float)):
+        alphas = (alphas,)
+    alphas = [float(a) for a in alphas]
+    if not 1 <= len(alphas) <= native.EVAL_CONF_MAX_LEVELS or len(set(alphas)) != len(alphas):
+        raise RovitHipError(f'conformal: 1..{native.EVAL_CONF_MAX_LEVELS} distinct levels are needed, got {alphas!r}')
+    fractions = [conformal_fraction(a) for a in alphas]
+    if not (isinstance(seed, int) and 0 <= seed < 1 << 64):
+        raise RovitHipError(f'conformal: seed must be an integer in [0, 2^64), got {seed!r}')
+    if not (isinstance(raps_k, int) and not isinstance(raps_k, bool) and 0 <= raps_k <= native.EVAL_MAX_CLASSES):
+        raise RovitHipError(f'conformal: raps_k must be an int in 0..{native.EVAL_MAX_CLASSES}, got {raps_k!r}')
+    if not (isinstance(raps_lambda, (int, float)) and 0.0 <= raps_lambda < math.inf):
+        raise RovitHipError(f'conformal: raps_lambda must be finite and >= 0, got {raps_lambda!r}')
+    return alphas, fractions
+
+
+def conformal_uniforms(n: int, seed: int, row_offset: int = 0) -> np.ndarray:
+    """u of rows row_offset .. row_offset + n - 1 as the kernels draw it: w = word 0 of Philox4x32-10 with key ``seed`` and counter
+    (row, 0, EVAL_CONF_STREAM, 0); u = (fp32(w >> 8) + 0.5) * 2^-24 in fp32 (the addition rounds to even once w >> 8 >= 2^23)."""
+    from oracle.philox import philox4x32_10 as philox          # checker only, like the bootstrap's draws
+    row = np.arange(n, dtype=np.uint64) + np.uint64(row_offset)
+    w = philox([row, np.zeros(n, np.uint64), np.full(n, native.EVAL_CONF_STREAM, np.uint64), np.zeros(n, np.uint64)],
+               [seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF])[0]
+    return ((w >> np.uint64(8)).astype(np.float32) + np.float32(0.5)) * np.float32(2.0 ** -24)
+
+
+def conformal_class_scores(probs, name: str, u=None, raps_lambda: float = 0.01, raps_k: int = 1):
+    """s(c) of every row and candidate class c for 'lac', 'aps' or 'raps': ``(fp32, exact)``, both (n, C).  The classes are ordered by
+    p descending, ties by lower index first; r(c) is the 1-based rank and cum(c) the float32 running sum in rank order up to and
+    including c.  ``exact`` is the fp64 statement 1 - p, cum - u p, cum - u p + lambda max(0, r - raps_k) on those fp32 inputs; ``fp32``
+    rounds it the way the kernel does (one rounding for 1 - p and for the fused cum - u p, a second one for the fused RAPS term).  A
+    NaN probability makes the row's aps and raps NaN."""
+    p = np.asarray(probs, dtype=np.float32)
+    n, C = p.shape
+    if name == 'lac':
+        s = (np.float32(1.0) - p) + np.float32(0.0)
+        return s, s.astype(np.float64)
+    with np.errstate(invalid='ignore'):
+        order = np.argsort(-p, axis=1, kind='stable')
+        cum_sorted = np.cumsum(np.take_along_axis(p, order, axis=1), axis=1, dtype=np.float32)
+    rank = np.argsort(order, axis=1, kind='stable')                      # 0-based rank of class c
+    cum = np.take_along_axis(cum_sorted, rank, axis=1).astype(np.float64)
+    uu = np.zeros(n) if u is None else np.asarray(u, dtype=np.float32).astype(np.float64)
+    exact = cum - uu[:, None] * p.astype(np.float64)
+    s = exact.astype(np.float32)
+    if name == 'raps':
+        pen = float(np.float32(raps_lambda)) * np.maximum(0, rank + 1 - int(raps_k)).astype(np.float64)
+        exact = exact + pen
+        s = (s.astype(np.float64) + pen).astype(np.float32)
+    bad = np.isnan(p).any(axis=1)
+    s, exact = s + np.float32(0.0), exact + 0.0
+    s[bad], exact[bad] = np.nan, np.nan
+    return s, exact
+
+
+def conformal_scores(arrays: Dict, extras: Optional[Dict], num_classes: int, scores: Sequence[str], randomized: bool = True, seed: int = 0,
+                     raps_lambda: float = 0.01, raps_k: int = 1, row_offset: int = 0) -> Dict:
+    """The score columns of recorded arrays (either naming, see ``_record_columns``; ``label`` None: no labels, class scores only):
+    ``columns`` (M, n) fp32 as the kernel rounds them, ``exact`` (M, n) the fp64 statements on the fp32 inputs, ``valid`` (M, n),
+    ``u`` (n) fp32 (zeros unless ``randomized``), ``label_ok`` (n), ``class_scores`` {name: (n, C) fp32} for the class scores and
+    ``sigma``.  A class score of a row without a valid label is NaN."""
+    C = int(num_classes)
+    probs, label, st, sigma, mu = _record_columns(arrays, extras)
+    sp = next((arrays[k] for k in ('sev_pred', 'severity_pred') if k in arrays), None)
+    probs = np.asarray(probs, dtype=np.float32).reshape(-1, C)
+    n = probs.shape[0]
+    f32 = lambda v: None if v is None else np.asarray(v, dtype=np.float32).reshape(-1)
+    st, sp, sigma, mu = f32(st), f32(sp), f32(sigma), f32(mu)
+    if label is None:
+        label_ok, y = np.zeros(n, dtype=bool), np.zeros(n, dtype=np.int64)
+    else:
+        label = np.asarray(label).astype(np.int64).reshape(-1)
+        label_ok = (label >= 0) & (label < C)
+        y = np.where(label_ok, label, 0)
+    u = conformal_uniforms(n, seed, row_offset) if randomized else np.zeros(n, dtype=np.float32)
+    columns, exact, valid, per_class = [], [], [], {}
+    for name in scores:
+        ok = label_ok.copy()
+        with np.errstate(divide='ignore', invalid='ignore'):
+            if name in CONFORMAL_CLASS_SCORES:
+                s, e = conformal_class_scores(probs, name, u, raps_lambda, raps_k)
+                per_class[name] = s
+                col = np.where(label_ok, s[np.arange(n), y], np.float32(np.nan))
+                ex = np.where(label_ok, e[np.arange(n), y], np.nan)
+            elif name in ('kan_abs', 'mu_abs'):
+                col = np.abs(st - (sp if name == 'kan_abs' else mu)) + np.float32(0.0)
+                ex = col.astype(np.float64)
+            elif name == 'mu_scaled':
+                ex = np.abs(st - mu).astype(np.float64) / sigma.astype(np.float64) + 0.0
+                col = ex.astype(np.float32)
+                ok &= np.isfinite(sigma) & (sigma > 0)
+            else:
+                col = f32(extras[name]) + np.float32(0.0)
+                ex = col.astype(np.float64)
+        columns.append(col.astype(np.float32))
+        exact.append(ex)
+        valid.append(ok & np.isfinite(col))
+    return {'columns': np.stack(columns), 'exact': np.stack(exact), 'valid': np.stack(valid), 'u': u, 'label_ok': label_ok,
+            'class_scores': per_class, 'sigma': sigma}
+
+
+def conformal_valid(columns, scores: Sequence[str], label, sigma, num_classes: int) -> np.ndarray:
+    """(M, n): the rows the fit uses of given score columns: a label in [0, C), a finite score and, for 'mu_scaled', a finite sigma > 0."""
+    label = np.asarray(label).astype(np.int64).reshape(-1)
+    ok = (label >= 0) & (label < num_classes)
+    valid = np.isfinite(np.asarray(columns, dtype=np.float32)) & ok[None, :]
+    for m, name in enumerate(scores):
+        if name == 'mu_scaled':
+            sg = np.asarray(sigma, dtype=np.float32).reshape(-1)
+            with np.errstate(invalid='ignore'):
+                valid[m] &= np.isfinite(sg) & (sg > 0)
+    return valid
+
+
+def conformal_block(columns, valid, label, num_classes: int, fractions, class_conditional: bool = False) -> np.ndarray:
+    """The result block of ``rovit_eval_conformal`` (include/rovit_hip.h) from (M, n) fp32 score columns and their validity, on the
+    host: per entry (score, group, level) n_g, k (``conformal_rank``), the threshold ``np.sort(valid scores)[k - 1]`` as fp32 bits,
+    less = #{< threshold}, equal = #{== threshold}; k > n_g: less = n_g, equal = 0, +inf, trivial."""
+    columns = np.atleast_2d(np.asarray(columns, dtype=np.float32))
+    valid = np.atleast_2d(np.asarray(valid, dtype=bool))
+    label = np.asarray(label).astype(np.int64).reshape(-1)
+    C, (M, n), A = int(num_classes), columns.shape, len(fractions)
+    G = 1 + C if class_conditional else 1
+    ok = (label >= 0) & (label < C)
+    blk = np.zeros(native.eval_conformal_words(M, G, A), dtype=np.int64)
+    blk[native.EVAL_CONF_N], blk[native.EVAL_CONF_BAD_LABELS], blk[native.EVAL_CONF_N_LABELLED] = n, int((~ok).sum()), int(ok.sum())
+    for m in range(M):
+        blk[native.EVAL_CONF_BAD_ROWS + m] = int((ok & ~valid[m]).sum())
+        for g in range(G):
+            rows = valid[m] & ok if g == 0 else valid[m] & (label == g - 1)
+            v = np.sort(columns[m][rows])
+            for a, fr in enumerate(fractions):
+                at = native.EVAL_CONF_ENTRIES + native.EVAL_CONF_ENTRY_WORDS * ((m * G + g) * A + a)
+                n_g = int(v.shape[0])
+                k = conformal_rank(n_g, fr)
+                if k > n_g:
+                    blk[at:at + 6] = [n_g, k, n_g, 0, 0x7F800000, 1]
+                else:
+                    q = v[k - 1]
+                    blk[at:at + 6] = [n_g, k, int((v < q).sum()), int((v == q).sum()), int(q.view(np.uint32)), 0]
+    return blk
+
+
+def conformal_reference(arrays: Dict, extras: Optional[Dict], num_classes: int, alphas: Sequence[float] = (0.1,),
+                        scores: Sequence[str] = ('lac', 'aps', 'raps', 'kan_abs'), class_conditional: bool = False, randomized: bool = True,
+                        seed: int = 0, raps_lambda: float = 0.01, raps_k: int = 1) -> Dict:
+    """The definitions of split conformal prediction in numpy: ``arrays`` as ``EvalAccumulator.arrays()`` returns them (or with the keys
+    ``selective_columns`` reads), ``extras`` the extra columns.  Scores: ``conformal_scores``.  Groups: 0 = every row with a label in
+    [0, C); with ``class_conditional`` 1 + c = the rows of true class c.  Threshold of (score, group, level): the k-th smallest valid
+    score, k = n_g + 1 - floor((n_g + 1) alpha) with alpha as ``conformal_fraction`` (``conformal_block``).  Returns the score dict of
+    ``conformal_scores`` plus ``block``, the result block: the oracle of the kernel, and what ``conformal()`` runs for CPU tensors."""
+    _, label, _, _, _ = _record_columns(arrays, extras)
+    out = conformal_scores(arrays, extras, num_classes, scores, randomized, seed, raps_lambda, raps_k)
+    out['block'] = conformal_block(out['columns'], out['valid'], label, num_classes, [conformal_fraction(a) for a in alphas], class_conditional)
+    return out
+
+
+def conformal_membership(class_scores: np.ndarray, thresholds: np.ndarray, class_conditional: bool) -> np.ndarray:
+    """(n, C) bool: class c is in the set iff s(c) <= threshold of group 1 + c (``class_conditional``) or of group 0; ``thresholds``
+    holds one score's and one level's G values.  NaN scores are in no set."""
+    thr = np.asarray(thresholds, dtype=np.float32).reshape(-1)
+    q = thr[1:][None, :] if class_conditional else thr[0]
+    with np.errstate(invalid='ignore'):
+        return np.asarray(class_scores, dtype=np.float32) <= q
+
+
+def conformal_apply_block(arrays: Dict, extras: Optional[Dict], num_classes: int, scores: Sequence[str], thresholds, class_conditional: bool = False,
+                          randomized: bool = True, seed: int = 0, raps_lambda: float = 0.01, raps_k: int = 1, row_offset: int = 0):
+    """The result block of ``rovit_eval_conformal_apply`` (include/rovit_hip.h) from recorded arrays and (M, G, A) fp32 thresholds, on
+    the host, and the (n, M_cls, A) membership bytes (bit c: class c is in the set).  The sum of sigma is in fp64."""
+    C, M = int(num_classes), len(scores)
+    thr = np.asarray(thresholds, dtype=np.float32).reshape(M, 1 + C if class_conditional else 1, -1)
+    A = thr.shape[2]
+    sc = conformal_scores(arrays, extras, C, scores, randomized, seed, raps_lambda, raps_k, row_offset)
+    _, label, _, _, _ = _record_columns(arrays, extras)
+    label = np.asarray(label).astype(np.int64).reshape(-1)
+    n, ok = len(label), sc['label_ok']
+    per = 16 + 32 * A
+    blk = np.zeros(native.eval_conformal_apply_words(M, A), dtype=np.int64)
+    blk[native.EVAL_CONF_N], blk[native.EVAL_CONF_BAD_LABELS], blk[native.EVAL_CONF_N_LABELLED] = n, int((~ok).sum()), int(ok.sum())
+    member = np.zeros((n, sum(s in CONFORMAL_CLASS_SCORES for s in scores), A), dtype=np.uint8)
+    mc = 0
+    for m, name in enumerate(scores):
+        base = native.EVAL_CONF_APPLY_SCORES + m * per
+        valid = sc['valid'][m]
+        blk[base], blk[base + 1] = int(valid.sum()), int((ok & ~valid).sum())
+        y = label[valid]
+        if name in CONFORMAL_CLASS_SCORES:
+            blk[base + 8:base + 8 + C] = np.bincount(y, minlength=C)
+        if name == 'mu_scaled':
+            blk[base + 2:base + 3].view(np.float64)[0] = sc['sigma'][valid].astype(np.float64).sum()
+        for a in range(A):
+            at = base + 16 + 32 * a
+            if name in CONFORMAL_CLASS_SCORES:
+                inside = conformal_membership(sc['class_scores'][name], thr[m, :, a], class_conditional)
+                member[:, mc, a] = (inside.astype(np.uint8) << np.arange(C, dtype=np.uint8)[None, :]).sum(axis=1)
+                size, hit = inside.sum(axis=1)[valid], inside[valid][np.arange(len(y)), y]
+                blk[at:at + C + 1] = np.bincount(size, minlength=C + 1)
+                blk[at + 9:at + 9 + C + 1] = np.bincount(size[hit], minlength=C + 1)
+                blk[at + 18:at + 18 + C] = np.bincount(y[hit], minlength=C)
+                blk[at + 26] = int(hit.sum())
+            else:
+                blk[at + 26] = int((sc['columns'][m][valid] <= thr[m, 0, a]).sum())
+        mc += name in CONFORMAL_CLASS_SCORES
+    return blk, member
+
+
+class Conformal:
+    """Fitted split-conformal thresholds: ``alphas``, ``scores``, ``thresholds[score][alpha]`` (a float; with ``class_conditional`` an
+    array of 1 + C: group 0 = all rows, 1 + c = true class c), ``status[score][alpha]`` ('ok' or 'trivial': k > n_g, the threshold is
+    +inf; an array of strings with ``class_conditional``), ``n[score]`` (the valid rows n_g), ``k[score][alpha]``, ``less`` and ``equal``
+    (the fitted rows below and at the threshold), ``bad_labels``, ``bad_rows[score]`` and the parameters the scores depend on
+    (``num_classes``, ``class_conditional``, ``randomized``, ``seed``, ``raps_lambda``, ``raps_k``) and ``rows``, the number of rows it
+    was fitted on: their u took the Philox counters 0 .. rows - 1, so ``evaluate`` draws the test rows' u from ``rows`` on.  A new row's label set
+    {c : s(c) <= threshold} contains its true class with probability >= 1 - alpha when the row is exchangeable with the fitted ones
+    (per class with ``class_conditional``); the interval centre +- threshold (times sigma for ``'mu_scaled'``) contains its severity."""
+
+    def __init__(self, alphas, scores, num_classes: int, thresholds: Dict, status: Dict, n: Dict, k: Dict, less: Optional[Dict] = None,
+                 equal: Optional[Dict] = None, bad_labels: int = 0, bad_rows: Optional[Dict] = None, class_conditional: bool = False,
+                 randomized: bool = True, seed: int = 0, raps_lambda: float = 0.01, raps_k: int = 1, rows: int = 0):
+        self.alphas, self.scores, self.num_classes = [float(a) for a in alphas], list(scores), int(num_classes)
+        self.rows = int(rows)
+        self.thresholds, self.status, self.n, self.k, self.less, self.equal = thresholds, status, n, k, less or {}, equal or {}
+        self.bad_labels, self.bad_rows = int(bad_labels), dict(bad_rows or {})
+        self.class_conditional, self.randomized, self.seed = bool(class_conditional), bool(randomized), int(seed)
+        self.raps_lambda, self.raps_k = float(raps_lambda), int(raps_k)
+        self.score_columns = self.u = self.block = None          # conformal(return_scores=True)
+
+    def __repr__(self) -> str:
+        return (f'Conformal(scores={self.scores!r}, alphas={self.alphas!r}, class_conditional={self.class_conditional}, '
+                f'randomized={self.randomized}, n={self.n.get(self.scores[0])!r})')
+
+    @property
+    def params(self) -> Dict:
+        return {'class_conditional': self.class_conditional, 'randomized': self.randomized, 'seed': self.seed, 'raps_lambda': self.raps_lambda,
+                'raps_k': self.raps_k}
+
+    def to_dict(self) -> Dict:
+        """Plain floats, ints, strings and lists of them (levels in the order of ``alphas``; +inf as the string 'inf'): ``json.dumps``
+        takes it, ``from_dict`` restores it."""
+        def plain(v):
+            if isinstance(v, (list, tuple, np.ndarray)):
+                return [plain(x) for x in v]
+            if isinstance(v, (str, np.str_)):
+                return str(v)
+            if isinstance(v, (float, np.floating)):
+                return 'inf' if v == math.inf else float(v)
+            return int(v)
+        per_level = lambda d: {s: [plain(d[s][a]) for a in self.alphas] for s in self.scores}
+        out = {'alphas': list(self.alphas), 'scores': list(self.scores), 'num_classes': self.num_classes, 'thresholds': per_level(self.thresholds),
+               'status': per_level(self.status), 'n': {s: plain(self.n[s]) for s in self.scores}, 'k': per_level(self.k),
+               'less': per_level(self.less) if self.less else {}, 'equal': per_level(self.equal) if self.equal else {},
+               'bad_labels': self.bad_labels, 'bad_rows': {s: int(self.bad_rows.get(s, 0)) for s in self.scores}, 'rows': self.rows}
+        out.update(self.params)
+        return out
+
+    @classmethod
+    def from_dict(cls, d: Dict) -> 'Conformal':
+        alphas, scores = [float(a) for a in d['alphas']], list(d['scores'])
+        cc = bool(d.get('class_conditional', False))
+        number = lambda v, kind: (np.array([kind(x) for x in v]) if isinstance(v, list) else kind(v))
+        per_level = lambda key, kind: {s: {a: number(d[key][s][i], kind) for i, a in enumerate(alphas)} for s in scores} if d.get(key) else {}
+        return cls(alphas, scores, d['num_classes'], per_level('thresholds', float), per_level('status', str),
+                   {s: number(d['n'][s], int) for s in scores}, per_level('k', int), per_level('less', int), per_level('equal', int),
+                   d.get('bad_labels', 0), d.get('bad_rows'), cc, d.get('randomized', True), d.get('seed', 0), d.get('raps_lambda', 0.01),
+                   d.get('raps_k', 1), d.get('rows', 0))
+
+    def threshold_array(self, scores: Optional[Sequence[str]] = None, alphas: Optional[Sequence[float]] = None) -> np.ndarray:
+        """(M, G, A) fp32: the thresholds as ``rovit_eval_conformal_apply`` reads them."""
+        scores, alphas = list(scores or self.scores), list(alphas or self.alphas)
+        G = 1 + self.num_classes if self.class_conditional else 1
+        out = np.zeros((len(scores), G, len(alphas)), dtype=np.float32)
+        for m, s in enumerate(scores):
+            for a, alpha in enumerate(alphas):
+                out[m, :, a] = np.asarray(self.thresholds[s][alpha], dtype=np.float32).reshape(-1)
+        return out
+
+    def _check_record(self, acc: 'EvalAccumulator', what: str) -> None:
+        if not isinstance(acc, EvalAccumulator) or acc.n < 1:
+            raise RovitHipError(f'{what}: an EvalAccumulator with recorded rows is needed')
+        if acc.num_classes != self.num_classes:
+            raise RovitHipError(f'{what}: fitted on {self.num_classes} classes, the accumulator holds {acc.num_classes}')
+        if list(acc._conformal_names(self.scores)) != self.scores:          # raises when a column the scores need is missing
+            raise RovitHipError(f'{what}: the accumulator cannot provide the scores {self.scores!r}')
+
+    def evaluate(self, acc: 'EvalAccumulator', _max_workgroups: int = 0) -> Dict:
+        """Score the test rows of another accumulator against the fitted thresholds: ``{'n', 'bad_labels', 'scores': {score: {'n',
+        'bad_rows', 'levels': {alpha: {...}}}}}``.  Per class score and level: ``coverage``, ``mean_set_size``, ``size_histogram`` (sizes
+        0..C), ``coverage_by_class``, ``coverage_by_size``, ``empty_rate``, ``singleton_rate`` and ``singleton_accuracy`` (NaN where a
+        denominator is 0).  Per regression score and level: ``coverage``, ``mean_width`` (2 q for the absolute scores, 2 q mean sigma for
+        ``'mu_scaled'``) and ``infinite``.  An extra-column score: ``coverage``.  Rows are left out and counted as in the fit.  With
+        ``class_conditional`` class c is in the set iff s(c) <= the threshold of group 1 + c; the other scores use group 0.  u is drawn
+        for the counter ``rows`` + the row's index in ``acc``, past the fitted rows' draws.  On the device the call makes ONE device-to-host copy (``'block'`` holds it)."""
+        self._check_record(acc, 'Conformal.evaluate')
+        M, A, C = len(self.scores), len(self.alphas), self.num_classes
+        thr = self.threshold_array()
+        if acc.device.type != 'cuda':
+            arrays, extras = acc._host_columns()
+            block, _ = conformal_apply_block(arrays, extras, C, self.scores, thr, row_offset=self.rows, **self.params)
+        else:
+            n = acc.n
+            out = torch.empty(native.eval_conformal_apply_words(M, A), dtype=torch.int64, device=acc.device)
+            ws_bytes = native.load().rovit_eval_conformal_apply_workspace_bytes(n, M)
+            workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=acc.device)
+            thr_dev = torch.from_numpy(thr.reshape(-1)).to(acc.device, non_blocking=True)
+            d = acc._conformal_descriptor(self.scores, A, self.params)
+            d.max_workgroups, d.row_offset = _max_workgroups, self.rows
+            d.thresholds, d.workspace, d.workspace_bytes, d.result = native.ptr(thr_dev), native.ptr(workspace), ws_bytes, native.ptr(out)
+            native.call('rovit_eval_conformal_apply', ctypes.byref(d), native.stream_ptr())
+            block = out.cpu().numpy()                            # the call's single device-to-host copy
+        res = conformal_metrics_from_block(block, self.scores, self.alphas, thr, C)
+        res['block'] = np.array(block)
+        return res
+
+    def _level(self, alpha) -> float:
+        if alpha is None:
+            return self.alphas[0]
+        if float(alpha) not in self.alphas:
+            raise RovitHipError(f'Conformal: the level {alpha!r} was not fitted (fitted: {self.alphas!r})')
+        return float(alpha)
+
+    def predict(self, outputs: Dict, score: str = 'aps', alpha: Optional[float] = None, row_offset: int = 0) -> Dict:
+        """Label sets and severity intervals of a model's output dict, for deployment: ``'sets'`` (B, C) bool from the class score
+        ``score`` at level ``alpha`` (None: the first fitted level), ``'set_size'`` (B,), and, when their score was fitted,
+        ``'kan_interval'`` = kan_severity +- q ('kan_abs') and ``'mu_interval'`` = mu +- q sigma ('mu_scaled', sigma = exp(0.5 log_var))
+        or mu +- q ('mu_abs', used when 'mu_scaled' was not fitted), both (B, 2).  The softmax is torch's; on the device the membership
+        comes from ``rovit_eval_conformal_apply``'s score function in one launch, with u drawn for the rows ``row_offset + i``, and
+        nothing is copied to the host.  Offsets from ``rows`` on keep the draws apart from those of the fitted rows."""
+        if score not in CONFORMAL_CLASS_SCORES or score not in self.scores:
+            raise RovitHipError(f'Conformal.predict: {score!r} is not a fitted class score (fitted: {[s for s in self.scores if s in CONFORMAL_CLASS_SCORES]!r})')
+        alpha = self._level(alpha)
+        if not (isinstance(row_offset, int) and 0 <= row_offset < 1 << 32):
+            raise RovitHipError(f'Conformal.predict: row_offset must be an integer in [0, 2^32), got {row_offset!r}')
+        logits = outputs['cls_logits'].detach()
+        C = self.num_classes
+        if logits.dim() != 2 or logits.shape[1] != C or logits.shape[0] < 1:
+            raise RovitHipError(f'Conformal.predict: cls_logits must be (B >= 1, {C}), got {tuple(logits.shape)}')
+        B = logits.shape[0]
+        probs = torch.softmax(logits.float(), dim=1).contiguous()
+        thr = self.threshold_array([score], [alpha])
+        bits = torch.arange(C, device=logits.device)
+        if not logits.is_cuda:
+            s, _ = conformal_class_scores(probs.numpy(), score, conformal_uniforms(B, self.seed, row_offset) if self.randomized else None,
+                                          self.raps_lambda, self.raps_k)
+            sets = torch.from_numpy(conformal_membership(s, thr[0, :, 0], self.class_conditional))
+        else:
+            member = torch.empty(B, dtype=torch.uint8, device=logits.device)
+            thr_dev = torch.from_numpy(thr.reshape(-1)).to(logits.device, non_blocking=True)
+            d = native.EvalConf()
+            d.n, d.num_classes, d.num_scores, d.num_levels, d.class_conditional, d.randomized = B, C, 1, 1, int(self.class_conditional), int(self.randomized)
+            d.raps_k, d.raps_lambda, d.seed, d.row_offset = self.raps_k, self.raps_lambda, self.seed, row_offset
+            d.score_kind[0] = CONFORMAL_KINDS[score]
+            d.probs, d.thresholds, d.member_out = native.ptr(probs), native.ptr(thr_dev), native.ptr(member)
+            native.call('rovit_eval_conformal_apply', ctypes.byref(d), native.stream_ptr())
+            sets = ((member.long()[:, None] >> bits[None, :]) & 1).bool()
+        out = {'sets': sets, 'set_size': sets.sum(dim=1)}
+        flat = lambda t: t.detach().float().reshape(-1)
+        band = lambda centre, half: torch.stack([centre - half, centre + half], dim=1)
+        if 'kan_abs' in self.scores and outputs.get('kan_severity') is not None:
+            out['kan_interval'] = band(flat(outputs['kan_severity']), float(self.threshold_array(['kan_abs'], [alpha])[0, 0, 0]))
+        if outputs.get('mu') is not None:
+            if 'mu_scaled' in self.scores and outputs.get('log_var') is not None:
+                q = float(self.threshold_array(['mu_scaled'], [alpha])[0, 0, 0])
+                out['mu_interval'] = band(flat(outputs['mu']), q * torch.exp(0.5 * flat(outputs['log_var'])))
+            elif 'mu_abs' in self.scores:
+                out['mu_interval'] = band(flat(outputs['mu']), float(self.threshold_array(['mu_abs'], [alpha])[0, 0, 0]))
+        return out
+
+
+def conformal_from_block(blk: np.ndarray, alphas: Sequence[float], scores: Sequence[str], num_classes: int, class_conditional: bool = False,
+                         randomized: bool = True, seed: int = 0, raps_lambda: float = 0.01, raps_k: int = 1) -> Conformal:
+    """The ``Conformal`` that ``EvalAccumulator.conformal`` returns from one result block.  Raises when a score has no valid row."""
+    blk = np.asarray(blk, dtype=np.int64)
+    C, M, A = int(num_classes), len(scores), len(alphas)
+    G = 1 + C if class_conditional else 1
+    n = int(blk[native.EVAL_CONF_N])
+    if int(blk[native.EVAL_CONF_N_LABELLED]) < 1:
+        raise RovitHipError(f'conformal: none of the {n} recorded rows has a class label in [0, {C})')
+    e = blk[native.EVAL_CONF_ENTRIES:native.EVAL_CONF_ENTRIES + native.EVAL_CONF_ENTRY_WORDS * M * G * A].reshape(M, G, A, native.EVAL_CONF_ENTRY_WORDS)
+    q = e[..., 4].astype(np.uint32).view(np.float32)
+    pick = (lambda v: v.copy()) if class_conditional else (lambda v: v[0].item())
+    fields = {'thresholds': {}, 'status': {}, 'k': {}, 'less': {}, 'equal': {}}
+    n_valid = {}
+    for m, s in enumerate(scores):
+        if int(e[m, 0, 0, 0]) < 1:
+            raise RovitHipError(f'conformal: the score {s!r} has no valid row among the {n} recorded ones')
+        n_valid[s] = pick(e[m, :, 0, 0])
+        for key, values in (('thresholds', q[m].astype(np.float64)), ('k', e[m, :, :, 1]), ('less', e[m, :, :, 2]), ('equal', e[m, :, :, 3]),
+                            ('status', np.where(e[m, :, :, 5] != 0, 'trivial', 'ok'))):
+            fields[key][s] = {alpha: pick(values[:, a]) for a, alpha in enumerate(alphas)}
+    return Conformal(alphas, scores, C, fields['thresholds'], fields['status'], n_valid, fields['k'], fields['less'], fields['equal'],
+                     int(blk[native.EVAL_CONF_BAD_LABELS]), {s: int(blk[native.EVAL_CONF_BAD_ROWS + m]) for m, s in enumerate(scores)},
+                     class_conditional, randomized, seed, raps_lambda, raps_k, n)
+
+
+def conformal_metrics_from_block(blk: np.ndarray, scores: Sequence[str], alphas: Sequence[float], thresholds: np.ndarray, num_classes: int) -> Dict:
+    """The dict ``Conformal.evaluate`` returns from one result block of ``rovit_eval_conformal_apply``; every ratio is taken in fp64."""
+    blk = np.asarray(blk, dtype=np.int64)
+    f = blk.view(np.float64)
+    C, A = int(num_classes), len(alphas)
+    per = 16 + 32 * A
+    ratio = lambda a, b: float(a) / float(b) if b else float('nan')
+    res = {'n': int(blk[native.EVAL_CONF_N]), 'bad_labels': int(blk[native.EVAL_CONF_BAD_LABELS]), 'scores': {}}
+    for m, name in enumerate(scores):
+        base = native.EVAL_CONF_APPLY_SCORES + m * per
+        nv = int(blk[base])
+        entry = {'n': nv, 'bad_rows': int(blk[base + 1]), 'levels': {}}
+        for a, alpha in enumerate(alphas):
+            at = base + 16 + 32 * a
+            q = float(thresholds[m, 0, a])
+            lv = {'coverage': ratio(blk[at + 26], nv)}
+            if name in CONFORMAL_CLASS_SCORES:
+                hist, by_size, by_class = blk[at:at + C + 1], blk[at + 9:at + 9 + C + 1], blk[at + 18:at + 18 + C]
+                lv.update(mean_set_size=ratio(int((np.arange(C + 1) * hist).sum()), nv), size_histogram=[int(v) for v in hist],
+                          coverage_by_class=[ratio(by_class[c], blk[base + 8 + c]) for c in range(C)],
+                          coverage_by_size=[ratio(by_size[k], hist[k]) for k in range(C + 1)], empty_rate=ratio(hist[0], nv),
+                          singleton_rate=ratio(hist[1], nv), singleton_accuracy=ratio(by_size[1], hist[1]))
+            elif name in ('kan_abs', 'mu_abs'):
+                lv.update(mean_width=2.0 * q, infinite=math.isinf(q))
+            elif name == 'mu_scaled':
+                lv.update(mean_width=2.0 * q * ratio(f[base + 2], nv), infinite=math.isinf(q))
+            entry['levels'][alpha] = lv
+        res['scores'][name] = entry
+    return res
 
 
 # ---- selective prediction: restatement and summaries ---------------------------------------------------------------------------

@@ -133,6 +133,10 @@ SIGNATURES = {
     'rovit_density_score': (_i, [_vp, _vp]),
     'rovit_ood_metrics_workspace_bytes': (_sz, [_i, _i]),
     'rovit_ood_metrics': (_i, [_vp, _vp]),
+    'rovit_eval_conformal_workspace_bytes': (_sz, [_i, _i, _i, _i]),
+    'rovit_eval_conformal': (_i, [_vp, _vp]),
+    'rovit_eval_conformal_apply_workspace_bytes': (_sz, [_i, _i]),
+    'rovit_eval_conformal_apply': (_i, [_vp, _vp]),
     'rovit_augment_batch': (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, C.c_ulonglong, C.c_ulonglong, _vp, _i, _i, _vp]),
 }
 
@@ -323,6 +327,34 @@ def density_offsets(E: int, C: int) -> dict:
     mean = means + C * E
     scatter = mean + E
     return {'means': means, 'mean': mean, 'scatter': scatter, 'words': scatter + E * E}
+
+
+# rovit_eval_conformal / rovit_eval_conformal_apply: limits, score kinds, the Philox stream word and the result blocks' layouts (the
+# ROVIT_EVAL_CONF_* names of include/rovit_hip.h)
+EVAL_CONF_MAX_SCORES, EVAL_CONF_MAX_LEVELS, EVAL_CONF_MAX_DEN, EVAL_CONF_STREAM = 8, 8, 1 << 20, 0x436F6E66
+EVAL_CONF_LAC, EVAL_CONF_APS, EVAL_CONF_RAPS, EVAL_CONF_KAN_ABS, EVAL_CONF_MU_ABS, EVAL_CONF_MU_SCALED, EVAL_CONF_COLUMN = range(7)
+EVAL_CONF_N, EVAL_CONF_BAD_LABELS, EVAL_CONF_N_LABELLED, EVAL_CONF_BAD_ROWS, EVAL_CONF_ENTRIES, EVAL_CONF_ENTRY_WORDS = 0, 1, 2, 8, 16, 6
+EVAL_CONF_APPLY_SCORES = 8
+
+
+class EvalConf(C.Structure):
+    """``rovit_eval_conf`` of include/rovit_hip.h, field for field."""
+    _fields_ = [('n', _i), ('num_classes', _i), ('num_scores', _i), ('num_levels', _i), ('class_conditional', _i), ('randomized', _i),
+                ('raps_k', _i), ('max_workgroups', _i), ('raps_lambda', _f), ('row_offset', C.c_uint), ('seed', C.c_ulonglong),
+                ('score_kind', _i * EVAL_CONF_MAX_SCORES), ('alpha_num', C.c_uint * EVAL_CONF_MAX_LEVELS),
+                ('alpha_den', C.c_uint * EVAL_CONF_MAX_LEVELS), ('score_column', _vp * EVAL_CONF_MAX_SCORES),
+                ('probs', _vp), ('label', _vp), ('sev_pred', _vp), ('sev_true', _vp), ('uncertainty', _vp), ('mu', _vp), ('thresholds', _vp),
+                ('workspace', _vp), ('workspace_bytes', _sz), ('result', _vp), ('scores_out', _vp), ('u_out', _vp), ('member_out', _vp)]
+
+
+def eval_conformal_words(M: int, G: int, A: int) -> int:
+    """ROVIT_EVAL_CONF_WORDS(M, G, A): entry e = (m G + g) A + a sits at EVAL_CONF_ENTRIES + 6 e."""
+    return EVAL_CONF_ENTRIES + EVAL_CONF_ENTRY_WORDS * M * G * A
+
+
+def eval_conformal_apply_words(M: int, A: int) -> int:
+    """ROVIT_EVAL_CONF_APPLY_WORDS(M, A): score m sits at EVAL_CONF_APPLY_SCORES + m (16 + 32 A), its level a at + 16 + 32 a."""
+    return EVAL_CONF_APPLY_SCORES + M * (16 + 32 * A)
 
 
 class AugmentConfigC(C.Structure):
