@@ -1051,6 +1051,74 @@ int rovit_eval_conformal(const rovit_eval_conf* p, rovit_stream_t stream);
 size_t rovit_eval_conformal_apply_workspace_bytes(int n, int num_scores);
 int rovit_eval_conformal_apply(const rovit_eval_conf* p, rovit_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Nearest neighbours in feature space (neighbors.hip): the k nearest recorded rows r_j, j in [0, n), of every query row q_i, with no
+ * (batch, n) matrix in memory; the neighbour-weighted vote on top.  Rows are fp32 (n, embed) row-major.
+ *   ROVIT_KNN_L2      d(q, r) = max(0, (|q|^2 + |r|^2) - 2 q.r)
+ *   ROVIT_KNN_COSINE  d(q, r) = max(0, 1 - q^.r^), x^ = x / sqrt(|x|^2) element by element (IEEE sqrt and division)
+ * Every term is fp32; q.r and the squared norms are fma chains in ascending feature index from 0 (q.r on v_mfma_f32_32x32x2_f32, whose
+ * result is that chain); the other operations are single fp32 operations in the order written.  d is a function of the two rows alone.
+ * A recorded row is valid when every feature and its squared norm are finite and, with _COSINE, the squared norm is positive; other rows
+ * never are neighbours.  A query row that is not valid in the same sense gets index -1 and distance +inf in every slot.  A pair whose
+ * fp32 distance is not finite (with _L2, norms so large that |q|^2 + |r|^2 or 2 q.r overflows fp32: above about 1.7e38) is no candidate.
+ * Order: the 64-bit key (bits(d) << 32) | j; d >= 0, so the keys order as unsigned integers and keys of distinct rows are distinct.  The
+ * k smallest keys are the answer, ascending: ties in distance go to the lower index.  Fewer valid rows than k: the remaining slots hold
+ * index -1 and distance +inf.  exclude (batch) int32 or NULL: per query one row index that is left out (any value outside [0, n): none).
+ *
+ * rovit_knn_build: one launch, a thread per row: norms[j] = |r_j|^2, valid[j] = 0 / 1, with _COSINE normalized[j] = r^_j (zeros for a
+ * row that is not valid; with _L2 the pointer is NULL), result = ROVIT_KNN_WORDS int64 words [ROVIT_KNN_N] [_N_VALID] [_BAD_ROWS].
+ * rovit_knn_search: rows = the recorded rows with _L2, the normalized copy with _COSINE.  Three kernels: the queries' norms and flags; the
+ * search over (query tiles of ROVIT_KNN_QUERY_TILE rows) x (reference splits), every split leaving its smallest keys per query in the
+ * workspace; the merge, which takes the k smallest keys per query and writes
+ *   distances (batch, k) fp32, indices (batch, k) int32; with ref_labels: labels (batch, k) int32 (-1 in an empty slot); with
+ *   ref_severity: severities (batch, k) fp32 (NaN in an empty slot) and severity (batch) = sum w_j s_j / sum w_j;
+ *   kth_distance (batch): the distance in the last valid slot; mean_distance (batch): the mean over the valid slots (both +inf with none);
+ *   with ref_labels and num_classes = C >= 1: class_probs (batch, C) = sum w_j [y_j = c] / sum w_j (labels outside [0, C) carry no vote)
+ *   and cls (batch) = the first argmax of the fp64 sums (-1 without a valid slot).
+ *   w_j = exp(-(d_j - d_1) / temperature) over the valid slots, everything in fp64 in slot order, rounded to fp32 once.
+ * Only integer compares decide membership, work items are walked with a stride of the grid, no floating-point atomic: every output is
+ * bit-identical from run to run, for every grid (max_workgroups > 0 caps it) and for every number of reference splits (a function of
+ * batch and n alone).  workspace: rovit_knn_workspace_bytes(batch, n, embed, k) bytes, 16-byte aligned (0 outside the limits).
+ * Limits: embed a multiple of 32 in 32..256, 1 <= n <= ROVIT_KAN_STATS_MAX_ROWS, batch >= 1, 1 <= k <= ROVIT_KNN_MAX_K,
+ * 0 <= num_classes <= ROVIT_KNN_MAX_CLASSES, temperature > 0; queries, rows and the normalized copy 16-byte aligned.  A bad descriptor is
+ * refused before any launch.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define ROVIT_KNN_MAX_K 32
+#define ROVIT_KNN_MAX_CLASSES 1024
+#define ROVIT_KNN_QUERY_TILE 64
+enum { ROVIT_KNN_L2 = 0, ROVIT_KNN_COSINE = 1 };
+enum { ROVIT_KNN_N = 0, ROVIT_KNN_N_VALID = 1, ROVIT_KNN_BAD_ROWS = 2, ROVIT_KNN_WORDS = 4 };
+typedef struct rovit_knn_index {
+  int n, embed, metric, max_workgroups;
+  const float* features;             /* (n, embed) */
+  float* norms;                      /* (n) */
+  int* valid;                        /* (n) */
+  float* normalized;                 /* (n, embed) with ROVIT_KNN_COSINE, else NULL */
+  void* result;                      /* ROVIT_KNN_WORDS 8-byte words */
+} rovit_knn_index;
+typedef struct rovit_knn_query {
+  int batch, n, embed, k, metric, num_classes, max_workgroups, reserved;
+  double temperature;
+  const float* queries;              /* (batch, embed) */
+  const float* rows;                 /* (n, embed): the recorded rows (_L2) or their normalized copy (_COSINE) */
+  const float* norms;                /* (n) */
+  const int* valid;                  /* (n) */
+  const int* exclude;                /* (batch) or NULL */
+  const int* ref_labels;             /* (n) or NULL */
+  const float* ref_severity;         /* (n) or NULL */
+  void* workspace;
+  size_t workspace_bytes;
+  float* distances; int* indices;    /* (batch, k) each */
+  int* labels; float* severities;    /* (batch, k) each; with ref_labels / ref_severity */
+  float* class_probs;                /* (batch, num_classes); with ref_labels and num_classes >= 1 */
+  int* cls;                          /* (batch); with class_probs */
+  float* severity;                   /* (batch); with ref_severity */
+  float* kth_distance; float* mean_distance;   /* (batch) each */
+} rovit_knn_query;
+size_t rovit_knn_workspace_bytes(int batch, int n, int embed, int k);
+int rovit_knn_build(const rovit_knn_index* p, rovit_stream_t stream);
+int rovit_knn_search(const rovit_knn_query* p, rovit_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

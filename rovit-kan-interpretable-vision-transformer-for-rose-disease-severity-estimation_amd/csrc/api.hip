@@ -41,6 +41,8 @@ void rovit_set_error(const char* fmt, ...) {
 // tests/test_evaluation_cpu.py and tests/test_mc_dropout_cpu.py pin 440.)
 // (rovit_eval_conformal_workspace_bytes, rovit_eval_conformal, rovit_eval_conformal_apply_workspace_bytes and rovit_eval_conformal_apply
 // were added at 440 the same way: split conformal prediction on the evaluation record, conformal.hip.)
+// (rovit_knn_workspace_bytes, rovit_knn_build and rovit_knn_search were added at 440 the same way: nearest neighbours in feature space,
+// neighbors.hip.  The number stays for the reason given above: no argument list changed and two test files pin 440.)
 extern "C" int rovit_version(void) { return 440; }
 extern "C" const char* rovit_last_error_string(void) { return g_err; }
 

@@ -13,7 +13,11 @@ Mahalanobis and relative Mahalanobis distance as extra columns (two more scores 
 scores the test set against an out-of-distribution loader: AUROC, AUPR and FPR at 95 % TPR of every uncertainty score.
 ``fit_conformal(val_loader)`` fits split-conformal thresholds on another split (``EvalAccumulator.conformal``);
 ``evaluate(conformal=cp)`` reports the coverage and size of the label sets and the coverage and width of the severity intervals on the
-test set (``Conformal.evaluate``)."""
+test set (``Conformal.evaluate``).
+``fit_index(train_loader)`` records the training features in a ``rovit_hip.neighbors.FeatureIndex``; ``evaluate(index=fi, knn_k=10)``
+records each row's distance to its k-th nearest training feature as the extra column ``knn_distance`` (one more score of the selective
+card) and adds ``metrics['knn']``: how well the neighbour-weighted vote alone classifies and estimates severity, and how often it agrees
+with the classification head; ``evaluate_ood(..., index=fi)`` adds the ``'knn'`` card."""
 from pathlib import Path
 from typing import Dict
 
@@ -37,21 +41,32 @@ class Evaluator:
         self.calibration = None
         self.density = None
         self.conformal = None
+        self.index = None
+        self._knn_tally = None
 
     MC_COLUMNS = ('predictive_entropy_mc', 'mutual_information', 'epistemic_var', 'uncertainty_std')
 
     DENSITY_COLUMNS = ('mahalanobis', 'relative_mahalanobis')
+    KNN_COLUMN = 'knn_distance'
     OOD_LEVEL = 0.95
 
-    def collect(self, selective: bool = False, mc_samples: int = 0, mc_seed: int = 0, record_mu: bool = False, density=None) -> EvalAccumulator:
+    def collect(self, selective: bool = False, mc_samples: int = 0, mc_seed: int = 0, record_mu: bool = False, density=None, index=None,
+                knn_k: int = 10) -> EvalAccumulator:
         """The collection loop alone: one forward and one record launch per batch, nothing copied to the host.  ``selective`` (or
         ``record_mu``) also records the uncertainty head's ``mu`` as an extra column when the model returns one; ``mc_samples = T > 0``
         adds the MC-dropout columns of ``model.predict_mc(images, num_samples=T, seed=mc_seed, offset=batch index)``, a SECOND backbone
         pass per batch."""
         if mc_samples and not selective:
             raise RovitHipError('Evaluator: mc_samples records columns for the selective score card; pass selective=True with it')
-        acc = self.accumulator = self._collect(self.test_loader, selective, mc_samples, mc_seed, record_mu, density)
+        acc = self.accumulator = self._collect(self.test_loader, selective, mc_samples, mc_seed, record_mu, density, index, knn_k)
         return acc
+
+    def fit_index(self, loader, metric: str = 'cosine'):
+        """Record the backbone features of another split, normally the training loader, with their class labels and severities in a
+        ``FeatureIndex`` (``RoViTKAN.fit_feature_index``): one backbone pass and one build launch, nothing copied to the host.  The index
+        is returned and kept on ``self.index``; pass it to ``evaluate(index=...)`` or ``evaluate_ood(..., index=...)``."""
+        self.index = self.model.fit_feature_index(loader, metric=metric)
+        return self.index
 
     def fit_density(self, loader, shrinkage: float = 1e-3):
         """Fit the feature-space density (``RoViTKAN.fit_feature_density``) on another split, normally the training loader: one backbone
@@ -74,18 +89,20 @@ class Evaluator:
         self.conformal = self._collect(loader, False, 0, 0, True).conformal(**kw)
         return self.conformal
 
-    def _collect(self, loader, selective: bool, mc_samples: int, mc_seed: int, record_mu: bool, density=None) -> EvalAccumulator:
+    def _collect(self, loader, selective: bool, mc_samples: int, mc_seed: int, record_mu: bool, density=None, index=None,
+                 knn_k: int = 10) -> EvalAccumulator:
         acc = EvalAccumulator(len(self.config.data.class_names))
+        self._knn_tally = [] if index is not None else None
         self.model.eval()
         with torch.no_grad():
-            for index, (images, class_labels, severity_labels) in enumerate(loader):
+            for batch_index, (images, class_labels, severity_labels) in enumerate(loader):
                 images = images.to(self.device)
                 outputs = self.model(images)
                 extra = {}
                 if (selective or record_mu) and outputs.get('mu') is not None:
                     extra['mu'] = outputs['mu']
                 if selective and mc_samples:
-                    mc = self.model.predict_mc(images, num_samples=mc_samples, seed=mc_seed, offset=index)
+                    mc = self.model.predict_mc(images, num_samples=mc_samples, seed=mc_seed, offset=batch_index)
                     extra['predictive_entropy_mc'], extra['mutual_information'] = mc['predictive_entropy'], mc['mutual_information']
                     if 'epistemic_var' in mc:                 # from curriculum stage 3
                         extra['epistemic_var'], extra['uncertainty_std'] = mc['epistemic_var'], mc['uncertainty_std']
@@ -93,11 +110,42 @@ class Evaluator:
                     d = density.score(outputs['features'])
                     for k in self.DENSITY_COLUMNS:
                         extra[k] = d[k]
+                if index is not None:
+                    nn = index.search(outputs['features'], k=knn_k)
+                    extra[self.KNN_COLUMN] = nn['kth_distance']
+                    self._knn_tally.append(self._knn_row(nn, outputs, class_labels, severity_labels))
                 acc.update(outputs, class_labels, severity_labels, extra=extra or None)
         return acc
 
+    @staticmethod
+    def _knn_row(nn: Dict, outputs: Dict, class_labels, severity_labels) -> torch.Tensor:
+        """One batch's tallies of the neighbour vote as a (4,) fp64 tensor on the features' device, over the rows that VOTED (a finite
+        ``kth_distance``: at least one neighbour; a bad query row, or an index without a valid row, has none): such rows, those whose
+        vote equals the label, the sum of |vote severity - label severity|, those whose vote equals the classification head's argmax.
+        Nothing is copied to the host."""
+        dev = nn['kth_distance'].device
+        voted = torch.isfinite(nn['kth_distance'])
+        zero = torch.zeros((), dtype=torch.float64, device=dev)
+        hit = agree = err = zero
+        if 'class' in nn:
+            vote = nn['class'].to(torch.int64)
+            hit = (voted & (vote == class_labels.to(dev).reshape(-1).to(torch.int64))).sum().to(torch.float64)
+            agree = (voted & (vote == outputs['cls_logits'].argmax(dim=1))).sum().to(torch.float64)
+        if 'severity' in nn:
+            diff = (nn['severity'].double() - severity_labels.to(dev).reshape(-1).double()).abs()
+            err = torch.where(voted, diff, torch.zeros_like(diff)).sum()
+        return torch.stack([voted.sum().to(torch.float64), hit, err, agree])
+
+    def _knn_card(self, index, knn_k: int) -> Dict:
+        """``metrics['knn']`` from the batches' tallies: one device-to-host copy of four numbers.  Every ratio is over the rows that
+        voted (see ``_knn_row``); with none, the three figures are None."""
+        rows, hit, err, agree = torch.stack(self._knn_tally).sum(dim=0).cpu().tolist()
+        voted = bool(index.has_labels) and index.num_classes is not None and rows > 0
+        return {'k': knn_k, 'accuracy': 100.0 * hit / rows if voted else None,
+                'severity_mae': err / rows if index.has_severity and rows > 0 else None, 'agreement': agree / rows if voted else None}
+
     def evaluate(self, return_arrays: bool = False, bootstrap: int = 0, bootstrap_seed: int = 0, selective: bool = False,
-                 mc_samples: int = 0, mc_seed: int = 0, calibration=None, density=None, conformal=None):
+                 mc_samples: int = 0, mc_seed: int = 0, calibration=None, density=None, conformal=None, index=None, knn_k: int = 10):
         """``selective=True`` adds ``metrics['selective']`` (``EvalAccumulator.selective`` with 20 coverages: the built-in scores, and
         with ``mc_samples = T > 0`` the MC-dropout scores predictive_entropy_mc and mutual_information, from curriculum stage 3 also
         epistemic_var and uncertainty_std) and a "Selective prediction" section in the table and the file.  The MC columns cost a
@@ -116,10 +164,17 @@ class Evaluator:
 
         ``conformal`` (a ``Conformal``, normally ``fit_conformal(val_loader)``) adds ``metrics['conformal']``, what
         ``Conformal.evaluate`` returns for the test rows (one more device-to-host copy), and a "Conformal prediction" section in the
-        table and the file."""
+        table and the file.
+
+        ``index`` (a built ``FeatureIndex``, normally ``fit_index(train_loader)``) records ``knn_distance``, the distance of every row
+        to its ``knn_k``-th nearest recorded feature, as an extra column (one more search per batch; with ``selective=True`` one more
+        score of the card), and adds ``metrics['knn']`` = ``{'k', 'accuracy', 'severity_mae', 'agreement'}``: accuracy (per cent) and
+        severity MAE of the neighbour-weighted vote alone, and the share of rows where the vote and the classification head agree, all
+        three over the rows that have at least one neighbour; a "Nearest neighbours" section goes into the table and the file."""
         print(f'\n{RULE}\nRunning Evaluation on Test Set\n{RULE}\n')
         names = list(self.config.data.class_names)
-        acc = self.collect(selective, mc_samples, mc_seed, record_mu=calibration is not None or conformal is not None, density=density)
+        acc = self.collect(selective, mc_samples, mc_seed, record_mu=calibration is not None or conformal is not None, density=density,
+                           index=index, knn_k=knn_k)
         ci = acc.bootstrap(bootstrap, seed=bootstrap_seed) if bootstrap else None          # brings the point block along in its one copy
         m = acc.compute()                                   # the loop's one synchronisation
         metrics = {k: m[k] for k in ('accuracy', 'macro_f1', 'weighted_f1', 'mae', 'spearman_rho', 'spearman', 'brier_score', 'ece')}
@@ -132,7 +187,7 @@ class Evaluator:
             metrics['confidence_intervals'] = ci
         if selective:
             have = acc._extra_names or ()
-            scores = ['confidence', 'entropy'] + (['sigma'] if acc._has_uncertainty else []) + [c for c in self.MC_COLUMNS + self.DENSITY_COLUMNS if c in have]
+            scores = ['confidence', 'entropy'] + (['sigma'] if acc._has_uncertainty else []) + [c for c in self.MC_COLUMNS + self.DENSITY_COLUMNS + (self.KNN_COLUMN,) if c in have]
             risks = ['error', 'abs_err'] + (['mu_abs_err'] if 'mu' in have else [])
             metrics['selective'] = acc.selective(scores=scores, risks=risks)
         if calibration is not None:
@@ -143,11 +198,13 @@ class Evaluator:
                 metrics['calibration']['selective'] = applied.selective(scores=scores, risks=risks)
         if conformal is not None:
             metrics['conformal'] = conformal.evaluate(acc)
+        if index is not None:
+            metrics['knn'] = self._knn_card(index, knn_k)
         self._print_results(metrics)
         self._save_results(metrics)
         return (metrics, acc.arrays()) if return_arrays else metrics
 
-    def _ood_columns(self, loader, density) -> Dict[str, torch.Tensor]:
+    def _ood_columns(self, loader, density, index=None, knn_k: int = 10) -> Dict[str, torch.Tensor]:
         """The anomaly scores of every image of a loader as device columns: nothing is copied to the host."""
         cols: Dict[str, list] = {}
         self.model.eval()
@@ -164,18 +221,21 @@ class Evaluator:
                 if density is not None:
                     d = density.score(out['features'])
                     row.update({k: d[k] for k in self.DENSITY_COLUMNS})
+                if index is not None:
+                    row['knn'] = index.search(out['features'], k=knn_k)['kth_distance']
                 for k, v in row.items():
                     cols.setdefault(k, []).append(v)
         return {k: torch.cat(v) for k, v in cols.items()}
 
-    def evaluate_ood(self, ood_loader, density=None) -> Dict[str, Dict]:
+    def evaluate_ood(self, ood_loader, density=None, index=None, knn_k: int = 10) -> Dict[str, Dict]:
         """Extension (not in the reference): how well each uncertainty score tells the test set (in-distribution) from ``ood_loader``
         (out-of-distribution; batches of images, or tuples whose first element is the images).  One ``rovit_hip.density.ood_metrics``
         card per score (AUROC, AUPR both ways, FPR at 95 % TPR; one device-to-host copy each): ``max_prob`` = 1 - max p, ``entropy``,
         ``energy`` = -logsumexp, ``sigma`` when the model returns log_var, and with a fitted ``density`` ``mahalanobis`` and
-        ``relative_mahalanobis``.  Printed as a table; higher = more anomalous for every score."""
+        ``relative_mahalanobis``, and with a built ``index`` (a ``FeatureIndex``) ``knn``, the distance to the ``knn_k``-th nearest
+        recorded feature (Sun et al. 2022).  Printed as a table; higher = more anomalous for every score."""
         from rovit_hip.density import ood_metrics
-        inside, outside = self._ood_columns(self.test_loader, density), self._ood_columns(ood_loader, density)
+        inside, outside = self._ood_columns(self.test_loader, density, index, knn_k), self._ood_columns(ood_loader, density, index, knn_k)
         cards = {k: ood_metrics(inside[k], outside[k], tpr_levels=(self.OOD_LEVEL,)) for k in inside if k in outside}
         lines = ['', 'Out-of-distribution detection:', f"{'Score':<24}{'AUROC':>10}{'AUPR-out':>10}{'AUPR-in':>10}{'FPR@95%TPR':>12}", '-' * 66]
         for k, c in cards.items():
@@ -258,6 +318,16 @@ class Evaluator:
                              f"{e['curve'][at[0]]:>10.4f}{e['curve'][at[1]]:>10.4f}")
         return lines + ['']
 
+    @staticmethod
+    def _knn_lines(metrics: Dict):
+        """The neighbour vote beside the heads: its accuracy and severity MAE, and its agreement with the classification head."""
+        card = metrics.get('knn')
+        if card is None:
+            return []
+        num = lambda v, spec: 'n/a' if v is None else format(v, spec)
+        return [f"Nearest neighbours (k = {card['k']}):", f"{'Vote accuracy:':<22}{num(card['accuracy'], '.2f')}%",
+                f"{'Vote severity MAE:':<22}{num(card['severity_mae'], '.4f')}", f"{'Agreement with head:':<22}{num(card['agreement'], '.4f')}", '']
+
     def _print_results(self, metrics: Dict) -> None:
         print('\n'.join(['', RULE, 'Evaluation Results', RULE] + self._summary(metrics, 'Spearman rho:') + [RULE, '']))
         if 'selective' in metrics:
@@ -266,6 +336,8 @@ class Evaluator:
             print('\n'.join(self._calibration_lines(metrics)))
         if 'conformal' in metrics:
             print('\n'.join(self._conformal_lines(metrics)))
+        if 'knn' in metrics:
+            print('\n'.join(self._knn_lines(metrics)))
         print('Per-Class Metrics:')
         print(f"{'Class':<20} {'Precision':<12} {'Recall':<12} {'F1-Score':<12} {'Support':<10}")
         print('-' * 70)
@@ -283,7 +355,7 @@ class Evaluator:
         for name, c in metrics['per_class'].items():
             lines += [f'{name}:', f"  Precision: {c['precision']:.2f}%", f"  Recall:    {c['recall']:.2f}%", f"  F1-Score:  {c['f1']:.2f}%",
                       f"  Support:   {c['support']}", '']
-        lines += self._selective_lines(metrics) + self._calibration_lines(metrics) + self._conformal_lines(metrics)
+        lines += self._selective_lines(metrics) + self._calibration_lines(metrics) + self._conformal_lines(metrics) + self._knn_lines(metrics)
         path = results_dir / 'evaluation_results.txt'
         path.write_text('\n'.join(lines) + '\n', encoding='utf-8')
         print(f'Results saved to {path}')

@@ -277,6 +277,24 @@ class RoViTKAN(nn.Module):
             self.train(was_training)
         return density.score(out['features'], out['cls_logits'])
 
+    def fit_feature_index(self, x_or_loader, labels=None, severity=None, metric: str = 'cosine', chunk: int = 256):
+        """Extension (not in the reference): a built ``rovit_hip.neighbors.FeatureIndex`` of this model's backbone features over images
+        (a (B,3,224,224) tensor with optional ``labels`` and ``severity``, or an iterable of batches ``(images, class_labels,
+        severity_labels, ...)``): the rows a nearest-neighbour search answers from."""
+        from rovit_hip import neighbors
+        return neighbors.fit_model_index(self, x_or_loader, labels, severity, metric, chunk)
+
+    def nearest_examples(self, x: torch.Tensor, index, k: int = 5) -> Dict[str, torch.Tensor]:
+        """Extension (not in the reference): explanation by example.  One forward, then ``index.search(features, k)``: the ``k`` nearest
+        recorded rows of every image with their labels and severities, the neighbours' vote, and beside it the heads' own ``class``
+        under ``head_class`` and, from curriculum stage 2, ``ordinal_severity`` under ``head_ordinal_severity``."""
+        pred = self.predict(x)
+        out = dict(index.search(pred['features'], k=k))
+        out['head_class'] = pred['class']
+        if 'ordinal_severity' in pred:
+            out['head_ordinal_severity'] = pred['ordinal_severity']
+        return out
+
     def count_parameters(self) -> Dict[str, int]:
         def n(m):
             return sum(p.numel() for p in m.parameters() if p.requires_grad)

@@ -133,6 +133,9 @@ SIGNATURES = {
     'rovit_density_score': (_i, [_vp, _vp]),
     'rovit_ood_metrics_workspace_bytes': (_sz, [_i, _i]),
     'rovit_ood_metrics': (_i, [_vp, _vp]),
+    'rovit_knn_workspace_bytes': (_sz, [_i, _i, _i, _i]),
+    'rovit_knn_build': (_i, [_vp, _vp]),
+    'rovit_knn_search': (_i, [_vp, _vp]),
     'rovit_eval_conformal_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'rovit_eval_conformal': (_i, [_vp, _vp]),
     'rovit_eval_conformal_apply_workspace_bytes': (_sz, [_i, _i]),
@@ -327,6 +330,27 @@ def density_offsets(E: int, C: int) -> dict:
     mean = means + C * E
     scatter = mean + E
     return {'means': means, 'mean': mean, 'scatter': scatter, 'words': scatter + E * E}
+
+
+# rovit_knn_build / rovit_knn_search: limits, metrics and the build's result block (the ROVIT_KNN_* names of include/rovit_hip.h)
+KNN_MAX_K, KNN_MAX_CLASSES, KNN_QUERY_TILE = 32, 1024, 64
+KNN_L2, KNN_COSINE = 0, 1
+KNN_N, KNN_N_VALID, KNN_BAD_ROWS, KNN_WORDS = 0, 1, 2, 4
+
+
+class KnnIndex(C.Structure):
+    """``rovit_knn_index`` of include/rovit_hip.h, field for field."""
+    _fields_ = [('n', _i), ('embed', _i), ('metric', _i), ('max_workgroups', _i), ('features', _vp), ('norms', _vp), ('valid', _vp),
+                ('normalized', _vp), ('result', _vp)]
+
+
+class KnnQuery(C.Structure):
+    """``rovit_knn_query`` of include/rovit_hip.h, field for field."""
+    _fields_ = [('batch', _i), ('n', _i), ('embed', _i), ('k', _i), ('metric', _i), ('num_classes', _i), ('max_workgroups', _i),
+                ('reserved', _i), ('temperature', C.c_double), ('queries', _vp), ('rows', _vp), ('norms', _vp), ('valid', _vp),
+                ('exclude', _vp), ('ref_labels', _vp), ('ref_severity', _vp), ('workspace', _vp), ('workspace_bytes', _sz),
+                ('distances', _vp), ('indices', _vp), ('labels', _vp), ('severities', _vp), ('class_probs', _vp), ('cls', _vp),
+                ('severity', _vp), ('kth_distance', _vp), ('mean_distance', _vp)]
 
 
 # rovit_eval_conformal / rovit_eval_conformal_apply: limits, score kinds, the Philox stream word and the result blocks' layouts (the
