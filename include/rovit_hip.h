@@ -392,6 +392,20 @@ int rovit_block_tail_fwd(const void* o, const void* wstream, const float* bp, co
  * dXb = bf16(float(dY) + the LayerNorm-backward term), and no fp32 dX is read or written. */
 int rovit_mlp_fused_bwd(const void* dY, const void* wstream_bwd, const void* dact, void* dpre, const void* xhat2, const float* rstd2,
                         float* dX, void* dXb, int M, rovit_stream_t stream);
+/* The row-local part of the backward between two attention backwards in ONE launch (what rovit_vit_backward runs on the one-launch MLP
+ * path): the qkv dgrad + norm1 backward of block i in front of the MLP dgrad chain of block i-1,
+ *   xout (M,192) = bf16(float(xmid_in) + rstd1 (g - mean(g) - xhat1 mean(g xhat1))),  g = bf16(dqkv (M,576) WqkvT^T)
+ *                  -- rovit_gemm_ln_bwd(dqkv, K = 576, ..., dXb_in = xmid_in, dXb = xout): same MFMA chain, same staged row arithmetic
+ *   then rovit_mlp_fused_bwd(dY = xout, ..., dX = NULL, dXb) of block i-1, on the rows just computed: they stay in LDS as the B
+ *   fragments of the fc2 dgrad and as the residual rows of the norm2 backward, so dpre and dXb are bit-identical to that call's;
+ *   xout is written (the fc2 weight gradient reads it) and never read by the launch.
+ * wstream_bwd: rovit_mlp_prepare_stream_bwd(w2T (768,192), w1T folded (192,768), wqkvT_next = block i's bf16 TRANSPOSED qkv weight
+ * (192,576), norm1 affine folded in, wstream): rovit_mlp_prepare_stream's dgrad image plus 18 entries of WqkvT fragments.
+ * Partial modes: dqkv == NULL = the MLP part alone (xout is then the INPUT dY; exactly rovit_mlp_fused_bwd); dact == NULL = the front
+ * part alone (dpre, xhat2, rstd2, dXb unused). */
+int rovit_mlp_prepare_stream_bwd(const void* w2T, const void* w1T, const void* wqkvT_next, void* wstream, rovit_stream_t stream);
+int rovit_block_bwd_fused(const void* dqkv, const void* xhat1, const float* rstd1, const void* xmid_in, void* xout, const void* wstream_bwd,
+                          const void* dact, void* dpre, const void* xhat2, const float* rstd2, void* dXb, int M, rovit_stream_t stream);
 /* dgrad through a Linear that follows a LayerNorm, fused with that LayerNorm's backward:
  * dxhat = dY W^T;  dX += rstd (dxhat - mean(dxhat) - xhat mean(dxhat xhat));  dXb = bf16(dX).
  * dXb_in != NULL (round 4): the incoming residual gradient as bf16 rows (M,192); then dXb = bf16(float(dXb_in) + that term) and the fp32

@@ -85,6 +85,13 @@ constexpr int TQKV = 9;                       // ring entries of the NEXT block'
 constexpr int TENTRIES = TPROJ + PENTRIES + TQKV;
 __host__ __device__ constexpr int tail_col(int ot, int row) { return 32 * (ot >> 1) + 8 * (row >> 2) + 4 * (ot & 1) + (row & 3); }
 constexpr int CSTR = 192 + 8;                 // staged output tile [ROWS][CSTR] bf16
+// FRONT (backward, round 5): the NEXT-higher block's qkv dgrad + norm1 backward runs IN FRONT of the MLP dgrad chain in the same launch
+// (rovit_block_bwd_fused).  Its K = 576 operand pair goes through the same ring: one front entry per k-step of 32 = the 12 output
+// tiles' WqkvT fragments (12 KB, lane (l15, lg) of piece ot = WqkvT[16 ot + l15][32 ks + 8 lg .. +7]) next to the waves' own
+// 16 x 32 dqkv pieces, which take the place of the gelu' pieces.  The 18 x 12 pieces sit behind the block-tail image.
+constexpr int FRONT_KS = 18;                  // k-steps of the qkv dgrad (K = 576)
+constexpr int FR_PIECES = 12;                 // weight pieces of a front entry
+constexpr int TFRONT = FRONT_KS * FR_PIECES / CH_PIECES;       // the front entries in units of a 24-piece image entry
 // NW waves per workgroup, 32 rows per wave.  NW = 8: one 256-row workgroup per CU.  NW = 4 (forward only): 128-row workgroups,
 // two per CU (76 KB each).  A backward slot also holds the workgroup's gelu' tile of the chunk (2 NW pieces).
 constexpr int slot_elems(int kind, int nw) { return CH_ELEMS + (kind ? 2 * nw * PIECE : 0); }
@@ -116,6 +123,12 @@ struct MlpArgs {
   bf16* xhat2;            // TAIL: norm2 output (M,192) kept for the backward (NULL: inference)
   float* rstd2;           // TAIL: (M)
   const bf16* gelu_table; // pipelined forward: the 32 KB table behind the two stream images
+  const bf16* fw;         // FRONT: the 18 front entries of the backward image (WqkvT fragments of the block above)
+  const bf16* fdq;        // FRONT: (M,576) dqkv of the block above
+  const bf16* fxhat;      // FRONT: (M,192) its xhat1
+  const float* frstd;     // FRONT: (M) its rstd1
+  const bf16* fxmid;      // FRONT: (M,192) its mid-block residual gradient
+  bf16* fxout;            // FRONT: (M,192) output: the gradient entering that block = this block's dY (xin is not read)
   float* X;               // (M,192) forward: residual stream; backward: dX; updated in place
   bf16* xhat;             // forward: next LayerNorm output or NULL; backward: xhat2 (input)
   float* rstd;            // forward: (M) output; backward: rstd2 (input)
@@ -159,8 +172,15 @@ __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :
 // Price: a weight fragment read from LDS serves one row tile instead of two (LDS reads x 2).  MEASURED (tools/ab_tail.sh, one box,
 // M = 50 432): 97.5 against 92.6 us for the training launch, 87.9 against 84.0 for inference -- bit-identical outputs, SLOWER: the
 // doubled fragment reads and the 16-wave barrier cost more than the occupancy gives.  Kept in the developer library (knob 18) only.
-template <int KIND, int MODE, int NW, bool STAG = false, bool PIPE = false, bool TAIL = false, int TPW = 2>
+// FRONT (backward, 8 waves): the qkv dgrad + norm1 backward of the block above in front of the chunk loop.  Each wave computes
+// dxhat1^T[192][its 32 rows] over 18 ring entries in the fc1-dgrad accumulators (one ascending-k chain per output tile, as
+// gemm_kdma_kernel sums), the tile is staged in LDS and a row pass (the arithmetic of gemm_kdma_kernel's EPI_LNBWD epilogue) writes the
+// bf16 gradient rows both to memory (the fc2 weight gradient reads them) and back into the staged tile, from where every wave takes
+// them as the B fragments of the fc2 dgrad.  Those fragments are also the residual input of the norm2 backward behind the loop:
+// the launch does not read xin.  g.mul == NULL: the front phase alone.
+template <int KIND, int MODE, int NW, bool STAG = false, bool PIPE = false, bool TAIL = false, int TPW = 2, bool FRONT = false>
 __global__ __launch_bounds__(NW * 64, TPW == 1 ? 4 : 2) void mlp_fused_kernel(const MlpArgs g) {
+  static_assert(!FRONT || (KIND == 1 && NW == 8 && !TAIL && TPW == 2), "the front phase belongs to the 8-wave backward");
   static_assert(TPW == 2 || (TPW == 1 && PIPE && TAIL && KIND == 0 && NW == 16), "one tile per wave: the 16-wave forward block tail");
   static_assert(!TAIL || PIPE || KIND == 1, "the forward block tail builds on the pipelined forward");
   constexpr int NBIAS = HID + D + (TAIL ? D + 3 * D : 0);       // floats behind the ring: b1, b2 [, proj bias, next block's qkv bias]
@@ -217,10 +237,12 @@ __global__ __launch_bounds__(NW * 64, TPW == 1 ? 4 : 2) void mlp_fused_kernel(co
     ((float4*)s_bias)[tid] = v;
   }
   bf16x8 xf[TPW][6];
+  if constexpr (!FRONT) {
 #pragma unroll
-  for (int i = 0; i < TPW; ++i)
+    for (int i = 0; i < TPW; ++i)
 #pragma unroll
-    for (int ks = 0; ks < 6; ++ks) xf[i][ks] = *(const bf16x8*)(g.xin + (size_t)mcl[i] * D + ks * 32 + lg * 8);
+      for (int ks = 0; ks < 6; ++ks) xf[i][ks] = *(const bf16x8*)(g.xin + (size_t)mcl[i] * D + ks * 32 + lg * 8);
+  }
   // buffer resources for the kept activations: rows >= M fall outside num_records and are dropped by the hardware
   __amdgpu_buffer_rsrc_t r_act, r_dact;
   // The kept activations are CHUNK-MAJOR, [24][rows][32] (32 hidden units = 64 bytes per row and chunk): the store instruction of a
@@ -253,6 +275,116 @@ __global__ __launch_bounds__(NW * 64, TPW == 1 ? 4 : 2) void mlp_fused_kernel(co
         a2[ot][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
       }
     }
+
+
+  if constexpr (FRONT) {
+    // ---- front phase: dxhat1^T = WqkvT x dqkv^T over 18 ring entries (DMA pieces per wave and entry: 2 weight + 2 own; no stores) ----
+    auto fdma = [&](int e, int slot) {
+      const bf16* src = g.fw + (size_t)e * (FR_PIECES * PIECE) + lane * 8;
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        // 12 pieces over 8 waves: pieces 8-11 are requested by two waves each (same bytes to the same place), so that every wave's count is 2
+        const int piece = q == 0 ? w : NW + (w & 3);
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + piece * PIECE),
+                                         (__attribute__((address_space(3))) void*)(lds + slot * SLOT + piece * PIECE), 16, 0, 0);
+      }
+#pragma unroll
+      for (int i = 0; i < 2; ++i)      // this wave's own dqkv pieces: lane (row l15, q = lg) <- dqkv[row][32 e + 8 q .. +7]
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(g.fdq + (size_t)mcl[i] * (3 * D) + e * 32 + lg * 8),
+                                         (__attribute__((address_space(3))) void*)(lds + slot * SLOT + (CH_PIECES + w + NW * i) * PIECE), 16, 0, 0);
+    };
+    fdma(0, 0);
+    fdma(1, 1);
+    int slot = 0;
+#pragma unroll 1
+    for (int e = 0; e < FRONT_KS; ++e) {
+      if (e < FRONT_KS - 1) wait_vm<4>(); else wait_vm<0>();      // entry e is in once only this wave's 4 pieces of entry e + 1 are outstanding
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+      if (e + 2 < FRONT_KS) fdma(e + 2, slot == 0 ? 2 : slot - 1);
+      const bf16* sb = lds + slot * SLOT + lane * 8;
+      const bf16x8 d0 = *(const bf16x8*)(sb + (CH_PIECES + w) * PIECE), d1 = *(const bf16x8*)(sb + (CH_PIECES + w + NW) * PIECE);
+#pragma unroll
+      for (int ot = 0; ot < 12; ++ot) {
+        const bf16x8 wq = *(const bf16x8*)(sb + ot * PIECE);
+        a2[ot][0] = mfma16(wq, d0, a2[ot][0]);
+        a2[ot][1] = mfma16(wq, d1, a2[ot][1]);
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      slot = slot == 2 ? 0 : slot + 1;
+    }
+    __builtin_amdgcn_s_barrier();                               // every wave has left the loop: the ring is free for the staged tile
+    asm volatile("" ::: "memory");
+    // ---- norm1 backward as a row pass over the staged tile (16 lanes per row, 8 passes of 32 rows) ----
+    constexpr int RP = 4 * NW;
+    const int c16 = tid & 15, prow = tid >> 4;
+    bf16x4 pa[4][3], pb[4][3], ha[4][3], hb[4][3];
+    float ra[4], rb[4];
+    auto ffetch = [&](int pass, bf16x4 (&ps)[3], bf16x4 (&hs)[3], float& rr) {
+      const int m = r0 + pass * RP + prow;
+      const int mc = m < g.M ? m : g.M - 1;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        ps[i] = ((const bf16x4*)(g.fxmid + (size_t)mc * D))[16 * i + c16];
+        hs[i] = ((const bf16x4*)(g.fxhat + (size_t)mc * D))[16 * i + c16];
+      }
+      rr = g.frstd[mc];
+    };
+#pragma unroll
+    for (int p = 0; p < 4; ++p) ffetch(p, pa[p], ha[p], ra[p]);
+    bf16* Cs = lds;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int ot = 0; ot < 12; ++ot) {
+        *(bf16x4*)(Cs + (16 * NW * i + 16 * w + l15) * CSTR + 16 * ot + 4 * lg) = pack4(a2[ot][i]);
+        a2[ot][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      }
+    barrier_lds();
+#pragma unroll
+    for (int p = 0; p < 4; ++p) ffetch(4 + p, pb[p], hb[p], rb[p]);
+    // xout = bf16(xmid + rstd1 (v - mean(v) - xhat1 mean(v xhat1))), v = the bf16-staged dgrad: all arithmetic first, stores last
+    auto ffinish = [&](int pass, const bf16x4 (&ps)[3], const bf16x4 (&hs)[3], float rr) {
+      const int row = pass * RP + prow;
+      const int m = r0 + row;
+      float v[12], h[12];
+      float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const bf16x4 t = *(const bf16x4*)(Cs + row * CSTR + 64 * i + 4 * c16);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { v[4 * i + e] = (float)t[e]; h[4 * i + e] = (float)hs[i][e]; s1 += v[4 * i + e]; s2 += v[4 * i + e] * h[4 * i + e]; }
+      }
+      const float c1 = wave_sum16(s1) * (1.f / 192.f), c2 = wave_sum16(s2) * (1.f / 192.f);
+      bf16x4 bq[3];
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        f32x4 x = {(float)ps[i][0], (float)ps[i][1], (float)ps[i][2], (float)ps[i][3]};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) x[e] += rr * (v[4 * i + e] - c1 - h[4 * i + e] * c2);
+        bq[i] = pack4(x);
+      }
+#pragma unroll
+      for (int i = 0; i < 3; ++i) *(bf16x4*)(Cs + row * CSTR + 64 * i + 4 * c16) = bq[i];       // in place: this lane's own elements
+      if (row < g.rpw && m < g.M) {
+        bf16x4* bp = (bf16x4*)(g.fxout + (size_t)m * D);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) bp[16 * i + c16] = bq[i];
+      }
+    };
+#pragma unroll
+    for (int p = 0; p < 4; ++p) ffinish(p, pa[p], ha[p], ra[p]);
+#pragma unroll
+    for (int p = 0; p < 4; ++p) ffinish(4 + p, pb[p], hb[p], rb[p]);
+    if (!g.mul) return;                                         // the front phase alone (wave-uniform)
+    barrier_lds();
+    // the rows this wave owns for the rest of the launch, as MFMA B fragments
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int ks = 0; ks < 6; ++ks) xf[i][ks] = *(const bf16x8*)(Cs + (16 * NW * i + 16 * w + l15) * CSTR + ks * 32 + lg * 8);
+    barrier_lds();                                              // the staged tile is consumed: the ring takes the MLP image
+  }
 
   const bf16* gtab = lds + REGION + 2 * NBIAS;       // PIPE: the GELU table (behind the biases)
   if constexpr (PIPE) {
@@ -864,6 +996,8 @@ __global__ __launch_bounds__(NW * 64, TPW == 1 ? 4 : 2) void mlp_fused_kernel(co
   float ra[4], rb[4];              // backward: rstd2
   auto fetch = [&](int pass, float4 (&xs)[3], bf16x4 (&hs)[3], float& rr) {
     const int mc = crow(pass);
+    if constexpr (FRONT) {               // the incoming gradient rows are on chip (xf): finish() takes them from the staged tile
+    } else
     if (KIND && !g.X) {                  // round 4: bf16 residual gradient -- the incoming gradient IS the launch's dY operand (row-major (M,192))
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
@@ -883,6 +1017,18 @@ __global__ __launch_bounds__(NW * 64, TPW == 1 ? 4 : 2) void mlp_fused_kernel(co
 #pragma unroll
   for (int p = 0; p < 4; ++p) fetch(p, xa[p], ha[p], ra[p]);
   bf16* Cs = lds;
+  // FRONT: the workgroup's rows go through LDS in two halves of 128 (row tile i of every wave), each as the staged dgrad next to the
+  // incoming gradient rows this launch's front phase produced (the waves' B fragments, as they stand: 16-byte runs of a row)
+  bf16* Xs = lds + 16 * NW * CSTR;
+  auto stage_half = [&](int i) {
+#pragma unroll
+    for (int ot = 0; ot < 12; ++ot) *(bf16x4*)(Cs + (16 * w + l15) * CSTR + 16 * ot + 4 * lg) = pack4(a2[ot][i]);
+#pragma unroll
+    for (int ks = 0; ks < 6; ++ks) *(bf16x8*)(Xs + (16 * w + l15) * CSTR + ks * 32 + lg * 8) = xf[i][ks];
+  };
+  if constexpr (FRONT) {
+    stage_half(0);
+  } else {
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -894,6 +1040,7 @@ __global__ __launch_bounds__(NW * 64, TPW == 1 ? 4 : 2) void mlp_fused_kernel(co
       }
       *(bf16x4*)(Cs + (16 * NW * i + 16 * w + l15) * CSTR + 16 * ot + 4 * lg) = pack4(v);
     }
+  }
   barrier_lds();
 #pragma unroll
   for (int p = 0; p < 4; ++p) fetch(4 + p, xb[p], hb[p], rb[p]);
@@ -903,12 +1050,17 @@ __global__ __launch_bounds__(NW * 64, TPW == 1 ? 4 : 2) void mlp_fused_kernel(co
     const int row = pass * RP + prow;
     const int m = r0 + row;
     float4* xp = (float4*)(g.X + (size_t)crow(pass) * D);
+    const int srow = FRONT ? row % (16 * NW) : row;           // row of the staged tile
     float v[12];
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-      const bf16x4 t = *(const bf16x4*)(Cs + row * CSTR + 64 * i + 4 * c16);
+      const bf16x4 t = *(const bf16x4*)(Cs + srow * CSTR + 64 * i + 4 * c16);
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[4 * i + e] = (float)t[e];
+      if constexpr (FRONT) {
+        const bf16x4 u = *(const bf16x4*)(Xs + srow * CSTR + 64 * i + 4 * c16);
+        xs[i] = make_float4((float)u[0], (float)u[1], (float)u[2], (float)u[3]);
+      }
     }
     if (KIND) {
       // dX += rstd (v - mean(v) - xhat mean(v xhat)); the affine is already folded into W1T (same arithmetic and summation
@@ -979,6 +1131,11 @@ __global__ __launch_bounds__(NW * 64, TPW == 1 ? 4 : 2) void mlp_fused_kernel(co
   };
 #pragma unroll
   for (int p = 0; p < 4; ++p) finish(p, xa[p], ha[p], ra[p]);
+  if constexpr (FRONT) {
+    barrier_lds();                                            // the first half is consumed
+    stage_half(1);
+    barrier_lds();
+  }
 #pragma unroll
   for (int p = 0; p < 4; ++p) finish(4 + p, xb[p], hb[p], rb[p]);
   }
@@ -994,7 +1151,10 @@ constexpr size_t NO_WP = ~(size_t)0;
 // (PENTRIES entries: entry j = fc1 fragments of chunk j | fc2 fragments of chunk j - PSKEW; the missing halves are zeros) and the
 // BLOCK-TAIL one (TENTRIES entries: TPROJ entries of proj-weight fragments, output tile ot = rows tail_col(ot, .) of the weight, then the
 // skewed image with the rows of the fc2 fragments permuted the same way; zeros when no proj weight is given).
-constexpr int STREAM_ENTRIES = NCHUNK + PENTRIES + TENTRIES;
+// Behind them, in a BACKWARD buffer: the front entries of rovit_block_bwd_fused (TFRONT image entries = 18 x 12 pieces of the WqkvT of
+// the block ABOVE, whose qkv dgrad runs in front of this block's MLP dgrad; zeros in a forward buffer or when there is no such block).
+constexpr int FRONT_ENTRY0 = NCHUNK + PENTRIES + TENTRIES;
+constexpr int STREAM_ENTRIES = FRONT_ENTRY0 + TFRONT;
 __global__ __launch_bounds__(256) void mlp_stream_prep_kernel(const MlpPrepArgs a) {
   const int blk = blockIdx.y;
   const char* q = a.base + a.blk0 + (size_t)blk * a.stride;
@@ -1002,12 +1162,18 @@ __global__ __launch_bounds__(256) void mlp_stream_prep_kernel(const MlpPrepArgs 
   const bf16* w2 = (const bf16*)(q + a.off_w2);
   bf16* out = (bf16*)(const_cast<char*>(q) + a.off_out);
   const int e = blockIdx.x * 256 + threadIdx.x;          // 16-byte element of the stream: STREAM_ENTRIES * 24 * 64
-  if (e >= STREAM_ENTRIES * CH_PIECES * 64) return;
+  if (e >= (a.bwd ? STREAM_ENTRIES : FRONT_ENTRY0) * CH_PIECES * 64) return;      // (a forward buffer has no front entries: nothing reads that part)
   const int lane = e & 63, piece = (e >> 6) % CH_PIECES, entry = e / (64 * CH_PIECES);
   const int l15 = lane & 15, lg = lane >> 4;
   bf16x8 v = {};
   const bf16* src = nullptr;
-  if (entry >= NCHUNK + PENTRIES) {                       // block-tail image
+  if (entry >= FRONT_ENTRY0) {                            // front entries (backward): piece ot of k-step ks = rows 16 ot .. +15 of WqkvT (192,576)
+    if (a.bwd && a.off_wq != NO_WP && (int)blockIdx.y < a.n_next) {
+      const int fp = (entry - FRONT_ENTRY0) * CH_PIECES + piece;
+      const int ks = fp / FR_PIECES, ot = fp - FR_PIECES * ks;
+      src = (const bf16*)(q + a.off_wq) + (size_t)(16 * ot + l15) * (3 * D) + 32 * ks + 8 * lg;
+    }
+  } else if (entry >= NCHUNK + PENTRIES) {                // block-tail image
     const int t = entry - (NCHUNK + PENTRIES);
     if (a.off_wp != NO_WP && a.bwd) {
       // backward block tail: NCHUNK plain entries whose second-GEMM (fc1 dgrad) rows are permuted by tail_col, then TPROJ entries of
@@ -1128,6 +1294,12 @@ extern "C" int rovit_mlp_prepare_stream_tail_bwd(const void* w2T, const void* w1
   return mlp_prepare_stream_impl(w2T, w1T, wprojT, wstream, stream, 1);
 }
 #endif
+// the dgrad image (w2T (768,192), w1T folded (192,768)) with the front entries of rovit_block_bwd_fused: wqkvT_next = the bf16 (192,576)
+// TRANSPOSED qkv weight, norm1 affine folded in, of the block whose qkv dgrad runs in front (the block above in the forward order)
+extern "C" int rovit_mlp_prepare_stream_bwd(const void* w2T, const void* w1T, const void* wqkvT_next, void* wstream, rovit_stream_t stream) {
+  ROVIT_CHECK_ARG(wqkvT_next && rovit_aligned16(wqkvT_next), ROVIT_ERR_NULL, "mlp_prepare_stream_bwd: wqkvT_next missing or misaligned");
+  return mlp_prepare_stream_impl(w2T, w1T, nullptr, wstream, stream, 1, wqkvT_next);
+}
 // ... with the block-tail image too (rovit_block_tail_fwd): wproj = the bf16 attention-output projection weight (192,192)
 // wqkv_next (may be NULL): the bf16 qkv weight (576,192) of the NEXT block with its norm1 affine folded in -- rovit_block_tail_fwd then
 // also writes that block's qkv projection
@@ -1298,6 +1470,37 @@ extern "C" int rovit_mlp_fused_bwd(const void* dY, const void* wstream_bwd, cons
   g.rpw = mlp_rpw(M);
   hipLaunchKernelGGL((mlp_fused_kernel<1, 1, 8>), dim3((M + g.rpw - 1) / g.rpw), dim3(512), lds_bytes(1, 8), (hipStream_t)stream, g);
   ROVIT_CHECK_LAUNCH("mlp_fused_kernel (backward)");
+  return ROVIT_OK;
+}
+
+// The row-local part of the backward between two attention backwards in ONE launch:
+//   xout (M,192) = bf16(xmid_in + LayerNorm-1-backward(dqkv WqkvT^T))           [rovit_gemm_ln_bwd, K = 576, of the block above]
+//   then rovit_mlp_fused_bwd with dY = xout, dX = NULL, of the block below, whose B fragments and norm2-backward residual rows are the
+//   bf16 rows just computed, taken from LDS: xout is written (the fc2 weight gradient reads it) and not read back.
+// wstream_bwd: rovit_mlp_prepare_stream_bwd's buffer.  Partial modes (block-range boundaries): dqkv == NULL runs the MLP part alone
+// (xout is then the INPUT dY: exactly rovit_mlp_fused_bwd), dact == NULL the front part alone.
+extern "C" int rovit_block_bwd_fused(const void* dqkv, const void* xhat1, const float* rstd1, const void* xmid_in, void* xout,
+                                     const void* wstream_bwd, const void* dact, void* dpre, const void* xhat2, const float* rstd2,
+                                     void* dXb, int M, rovit_stream_t stream) {
+  if (!dqkv) return rovit_mlp_fused_bwd(xout, wstream_bwd, dact, dpre, xhat2, rstd2, nullptr, dXb, M, stream);
+  ROVIT_CHECK_ARG(xhat1 && rstd1 && xmid_in && xout && wstream_bwd, ROVIT_ERR_NULL, "block_bwd_fused: null pointer");
+  ROVIT_CHECK_ARG(!dact || (dpre && xhat2 && rstd2 && dXb), ROVIT_ERR_NULL, "block_bwd_fused: null pointer in the MLP part");
+  ROVIT_CHECK_ARG(M > 0 && (size_t)M * HID * 2 < ((size_t)1 << 31), ROVIT_ERR_SHAPE, "block_bwd_fused: M = %d out of range", M);
+  ROVIT_CHECK_ARG(rovit_aligned16(dqkv) && rovit_aligned16(xhat1) && rovit_aligned16(xmid_in) && rovit_aligned16(xout) &&
+                      rovit_aligned16(wstream_bwd) && rovit_aligned16(dact) && rovit_aligned16(dpre) && rovit_aligned16(xhat2) &&
+                      rovit_aligned16(dXb),
+                  ROVIT_ERR_ALIGN, "block_bwd_fused: buffers must be 16-byte aligned");
+  MlpArgs g{};
+  g.fdq = (const bf16*)dqkv; g.fxhat = (const bf16*)xhat1; g.frstd = rstd1; g.fxmid = (const bf16*)xmid_in; g.fxout = (bf16*)xout;
+  g.wstream = (const bf16*)wstream_bwd; g.fw = g.wstream + (size_t)FRONT_ENTRY0 * CH_ELEMS;
+  g.act = (bf16*)dpre; g.mul = (const bf16*)dact; g.xhat = (bf16*)const_cast<void*>(xhat2); g.rstd = const_cast<float*>(rstd2);
+  g.xb = (bf16*)dXb; g.M = M;
+  ROVIT_CHECK_ARG(rovit_set_max_lds((const void*)mlp_fused_kernel<1, 1, 8, false, false, false, 2, true>, lds_bytes(1, 8)), ROVIT_ERR_LAUNCH,
+                  "block_bwd_fused: cannot raise the LDS limit");
+  g.rpw = mlp_rpw(M);
+  hipLaunchKernelGGL((mlp_fused_kernel<1, 1, 8, false, false, false, 2, true>), dim3((M + g.rpw - 1) / g.rpw), dim3(512), lds_bytes(1, 8),
+                     (hipStream_t)stream, g);
+  ROVIT_CHECK_LAUNCH("mlp_fused_kernel (backward with the front phase)");
   return ROVIT_OK;
 }
 

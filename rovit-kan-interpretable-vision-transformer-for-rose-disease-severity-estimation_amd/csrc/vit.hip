@@ -274,7 +274,7 @@ int vit_prepare_impl(const float* const* params, void* prep, int depth, rovit_st
   }
   RUN(rovit_mlp_stream_prep_blocks(prep, P.blk0, P.blk_stride, P.wfc1, P.wfc2, P.wmlp, P.wproj, 0, P.blk_stride + P.wqkv, depth, s_blocks,
                                    gelu_tables));     // + proj and the NEXT block's qkv: the block-tail image
-  RUN(rovit_mlp_stream_prep_blocks(prep, P.blk0, P.blk_stride, P.wfc2T, P.wfc1T, P.wmlpb, P.wprojT, 1, ~(size_t)0, depth, s_blocks));     // dgrad chain: (W2T, W1T) + WprojT: the backward block-tail image
+  RUN(rovit_mlp_stream_prep_blocks(prep, P.blk0, P.blk_stride, P.wfc2T, P.wfc1T, P.wmlpb, P.wprojT, 1, P.blk_stride + P.wqkvT, depth, s_blocks));     // dgrad chain: (W2T, W1T) + WprojT: the backward block-tail image; + the WqkvT of the block ABOVE: the front entries of rovit_block_bwd_fused
   return ROVIT_OK;
 }
 }  // namespace
@@ -688,6 +688,15 @@ int vit_backward_impl(const float* images, const float* d_features, const float*
   if (ss) ss->carry = false;
   hipEvent_t* ev_bdone = ss ? ss->ev_bdone : no_events;
   int pending = -1;                                   // block whose qkv weight gradient has not been issued yet
+  // Round 5: on the one-launch MLP path A5 of block i and A1 + A2 of block i - 1 are ONE launch (rovit_block_bwd_fused: both are row-local,
+  // and the gradient rows between them stay on chip).  A5 is therefore not issued at the end of iteration i but carried into iteration
+  // i - 1 (`a5_pending`).  It stays a launch of its own where it has no MLP launch behind it in this call -- block 0's (rovit_gemm_ln_bwd, as
+  // before) and the last block of a range (the same kernel in its front-only mode, the MLP part of the next range in its MLP-only mode: a
+  // backward cut into block ranges runs the same arithmetic as an uncut one) -- and for the last block's class-token form.
+  // The fused launch sits where A1 + A2 sat (A5 only got later): dqkv[p] of block i + 1 is read by it before A4 of block i - 1 overwrites
+  // it, the x0 buffer it writes was last read by block i + 3's weight gradients, and the one hand-over per block still follows the launch
+  // that produces dpre, xmid and the gradient rows.  The one WAIT per block did move: see the loop.
+  int a5_pending = -1;
 #define EVFAIL(what) do { rovit_set_error("vit_backward: " what " failed"); return ROVIT_ERR_LAUNCH; } while (0)
   // never more splits than the slab buffers were sized for (small batches have few 64-row steps)
   const int S_MERGE = std::min(std::min(ROVIT_KNOB(ROVIT_KNOB_WGRAD_SPLITS, 16), L.s_fc1), std::min(std::min(L.s_fc2, L.s_qkv), L.s_proj));
@@ -790,12 +799,26 @@ int vit_backward_impl(const float* images, const float* d_features, const float*
     char* dp = ws + L.dpre[p];
     char* dq = ws + L.dqkv[p];
     char* xmid = ws + L.x1[p];
-    if (ss && i + 2 < depth && ev_bdone[i + 2] && hipStreamWaitEvent(sA, ev_bdone[i + 2], 0) != hipSuccess) EVFAIL("event wait");
+    // The one wait per block, for the launch of stream B that carried block i + 2's qkv weight gradient (the merged launch of block
+    // i + 1).  What needs it is A4 below, which overwrites dqkv[p]; this block's MLP launch overwrites dpre[p] and x1[p], last read by the
+    // merged launch of block i + 2, which the wait of iteration i + 1 already covered.  Since round 5 the wait therefore sits in front
+    // of A4: in front of the MLP launch it put [MLP dgrad] -> record -> [B's launches] -> wait -> [next MLP dgrad] into one dependent chain,
+    // which became the block period once A5 had moved into the MLP launch (A's work between its record and its next wait fell from 165
+    // to 133 us, B's launches take ~130).  Only where no earlier wait covers block i + 2's launches (i + 3 >= depth: they are the last
+    // block's class-token weight gradients) does it stay in front of the MLP launch.
+    const bool wait_b = ss && i + 2 < depth && ev_bdone[i + 2];
+    const bool wait_early = i + 3 >= depth;
+    if (wait_b && wait_early && hipStreamWaitEvent(sA, ev_bdone[i + 2], 0) != hipSuccess) EVFAIL("event wait");
     // A1 + A2 in one launch (mlp_fused.hip): fc2 dgrad x gelu' -> dpre (kept for the fc1 weight gradient), fc1 dgrad + norm2 backward
     // without re-reading dpre; two launches below the batch threshold.  (Round 3 also built the backward's counterpart of the block tail
     // -- norm2 backward in registers and the proj dgrad in the same launch -- and measured it SLOWER in the step, 4.87 against 4.78 ms:
     // tools/attic)
-    if (one_launch) {
+    if (one_launch && a5_pending == i + 1) {      // [A5 of block i + 1] + [A1 + A2]: xin is written by this launch
+      char* su = ws + L.blk0 + (size_t)(i + 1) * L.blk_stride;
+      RUN(rovit_block_bwd_fused(ws + L.dqkv[(i + 1) & 1], su + L.xhat1, (const float*)(su + L.rstd1), ws + L.x1[(i + 1) & 1], xin, q + P.wmlpb,
+                                s + L.dact, dp, s + L.xhat2, (const float*)(s + L.rstd2), xmid, M, sA));
+      a5_pending = -1;
+    } else if (one_launch) {
       RUN(rovit_mlp_fused_bwd(xin, q + P.wmlpb, s + L.dact, dp, s + L.xhat2, (const float*)(s + L.rstd2), nullptr, xmid, M, sA));
     } else {
       RUN(rovit_gemm_nt(xin, D, q + P.wfc2T, D, M, MLP, D, nullptr, EPI_MUL, dp, MLP, nullptr, nullptr, 0, s + L.dact, MLP, nullptr, 0, sA));   // A1
@@ -816,9 +839,17 @@ int vit_backward_impl(const float* images, const float* d_features, const float*
       RUN(rovit_attention_relevance_step(s + L.qkv, (const float*)(s + L.lse), ws + L.dO, rel->u, rel->scratch, batch, 0, sA));
       if (i == 0) break;
     }
+    if (wait_b && !wait_early && hipStreamWaitEvent(sA, ev_bdone[i + 2], 0) != hipSuccess) EVFAIL("event wait");
     RUN(rovit_attention_bwd(s + L.qkv, s + L.o, (const float*)(s + L.lse), ws + L.dO, dq, batch, T, H, D / H, 0.125f, sA));       // A4
     // qkv dgrad fused with the backward of norm1
-    RUN(rovit_gemm_ln_bwd(dq, 3 * D, q + P.wqkvT, 3 * D, M, 3 * D, s + L.xhat1, (const float*)(s + L.rstd1), nullptr, xmid, xout, sA));   // A5
+    if (one_launch && i > last_block) {
+      a5_pending = i;                           // A5 rides in front of block i - 1's MLP dgrad
+    } else if (one_launch && i > 0) {           // the range ends here: the fused kernel's front part alone (its weight fragments: block i - 1's image)
+      RUN(rovit_block_bwd_fused(dq, s + L.xhat1, (const float*)(s + L.rstd1), xmid, xout, q - P.blk_stride + P.wmlpb, nullptr, nullptr, nullptr,
+                                nullptr, nullptr, M, sA));
+    } else {
+      RUN(rovit_gemm_ln_bwd(dq, 3 * D, q + P.wqkvT, 3 * D, M, 3 * D, s + L.xhat1, (const float*)(s + L.rstd1), nullptr, xmid, xout, sA));   // A5
+    }
     pending = i;
   }
   auto patch_grads = [&]() -> int {          // the patch embedding's and the position embedding's gradients (block range ending at 0)
