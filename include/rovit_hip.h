@@ -295,12 +295,26 @@ int rovit_vit_f32_workspace_field(int batch, int field, size_t* offset, size_t* 
  *   XHAT1 / XHAT2: bf16 (M,192) normalised rows before the norm1 / norm2 affine; RSTD1 / RSTD2: fp32 (M)
  *   QKV: bf16 (M,576); ATTN_O: bf16 (M,192) attention output before proj; ACT: bf16 gelu(fc1), (M,768) row-major when the
  *   two-launch MLP half ran (mlp_path, see rovit_vit_forward), CHUNK-MAJOR [24][M][32] when the one-launch half did
- *   DQKV: bf16 (M,576) gradient w.r.t. the qkv output of `block`, valid after rovit_vit_backward has processed that
- *   block and before it processes block-2 (call it with first_block = last_block = block, then read)
- * The last block (block = depth-1) runs everything behind its attention on the class-token rows alone: its ATTN_O, XHAT2, RSTD2 and
- * ACT are written on rows b*197 (b < batch) only, the other rows of those buffers hold nothing meaningful (ACT row-major there). */
+ *   DACT: bf16 gelu'(fc1 pre-activation), the layout of ACT (chunk-major when the one-launch half ran)
+ *   LSE: fp32 (batch,3,197) log-sum-exp of the scaled attention logits per (image, head, query), in log2 units
+ *   XHAT_CLS: fp32 (batch,192) class-token rows before the final norm's affine; RSTD_CLS: fp32 (batch) (`block` is not used)
+ * The backward's rotating buffers (block i uses x0[i % 3], x1[i & 1], dpre[i & 1], dqkv[i & 1]; they are reused two or three blocks
+ * later): each field is valid right after rovit_vit_backward(first_block = last_block = block) has returned and before the next block's
+ * range is issued:
+ *   DX_IN:  bf16 (M,192) gradient w.r.t. the residual stream leaving `block` (what enters its backward)
+ *   DPRE:   bf16 (M,768) gradient w.r.t. the fc1 pre-activation, the layout of ACT
+ *   DX_MID: bf16 (M,192) gradient w.r.t. the stream between the attention half and the MLP half
+ *   DO:     bf16 (M,192) gradient w.r.t. the attention output before proj
+ *   DQKV:   bf16 (M,576) gradient w.r.t. the qkv output of `block` (valid until block-2 is processed)
+ *   DX_OUT: bf16 (M,192) gradient w.r.t. the stream entering `block`; block 0's are the rows the patch-embedding, position and
+ *           class-token gradients are built from (DX_OUT of block i is DX_IN of block i-1: the same buffer)
+ * The last block (block = depth-1) runs everything behind its attention on the class-token rows alone: its ATTN_O, XHAT2, RSTD2, ACT
+ * and DACT, its LSE (query 0 of every head) and its DX_IN, DPRE, DX_MID and DO are written on rows b*197 (b < batch) only; the other
+ * rows of those buffers are never written and must not be read (ACT, DACT and DPRE are row-major there).  Its DQKV and DX_OUT hold
+ * every row. */
 enum { ROVIT_WS_XHAT1 = 0, ROVIT_WS_RSTD1 = 1, ROVIT_WS_QKV = 2, ROVIT_WS_ATTN_O = 3, ROVIT_WS_XHAT2 = 4, ROVIT_WS_RSTD2 = 5,
-       ROVIT_WS_ACT = 6, ROVIT_WS_DQKV = 7 };
+       ROVIT_WS_ACT = 6, ROVIT_WS_DQKV = 7, ROVIT_WS_DACT = 8, ROVIT_WS_LSE = 9, ROVIT_WS_XHAT_CLS = 10, ROVIT_WS_RSTD_CLS = 11,
+       ROVIT_WS_DX_IN = 12, ROVIT_WS_DX_MID = 13, ROVIT_WS_DPRE = 14, ROVIT_WS_DO = 15, ROVIT_WS_DX_OUT = 16 };
 int rovit_vit_workspace_field(int batch, int depth, int field, int block, size_t* offset, size_t* bytes);
 /* rovit_vit_backward for a data-parallel caller: for last_block > 0 the call does not wait for the range's weight
  * gradients on `stream`; `notify_stream` (the caller's reduction stream) is made to wait for them instead.  Issue the

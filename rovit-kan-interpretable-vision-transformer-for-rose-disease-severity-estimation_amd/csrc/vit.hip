@@ -241,8 +241,17 @@ extern "C" int rovit_vit_workspace_field(int batch, int depth, int field, int bl
     case ROVIT_WS_XHAT2: *offset = blk + L.xhat2; *bytes = M * D * 2; break;
     case ROVIT_WS_RSTD2: *offset = blk + L.rstd2; *bytes = M * 4; break;
     case ROVIT_WS_ACT: *offset = blk + L.act; *bytes = M * MLP * 2; break;
-    // the last block's backward (CLS rows only behind the attention) uses buffer 0, the others their parity's
-    case ROVIT_WS_DQKV: *offset = L.dqkv[block & 1]; *bytes = M * 3 * D * 2; break;
+    case ROVIT_WS_DQKV: *offset = L.dqkv[block & 1]; *bytes = M * 3 * D * 2; break;       // every block its parity's buffer, the last one too
+    case ROVIT_WS_DACT: *offset = blk + L.dact; *bytes = M * MLP * 2; break;
+    case ROVIT_WS_LSE: *offset = blk + L.lse; *bytes = (size_t)batch * H * T * 4; break;
+    case ROVIT_WS_XHAT_CLS: *offset = L.xhat_cls; *bytes = (size_t)batch * D * 4; break;
+    case ROVIT_WS_RSTD_CLS: *offset = L.rstd_cls; *bytes = (size_t)batch * 4; break;
+    // the backward's rotating buffers (see rovit_vit_backward: x0v, x1[i & 1], dpre[i & 1])
+    case ROVIT_WS_DX_IN: *offset = L.x0[block % 3]; *bytes = M * D * 2; break;
+    case ROVIT_WS_DX_MID: *offset = L.x1[block & 1]; *bytes = M * D * 2; break;
+    case ROVIT_WS_DPRE: *offset = L.dpre[block & 1]; *bytes = M * MLP * 2; break;
+    case ROVIT_WS_DO: *offset = L.dO; *bytes = M * D * 2; break;
+    case ROVIT_WS_DX_OUT: *offset = L.x0[(block + 2) % 3]; *bytes = M * D * 2; break;
     default: rovit_set_error("vit_workspace_field: unknown field %d", field); return ROVIT_ERR_SHAPE;
   }
   return ROVIT_OK;

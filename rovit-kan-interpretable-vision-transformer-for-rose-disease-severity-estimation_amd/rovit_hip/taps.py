@@ -48,27 +48,39 @@ def attention_probabilities(model, x: torch.Tensor) -> List[torch.Tensor]:
 
 
 # ---- views into the training workspace (include/rovit_hip.h: rovit_vit_workspace_field) ------------------------
-WS_XHAT1, WS_RSTD1, WS_QKV, WS_ATTN_O, WS_XHAT2, WS_RSTD2, WS_ACT, WS_DQKV = range(8)
+(WS_XHAT1, WS_RSTD1, WS_QKV, WS_ATTN_O, WS_XHAT2, WS_RSTD2, WS_ACT, WS_DQKV, WS_DACT, WS_LSE, WS_XHAT_CLS, WS_RSTD_CLS, WS_DX_IN, WS_DX_MID,
+ WS_DPRE, WS_DO, WS_DX_OUT) = range(17)
 _FIELD_DTYPE = {WS_XHAT1: (torch.bfloat16, 192), WS_QKV: (torch.bfloat16, 576), WS_ATTN_O: (torch.bfloat16, 192),
                 WS_XHAT2: (torch.bfloat16, 192), WS_ACT: (torch.bfloat16, 768), WS_DQKV: (torch.bfloat16, 576),
-                WS_RSTD1: (torch.float32, 1), WS_RSTD2: (torch.float32, 1)}
+                WS_RSTD1: (torch.float32, 1), WS_RSTD2: (torch.float32, 1), WS_DACT: (torch.bfloat16, 768), WS_LSE: (torch.float32, 197),
+                WS_XHAT_CLS: (torch.float32, 192), WS_RSTD_CLS: (torch.float32, 1), WS_DX_IN: (torch.bfloat16, 192),
+                WS_DX_MID: (torch.bfloat16, 192), WS_DPRE: (torch.bfloat16, 768), WS_DO: (torch.bfloat16, 192),
+                WS_DX_OUT: (torch.bfloat16, 192)}
+_CLS_ROWS_IN_LAST_BLOCK = (WS_ATTN_O, WS_XHAT2, WS_RSTD2, WS_ACT, WS_DACT, WS_DX_IN, WS_DX_MID, WS_DPRE, WS_DO)
+_CHUNK_MAJOR = (WS_ACT, WS_DACT, WS_DPRE)
 
 
 def workspace_view(ws: torch.Tensor, batch: int, depth: int, field: int, block: int, mlp_path: int = native.MLP_AUTO) -> torch.Tensor:
-    """(M, width) view of one saved buffer of a training workspace -- zero-copy, except WS_ACT when the one-launch MLP half wrote it
-    (mlp_path of the forward, see include/rovit_hip.h): that buffer is CHUNK-MAJOR [24][M][32] and is de-interleaved into a row-major
-    copy here (round 3 returned the raw bytes under a row-major shape).
-    The last block's WS_ATTN_O, WS_XHAT2, WS_RSTD2 and WS_ACT are written on the class-token rows b * 197 only: for those the view is
-    (batch, width), just those rows."""
+    """(M, width) view of one saved buffer of a training workspace -- zero-copy, except WS_ACT, WS_DACT and WS_DPRE when the one-launch MLP
+    half wrote them (mlp_path of the forward, see include/rovit_hip.h): those buffers are CHUNK-MAJOR [24][M][32] and are de-interleaved
+    into a row-major copy here (round 3 returned the raw bytes under a row-major shape).
+    The last block's WS_ATTN_O, WS_XHAT2, WS_RSTD2, WS_ACT, WS_DACT, WS_DX_IN, WS_DX_MID, WS_DPRE and WS_DO are written on the class-token
+    rows b * 197 only: for those the view is (batch, width), just those rows.  WS_LSE is (batch, 3, 197) (the last block's: (batch, 3, 1),
+    the class token's query); WS_XHAT_CLS (batch, 192) and WS_RSTD_CLS (batch, 1) belong to the final norm (`block` is not used).
+    The backward's fields (WS_DX_IN .. WS_DX_OUT, WS_DQKV) are valid right after rovit_vit_backward(first_block = last_block = block)."""
     off, nbytes = ctypes.c_size_t(), ctypes.c_size_t()
     call('rovit_vit_workspace_field', batch, depth, field, block, ctypes.byref(off), ctypes.byref(nbytes))
     dt, width = _FIELD_DTYPE[field]
     M = batch * 197
     flat = ws[off.value:off.value + nbytes.value].view(dt)
-    if block == depth - 1 and field in (WS_ATTN_O, WS_XHAT2, WS_RSTD2, WS_ACT):
+    if field == WS_LSE:
+        return flat.view(batch, 3, 197)[:, :, :1] if block == depth - 1 else flat.view(batch, 3, 197)
+    if field in (WS_XHAT_CLS, WS_RSTD_CLS):
+        return flat.view(batch, width)
+    if block == depth - 1 and field in _CLS_ROWS_IN_LAST_BLOCK:
         return flat.view(batch, 197, width)[:, 0]
-    if field == WS_ACT and (mlp_path == native.MLP_ONE_LAUNCH or (mlp_path == native.MLP_AUTO and M >= native.MLP_FUSED_MIN_ROWS)) \
-            and block != depth - 1:            # (the last block's MLP half runs on the CLS rows with the two-launch kernels: row-major)
+    if field in _CHUNK_MAJOR and (mlp_path == native.MLP_ONE_LAUNCH or (mlp_path == native.MLP_AUTO and M >= native.MLP_FUSED_MIN_ROWS)) \
+            and block != depth - 1:            # (the last block's MLP half runs on the CLS rows with the class-token kernels: row-major)
         return flat.view(24, M, 32).permute(1, 0, 2).reshape(M, width)
     return flat.view(M, width)
 
