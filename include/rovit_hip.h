@@ -915,6 +915,39 @@ int rovit_augment_batch(const unsigned char* src, int n_images, int src_h, int s
                         unsigned long long epoch, float* out, int out_h, int out_w, rovit_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Image corruptions of the same store (corrupt.hip): the eleven corruptions of a corruption-robustness benchmark (Hendrycks &
+ * Dietterich, ICLR 2019) at the store's own resolution, ONE launch per batch; the definitions, the severity tables and the draw rule are
+ * stated in full in rovit_hip/corrupt.py ("parity unpinned" where ImageNet-C has no parameter of the same meaning).
+ *   src (n_images, 3, h, w) uint8, h, w >= 8   indices (batch) int64 into the store   out (batch, 3, h, w) fp32
+ *   out_u8 (batch, 3, h, w) uint8 or NULL
+ * All arithmetic is on v = u8 / 255; the result is z = clamp(., 0, 1), out = (z - mean_c) / std_c with the ImageNet constants (no
+ * quantisation), out_u8 = floor(255 z + 0.5).  desc->param is sigma (gaussian_noise, gaussian_blur), c (shot_noise, brightness,
+ * contrast), p (impulse_noise), r (defocus_blur), R (motion_blur, integer), s (saturate), b (pixelate, integer) or the quality (jpeg,
+ * integer).  Draws: Philox4x32-10, key = desc->seed, counter = (pixel index y w + x, index in the STORE, kind, 0); the motion blur's angle
+ * from the counter (index in the STORE, 0, kind, 1).  Output rows are bit-identical for every batch size, order and split.
+ * rovit_corrupt_stats: sums (batch, 3) int64 = the integer sum of each sample's three uint8 planes (fixed-order integer reduction; 0 for an
+ * index outside the store); rovit_corrupt_batch reads them for ROVIT_CORRUPT_CONTRAST alone (`sums` may be NULL otherwise).
+ * An index outside [0, n_images) is not dereferenced: that sample's output is NaN (its out_u8 rows 0).
+ * Refused before any launch: null pointers, out or out_u8 overlapping src, a side below 8, an unknown kind, a parameter outside its range
+ * (stencil radii above ROVIT_CORRUPT_MAX_RADIUS: gaussian ceil(3 sigma), defocus r, motion R + 1).
+ * ------------------------------------------------------------------------------------------------------------ */
+enum {
+  ROVIT_CORRUPT_GAUSSIAN_NOISE = 0, ROVIT_CORRUPT_SHOT_NOISE = 1, ROVIT_CORRUPT_IMPULSE_NOISE = 2, ROVIT_CORRUPT_GAUSSIAN_BLUR = 3,
+  ROVIT_CORRUPT_DEFOCUS_BLUR = 4, ROVIT_CORRUPT_MOTION_BLUR = 5, ROVIT_CORRUPT_BRIGHTNESS = 6, ROVIT_CORRUPT_CONTRAST = 7,
+  ROVIT_CORRUPT_SATURATE = 8, ROVIT_CORRUPT_PIXELATE = 9, ROVIT_CORRUPT_JPEG = 10, ROVIT_CORRUPT_COUNT = 11
+};
+#define ROVIT_CORRUPT_MAX_RADIUS 18
+typedef struct rovit_corruption {
+  int kind;                  /* ROVIT_CORRUPT_* */
+  float param;
+  unsigned long long seed;
+} rovit_corruption;
+int rovit_corrupt_stats(const unsigned char* src, int n_images, int src_h, int src_w, const long long* indices, int batch, long long* sums,
+                        rovit_stream_t stream);
+int rovit_corrupt_batch(const unsigned char* src, int n_images, int src_h, int src_w, const long long* indices, int batch,
+                        const rovit_corruption* desc, const long long* sums, float* out, unsigned char* out_u8, rovit_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Feature-space density (density.hip): is a feature row anything like the training features?  Every score of the score card above reads
  * the heads; these three entries read outputs['features'] (models/rovit_kan.py) alone.  Mahalanobis distance to class-conditional
  * Gaussians with a tied covariance (Lee et al., NeurIPS 2018), its relative form (Ren et al. 2021), and the AUROC / AUPR / FPR@TPR of

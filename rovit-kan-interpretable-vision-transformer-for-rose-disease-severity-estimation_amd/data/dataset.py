@@ -204,6 +204,44 @@ class DeviceAugmentLoader:
                 yield imgs, self._labels_host.index_select(0, order[lo:hi]), self._sev_host.index_select(0, order[lo:hi])
 
 
+class DeviceCorruptLoader:
+    """``DeviceAugmentLoader``'s contract for one cell of a corruption benchmark: ``.dataset`` is a ``Subset`` of the store's
+    ``RoseLeafDataset``, ``len()`` = batches, iteration yields ``(images, class_labels, severity_labels)`` with the images an fp32
+    (B, 3, H, W) batch at the STORE's resolution made by one launch (two for ``contrast``) of ``rovit_hip.corrupt.corrupt`` and the labels
+    on the host (``labels_on_device=True``: on the device).  No shuffle and no epoch: ``indices`` are visited in the order given, and an
+    image's corruption depends on (its index in the store, ``corruption``, the parameter, ``seed``) alone, so every pass yields the same
+    bits.  ``param`` overrides the severity table.  ``.store`` and ``.indices`` are what ``Evaluator.evaluate_corruptions`` reads."""
+
+    def __init__(self, store, indices: Sequence[int], batch_size: int, corruption: str, severity: int = 3, seed: int = 0,
+                 labels_on_device: bool = False, param=None):
+        from rovit_hip.corrupt import _resolve
+        self.store, self.batch_size, self.corruption, self.severity = store, int(batch_size), corruption, severity
+        self.param = _resolve(corruption, severity, param)          # raises on an unknown name, severity or parameter
+        self.seed, self.labels_on_device = int(seed), labels_on_device
+        self._idx = torch.as_tensor(list(indices), dtype=torch.long)
+        if self.batch_size <= 0 or self._idx.numel() == 0:
+            raise ValueError('DeviceCorruptLoader needs a positive batch size and at least one index')
+        if int(self._idx.min()) < 0 or int(self._idx.max()) >= len(store):
+            raise IndexError(f'store index outside [0, {len(store)})')
+        self.indices = self._idx.tolist()
+        self.dataset = Subset(store.dataset, self.indices)
+        self._labels_host, self._sev_host = store.labels.cpu(), store.severities.cpu()
+
+    def __len__(self) -> int:
+        return (self._idx.numel() + self.batch_size - 1) // self.batch_size
+
+    def __iter__(self):
+        order_dev = self._idx.to(self.store.device, non_blocking=True)
+        for b in range(len(self)):
+            lo, hi = b * self.batch_size, (b + 1) * self.batch_size
+            sel = order_dev[lo:hi]
+            imgs = self.store.corrupt(sel, self.corruption, seed=self.seed, param=self.param)
+            if self.labels_on_device:
+                yield imgs, self.store.labels.index_select(0, sel), self.store.severities.index_select(0, sel)
+            else:
+                yield imgs, self._labels_host.index_select(0, self._idx[lo:hi]), self._sev_host.index_select(0, self._idx[lo:hi])
+
+
 def _split(n: int, frac: float, seed: int) -> Tuple[List[int], List[int]]:
     perm = torch.randperm(n, generator=torch.Generator().manual_seed(seed)).tolist()
     k = int(round(n * frac))

@@ -17,7 +17,9 @@ test set (``Conformal.evaluate``).
 ``fit_index(train_loader)`` records the training features in a ``rovit_hip.neighbors.FeatureIndex``; ``evaluate(index=fi, knn_k=10)``
 records each row's distance to its k-th nearest training feature as the extra column ``knn_distance`` (one more score of the selective
 card) and adds ``metrics['knn']``: how well the neighbour-weighted vote alone classifies and estimates severity, and how often it agrees
-with the classification head; ``evaluate_ood(..., index=fi)`` adds the ``'knn'`` card."""
+with the classification head; ``evaluate_ood(..., index=fi)`` adds the ``'knn'`` card.
+``evaluate_corruptions(store_or_loader)`` is the corruption-robustness score card: the test images corrupted on the device from the uint8
+store (``rovit_hip.corrupt``), one card per (corruption, severity) cell, the corruption errors and, against a baseline, CE and mCE."""
 from pathlib import Path
 from typing import Dict
 
@@ -242,6 +244,122 @@ class Evaluator:
             lines.append(f"{k:<24}{c['auroc']:>10.4f}{c['aupr_out']:>10.4f}{c['aupr_in']:>10.4f}{c['fpr_at_tpr'][self.OOD_LEVEL]:>12.4f}")
         print('\n'.join(lines + ['']))
         return cards
+
+    CORRUPTION_CARD = ('accuracy', 'macro_f1', 'mae', 'brier_score', 'ece')
+
+    def _corruption_source(self, source):
+        """(store, index list, batch size) of a ``DeviceImageStore`` or of a loader that carries one."""
+        from rovit_hip.augment import DeviceImageStore
+        source = self.test_loader if source is None else source
+        if isinstance(source, DeviceImageStore):
+            return source, list(range(len(source))), 64
+        store, subset = getattr(source, 'store', None), getattr(source, 'dataset', None)
+        if not isinstance(store, DeviceImageStore) or not hasattr(subset, 'indices'):
+            raise RovitHipError('evaluate_corruptions needs the uint8 images on the device: pass a DeviceImageStore, or build the loaders '
+                                'with create_dataloaders(..., device_cache=True)')
+        return store, list(subset.indices), int(getattr(source, 'batch_size', 64))
+
+    def _corruption_cell(self, store, order, batch_size: int, name: str, param: float, seed: int, clean_pred):
+        """One cell: one pass into a fresh ``EvalAccumulator`` (nothing read back per batch), its ``compute()`` and ONE more
+        device-to-host copy of three numbers: the predictions that differ from ``clean_pred``, the summed confidence and the summed
+        sigma.  Returns the card and the predictions (on the device)."""
+        acc = EvalAccumulator(len(self.config.data.class_names))
+        self.model.eval()
+        with torch.no_grad():
+            for lo in range(0, order.numel(), batch_size):
+                sel = order[lo:lo + batch_size]
+                outputs = self.model(store.corrupt(sel, name, seed=seed, param=param))
+                acc.update(outputs, store.labels.index_select(0, sel), store.severities.index_select(0, sel))
+        m = acc.compute()
+        if acc.device.type == 'cuda':
+            rec = {k: acc._rec[k][:acc.n] for k in ('pred', 'probs', 'uncertainty')}
+        else:
+            rec = {k: torch.from_numpy(v) for k, v in acc._cpu_arrays().items() if k in ('pred', 'probs', 'uncertainty')}
+        pred = rec['pred']
+        flips = (pred != clean_pred).sum() if clean_pred is not None else torch.zeros((), dtype=torch.int64, device=pred.device)
+        sigma = rec['uncertainty'].double().sum() if acc._has_uncertainty else torch.zeros((), dtype=torch.float64, device=pred.device)
+        flips, conf, sigma = torch.stack([flips.double(), rec['probs'].max(dim=1).values.double().sum(), sigma]).cpu().tolist()
+        card = {k: m[k] for k in self.CORRUPTION_CARD}
+        card.update(n=m['n'], correct=m['correct'], mean_confidence=conf / m['n'], flip_rate=flips / m['n'])
+        if acc._has_uncertainty:
+            card['mean_sigma'] = sigma / m['n']
+        return card, pred
+
+    def evaluate_corruptions(self, source=None, corruptions=None, severities=(1, 2, 3, 4, 5), seed: int = 0, baseline=None, params=None):
+        """Extension (not in the reference): the corruption-robustness score card of Hendrycks & Dietterich (ICLR 2019) with the
+        corruptions of ``rovit_hip.corrupt`` -- one card per (corruption, severity) cell, each one pass over ``source`` with the images
+        corrupted on the device from the uint8 store (one launch per batch, two for ``contrast``).
+
+        ``source``: a ``DeviceImageStore`` or a loader that carries one (default ``self.test_loader``; a loader without a store raises:
+        build it with ``create_dataloaders(..., device_cache=True)``).  ``corruptions``: names (default all eleven); ``severities``: a
+        subset of 1..5; ``params``: ``{name: {severity: value}}`` replaces entries of the severity table.  Returned dict: ``'clean'``,
+        the card of the uncorrupted pass (``brightness`` at c = 0, which is the plain normalisation, so that the clean and the corrupted
+        passes share a code path and a resolution); ``'cells'[name][severity]`` with ``accuracy``, ``macro_f1`` (per cent), ``mae``,
+        ``brier_score``, ``ece``, ``mean_confidence``, ``mean_sigma`` when the model returns ``log_var``, ``n``, ``correct`` and
+        ``flip_rate``, the share of rows whose predicted class differs from the clean pass's (both passes visit the same rows in the
+        same order); ``'error'[name]``, the mean error (100 - accuracy, per cent) over the severities; ``'mean_corruption_error'``, the
+        mean of those; ``'relative_error'[name]``, the same after subtracting the clean error.  ``baseline``: another call's result for
+        the same cells adds ``'ce'[name]`` = sum_s E_s / sum_s E_s^baseline (None where the baseline made no error) and their mean
+        ``'mce'``: Hendrycks's normalised numbers with the user's own baseline in AlexNet's place.  The table is printed and saved as
+        ``corruption_results.txt`` and ``.json`` in ``config.paths.results_dir``."""
+        from rovit_hip.corrupt import CORRUPTIONS, _resolve
+        store, indices, batch_size = self._corruption_source(source)
+        names = list(CORRUPTIONS if corruptions is None else corruptions)
+        severities = [int(s) for s in severities]
+        if not names or not severities:
+            raise RovitHipError('evaluate_corruptions: no corruption or no severity to evaluate')
+        table = {name: {s: _resolve(name, s, (params or {}).get(name, {}).get(s)) for s in severities} for name in names}
+        order = store.upload_indices(indices)
+        clean, clean_pred = self._corruption_cell(store, order, batch_size, 'brightness', 0.0, seed, None)
+        result = {'clean': clean, 'severities': severities, 'cells': {}, 'error': {}, 'relative_error': {}}
+        clean_error = 100.0 - clean['accuracy']
+        for name in names:
+            result['cells'][name] = {s: self._corruption_cell(store, order, batch_size, name, table[name][s], seed, clean_pred)[0] for s in severities}
+            errors = [100.0 - result['cells'][name][s]['accuracy'] for s in severities]
+            result['error'][name] = sum(errors) / len(errors)
+            result['relative_error'][name] = result['error'][name] - clean_error
+        result['mean_corruption_error'] = sum(result['error'].values()) / len(names)
+        if baseline is not None:
+            result['ce'] = {}
+            for name in names:
+                mine = sum(100.0 - result['cells'][name][s]['accuracy'] for s in severities)
+                theirs = sum(100.0 - baseline['cells'][name][s]['accuracy'] for s in severities)
+                result['ce'][name] = mine / theirs if theirs > 0 else None
+            known = [v for v in result['ce'].values() if v is not None]
+            result['mce'] = sum(known) / len(known) if known else None
+        lines = self._corruption_lines(result)
+        print('\n'.join(lines))
+        results_dir = getattr(getattr(self.config, 'paths', None), 'results_dir', None)
+        if results_dir is not None:
+            import json
+            results_dir = Path(results_dir)
+            results_dir.mkdir(parents=True, exist_ok=True)
+            (results_dir / 'corruption_results.txt').write_text('\n'.join(lines) + '\n', encoding='utf-8')
+            (results_dir / 'corruption_results.json').write_text(json.dumps(result, indent=1) + '\n', encoding='utf-8')
+            print(f"Results saved to {results_dir / 'corruption_results.txt'}")
+        return result
+
+    @staticmethod
+    def _corruption_lines(result: Dict):
+        """Rows are corruptions, columns severities, entries accuracy (per cent), with the mean sigma under each when present."""
+        sev = result['severities']
+        has_sigma = 'mean_sigma' in result['clean']
+        lines = ['', 'Corruption robustness (accuracy %' + (', mean sigma below' if has_sigma else '') + '):',
+                 f"{'Corruption':<18}" + ''.join(f'{"s=" + str(s):>9}' for s in sev) + f"{'Error':>9}" + (f"{'CE':>8}" if 'ce' in result else ''),
+                 '-' * (27 + 9 * len(sev) + (8 if 'ce' in result else 0))]
+        for name, cells in result['cells'].items():
+            ce = result.get('ce', {}).get(name)
+            lines.append(f'{name:<18}' + ''.join(f"{cells[s]['accuracy']:>9.2f}" for s in sev) + f"{result['error'][name]:>9.2f}"
+                         + ('' if 'ce' not in result else (f'{ce:>8.3f}' if ce is not None else f"{'n/a':>8}")))
+            if has_sigma:
+                lines.append(f"{'':<18}" + ''.join(f"{cells[s]['mean_sigma']:>9.4f}" for s in sev))
+        clean = result['clean']
+        lines += ['-' * (27 + 9 * len(sev) + (8 if 'ce' in result else 0)),
+                  f"{'clean':<18}{clean['accuracy']:>9.2f}" + (f"   (mean sigma {clean['mean_sigma']:.4f})" if has_sigma else ''),
+                  f"{'Mean corruption error:':<28}{result['mean_corruption_error']:.2f}%"]
+        if result.get('mce') is not None:
+            lines.append(f"{'mCE against the baseline:':<28}{result['mce']:.3f}")
+        return lines + ['']
 
     @staticmethod
     def _summary(metrics: Dict, rho_label: str):

@@ -305,3 +305,9 @@ class DeviceImageStore:
         call('rovit_augment_batch', ptr(self.images), N, Hs, Ws, ptr(idx), B, ptr(params), ptr(rows), C.addressof(cfg),
              int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch) & 0xFFFFFFFFFFFFFFFF, ptr(out), Ho, Wo, stream_ptr())
         return (out, rows) if return_params else out
+
+    def corrupt(self, indices, corruption: str, severity: int = 3, seed: int = 0, param=None, out: Optional[torch.Tensor] = None,
+                return_u8: bool = False):
+        """``rovit_hip.corrupt.corrupt(self, ...)``: the images under one of its ``CORRUPTIONS`` at the store's own resolution."""
+        from .corrupt import corrupt
+        return corrupt(self, indices, corruption, severity, seed, param, out, return_u8)

@@ -143,6 +143,8 @@ SIGNATURES = {
     'rovit_eval_conformal_apply_workspace_bytes': (_sz, [_i, _i]),
     'rovit_eval_conformal_apply': (_i, [_vp, _vp]),
     'rovit_augment_batch': (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, C.c_ulonglong, C.c_ulonglong, _vp, _i, _i, _vp]),
+    'rovit_corrupt_stats': (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp]),
+    'rovit_corrupt_batch': (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
 }
 
 
@@ -387,6 +389,14 @@ class AugmentConfigC(C.Structure):
     """``rovit_augment_config`` of include/rovit_hip.h, field for field."""
     _fields_ = [(k, _f) for k in ('p_hflip', 'p_vflip', 'scale_lo', 'scale_hi', 'log_ratio_lo', 'log_ratio_hi', 'theta_max',
                                   'brightness', 'contrast', 'saturation', 'hue')]
+
+
+class CorruptionC(C.Structure):
+    """``rovit_corruption`` of include/rovit_hip.h, field for field."""
+    _fields_ = [('kind', _i), ('param', _f), ('seed', C.c_ulonglong)]
+
+
+CORRUPT_MAX_RADIUS = 18          # ROVIT_CORRUPT_MAX_RADIUS: gaussian ceil(3 sigma), defocus r, motion R + 1
 
 
 # entry points only the developer library exports (round-2 / round-3 experiments that lost; tools/ A/B them)
