@@ -420,12 +420,25 @@ int rovit_mlp_fused_bwd(const void* dY, const void* wstream_bwd, const void* dac
 int rovit_mlp_prepare_stream_bwd(const void* w2T, const void* w1T, const void* wqkvT_next, void* wstream, rovit_stream_t stream);
 int rovit_block_bwd_fused(const void* dqkv, const void* xhat1, const float* rstd1, const void* xmid_in, void* xout, const void* wstream_bwd,
                           const void* dact, void* dpre, const void* xhat2, const float* rstd2, void* dXb, int M, rovit_stream_t stream);
+/* The same launch for the class-token block as block i (the last block, whose post-attention half runs on the class-token rows alone):
+ * xmid_step > 0 says that only the rows m with m % xmid_step == 0 of xmid_in carry a gradient (xmid_step = 197: one row per image).
+ * Every other row is taken as exact zeros by a select, so what xmid_in holds there (stale rows, NaN) never reaches an output; the rows
+ * are still addressed, so xmid_in must be a readable (M,192) buffer.  xout is bit-identical to
+ * rovit_gemm_ln_bwd_cls(dqkv, K = 576, ..., dXb_in = xmid_in, cls_step = xmid_step, dXb = xout), dpre / dXb to rovit_mlp_fused_bwd on it.
+ * xmid_step == 0 is rovit_block_bwd_fused; xmid_step < 0 is refused.  Partial modes as rovit_block_bwd_fused. */
+int rovit_block_bwd_fused_cls(const void* dqkv, const void* xhat1, const float* rstd1, const void* xmid_in, int xmid_step, void* xout,
+                              const void* wstream_bwd, const void* dact, void* dpre, const void* xhat2, const float* rstd2, void* dXb, int M,
+                              rovit_stream_t stream);
 /* dgrad through a Linear that follows a LayerNorm, fused with that LayerNorm's backward:
  * dxhat = dY W^T;  dX += rstd (dxhat - mean(dxhat) - xhat mean(dxhat xhat));  dXb = bf16(dX).
  * dXb_in != NULL (round 4): the incoming residual gradient as bf16 rows (M,192); then dXb = bf16(float(dXb_in) + that term) and the fp32
  * dX (may be NULL) is neither read nor written: 58 MB less per launch at batch 256. */
 int rovit_gemm_ln_bwd(const void* dY, int ldy, const void* W, int ldw, int M, int K, const void* xhat, const float* rstd, float* dX,
                       const void* dXb_in, void* dXb, rovit_stream_t stream);
+/* rovit_gemm_ln_bwd with a bf16 incoming gradient dXb_in that is non-zero on every cls_step-th row only (cls_step > 0; the class-token
+ * block of rovit_vit_backward): the other rows count as zeros and are not read.  dXb = bf16(that row or zero + the LayerNorm-backward term). */
+int rovit_gemm_ln_bwd_cls(const void* dY, int ldy, const void* W, int ldw, int M, int K, const void* xhat, const float* rstd,
+                          const void* dXb_in, int cls_step, void* dXb, rovit_stream_t stream);
 /* G(N,K) = dY(M,N)^T A(M,K) and colsum(dY), split over M into `splits` fp32 slabs inside ws */
 int rovit_wgrad_splits(int M, int N, int K);
 size_t rovit_wgrad_workspace_bytes(int N, int K, int splits);

@@ -33,6 +33,8 @@ void rovit_set_error(const char* fmt, ...) {
 // (rovit_augment_batch was added at 440 the same way: per-sample augmentation of a device-resident uint8 image store, augment_batch.hip.)
 // (rovit_joint_loss_mixed and rovit_train_finalize were added at 440 the same way: the CutMix / MixUp loss with a per-batch record and the
 // per-epoch reduction, train_epoch.hip.)
+// (rovit_block_bwd_fused_cls and rovit_gemm_ln_bwd_cls were added at 440 the same way: the class-token forms of the backward's fused
+// launch and of the qkv dgrad it replaces, mlp_fused.hip / gemm.hip.)
 // (rovit_adamw_ema_flat_multi and rovit_swap_flat_multi were added at 440 the same way: weight EMA inside the AdamW launch, optim.hip.)
 // (rovit_eval_calibrate_workspace_bytes, rovit_eval_calibrate and rovit_eval_recalibrate were added at 440 the same way: temperature and
 // sigma scaling of the evaluation record, calibrate.hip.)

@@ -69,6 +69,9 @@ enum RovitKnob {
   ROVIT_KNOB_ATTN_FWD3 = 20,     // 1: attention forward with three workgroups per CU (attn_fwd3_kernel)
   ROVIT_KNOB_GRADCAM_RECOMPUTE = 21, // 1: Grad-CAM++'s second pass recomputes g = dqkv . Wqkv instead of reading the fp32 scratch (gradcam.hip)
   ROVIT_KNOB_SKIP_WGRAD_REDUCE = 14,  // 1: the slab-reduce / affine-finalize launches are not issued (gradients WRONG): upper bound of what folding them away could gain
+  ROVIT_KNOB_BWD_ENDS = 22,      // ends of the backward (vit.hip, round 6): bit 0 fused class-token A5, 1 early release, 2 serial bottom, 3 attention first
+  ROVIT_KNOB_BOTTOM_A5_CUS = 23, // CUs the qkv dgrad behind an early-released weight gradient sizes its grid for (default 256)
+  ROVIT_KNOB_LONE_WGRAD_192 = 24, // 1: a lone weight gradient on the merged launch's 192 x 192 eight-wave tiles (default: 96 x 96)
   ROVIT_KNOB_COUNT = 32
 };
 #ifdef ROVIT_DEV
@@ -237,9 +240,6 @@ int rovit_cls_tail_bwd(const float* dfeat, const float* xhat_cls, const float* r
 // attention backward whose dout carries gradient on the first `dout_rows` rows of every image only (the last block: the class token's)
 int rovit_attention_bwd_rows(const void* qkv, const void* out, const float* lse2, const void* dout, int dout_rows, void* dqkv, int batch,
                              int tokens, int heads, int head_dim, float scale, rovit_stream_t stream);
-// rovit_gemm_ln_bwd with a bf16 residual gradient that is non-zero on every `cls_step`-th row only (other rows: zero, not read)
-int rovit_gemm_ln_bwd_cls(const void* dY, int ldy, const void* W, int ldw, int M, int K, const void* xhat, const float* rstd,
-                          const void* dXb_in, int cls_step, void* dXb, rovit_stream_t stream);
 // several weight gradients G[N][K] = dY[M][N]^T A[M][K] that share M, in one launch (gemm.hip)
 struct RovitWgradDesc { const void* dY; int ldy; const void* A; int lda; int N, K; float* ws; int a_blk, y_blk; };   // *_blk: operand chunk-major [cols/32][M][32]
 int rovit_wgrad_batch(const RovitWgradDesc* descs, int n, int M, int splits, rovit_stream_t stream);

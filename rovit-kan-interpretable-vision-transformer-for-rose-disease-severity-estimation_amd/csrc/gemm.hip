@@ -1727,7 +1727,7 @@ int rovit_wgrad_batch(const RovitWgradDesc* descs, int n, int M, int splits, rov
   // smaller tiles: DESIGN.md "weight gradients").  12 tiles per M-split; 16 splits = 192 workgroups in the step (the other
   // stream's dgrad kernels keep the remaining CUs busy), 21 = 252 is the fastest standalone (73 us against 107 us for 64 x 192
   // tiles x 14 splits on the same box).
-  if (n == 1 && g.p[0].K % 96 == 0) launch_wgrad<96, 96>(g, (hipStream_t)stream);
+  if (n == 1 && g.p[0].K % 96 == 0 && !ROVIT_KNOB(ROVIT_KNOB_LONE_WGRAD_192, 0)) launch_wgrad<96, 96>(g, (hipStream_t)stream);
   else {                             // 192 x 192 tiles, eight waves: 12 tiles per split
     for (int j = 0; j < n; ++j) ROVIT_CHECK_ARG(descs[j].N % 192 == 0 && descs[j].K % 192 == 0, ROVIT_ERR_SHAPE, "wgrad_batch: N, K %% 192 for 192-wide tiles");
     launch_wgrad<192, 192, 4>(g, (hipStream_t)stream);
@@ -1829,8 +1829,8 @@ extern "C" int rovit_gemm_ln_bwd(const void* dY, int ldy, const void* W, int ldw
                                  float* dX, const void* dXb_in, void* dXb, rovit_stream_t stream) {
   return gemm_ln_bwd_impl(dY, ldy, W, ldw, M, K, xhat, rstd, dX, dXb_in, 0, dXb, stream);
 }
-int rovit_gemm_ln_bwd_cls(const void* dY, int ldy, const void* W, int ldw, int M, int K, const void* xhat, const float* rstd,
-                          const void* dXb_in, int cls_step, void* dXb, rovit_stream_t stream) {
+extern "C" int rovit_gemm_ln_bwd_cls(const void* dY, int ldy, const void* W, int ldw, int M, int K, const void* xhat, const float* rstd,
+                                     const void* dXb_in, int cls_step, void* dXb, rovit_stream_t stream) {
   ROVIT_CHECK_ARG(dXb_in && cls_step > 0, ROVIT_ERR_NULL, "gemm_ln_bwd_cls: needs the bf16 incoming gradient and a row step");
   return gemm_ln_bwd_impl(dY, ldy, W, ldw, M, K, xhat, rstd, nullptr, dXb_in, cls_step, dXb, stream);
 }

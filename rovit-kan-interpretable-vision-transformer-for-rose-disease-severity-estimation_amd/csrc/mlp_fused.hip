@@ -129,6 +129,7 @@ struct MlpArgs {
   const float* frstd;     // FRONT: (M) its rstd1
   const bf16* fxmid;      // FRONT: (M,192) its mid-block residual gradient
   bf16* fxout;            // FRONT: (M,192) output: the gradient entering that block = this block's dY (xin is not read)
+  int fstep;              // FRONT: > 0: only rows m % fstep == 0 of fxmid carry gradient (the class-token block's), the others count as zeros
   float* X;               // (M,192) forward: residual stream; backward: dX; updated in place
   bf16* xhat;             // forward: next LayerNorm output or NULL; backward: xhat2 (input)
   float* rstd;            // forward: (M) output; backward: rstd2 (input)
@@ -356,10 +357,12 @@ __global__ __launch_bounds__(NW * 64, TPW == 1 ? 4 : 2) void mlp_fused_kernel(co
         for (int e = 0; e < 4; ++e) { v[4 * i + e] = (float)t[e]; h[4 * i + e] = (float)hs[i][e]; s1 += v[4 * i + e]; s2 += v[4 * i + e] * h[4 * i + e]; }
       }
       const float c1 = wave_sum16(s1) * (1.f / 192.f), c2 = wave_sum16(s2) * (1.f / 192.f);
+      // fstep > 0: a row without an incoming gradient is zeros by a select, whatever fxmid holds there (gemm.hip's EPI_LNBWD: has_in)
+      const bool has_in = g.fstep <= 0 || (m % g.fstep) == 0;
       bf16x4 bq[3];
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
-        f32x4 x = {(float)ps[i][0], (float)ps[i][1], (float)ps[i][2], (float)ps[i][3]};
+        f32x4 x = has_in ? (f32x4){(float)ps[i][0], (float)ps[i][1], (float)ps[i][2], (float)ps[i][3]} : (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int e = 0; e < 4; ++e) x[e] += rr * (v[4 * i + e] - c1 - h[4 * i + e] * c2);
         bq[i] = pack4(x);
@@ -1479,9 +1482,12 @@ extern "C" int rovit_mlp_fused_bwd(const void* dY, const void* wstream_bwd, cons
 //   bf16 rows just computed, taken from LDS: xout is written (the fc2 weight gradient reads it) and not read back.
 // wstream_bwd: rovit_mlp_prepare_stream_bwd's buffer.  Partial modes (block-range boundaries): dqkv == NULL runs the MLP part alone
 // (xout is then the INPUT dY: exactly rovit_mlp_fused_bwd), dact == NULL the front part alone.
-extern "C" int rovit_block_bwd_fused(const void* dqkv, const void* xhat1, const float* rstd1, const void* xmid_in, void* xout,
-                                     const void* wstream_bwd, const void* dact, void* dpre, const void* xhat2, const float* rstd2,
-                                     void* dXb, int M, rovit_stream_t stream) {
+// xmid_step > 0 (rovit_block_bwd_fused_cls): block i is the class-token block, whose mid-block gradient xmid_in carries gradient on every
+// xmid_step-th row only; the other rows are taken as zeros and what the buffer holds there does not matter (rovit_gemm_ln_bwd_cls).
+static int block_bwd_fused_impl(const void* dqkv, const void* xhat1, const float* rstd1, const void* xmid_in, int xmid_step, void* xout,
+                                const void* wstream_bwd, const void* dact, void* dpre, const void* xhat2, const float* rstd2,
+                                void* dXb, int M, rovit_stream_t stream) {
+  ROVIT_CHECK_ARG(xmid_step >= 0, ROVIT_ERR_SHAPE, "block_bwd_fused: xmid_step must be >= 0, got %d", xmid_step);
   if (!dqkv) return rovit_mlp_fused_bwd(xout, wstream_bwd, dact, dpre, xhat2, rstd2, nullptr, dXb, M, stream);
   ROVIT_CHECK_ARG(xhat1 && rstd1 && xmid_in && xout && wstream_bwd, ROVIT_ERR_NULL, "block_bwd_fused: null pointer");
   ROVIT_CHECK_ARG(!dact || (dpre && xhat2 && rstd2 && dXb), ROVIT_ERR_NULL, "block_bwd_fused: null pointer in the MLP part");
@@ -1492,6 +1498,7 @@ extern "C" int rovit_block_bwd_fused(const void* dqkv, const void* xhat1, const 
                   ROVIT_ERR_ALIGN, "block_bwd_fused: buffers must be 16-byte aligned");
   MlpArgs g{};
   g.fdq = (const bf16*)dqkv; g.fxhat = (const bf16*)xhat1; g.frstd = rstd1; g.fxmid = (const bf16*)xmid_in; g.fxout = (bf16*)xout;
+  g.fstep = xmid_step;
   g.wstream = (const bf16*)wstream_bwd; g.fw = g.wstream + (size_t)FRONT_ENTRY0 * CH_ELEMS;
   g.act = (bf16*)dpre; g.mul = (const bf16*)dact; g.xhat = (bf16*)const_cast<void*>(xhat2); g.rstd = const_cast<float*>(rstd2);
   g.xb = (bf16*)dXb; g.M = M;
@@ -1502,6 +1509,16 @@ extern "C" int rovit_block_bwd_fused(const void* dqkv, const void* xhat1, const 
                      (hipStream_t)stream, g);
   ROVIT_CHECK_LAUNCH("mlp_fused_kernel (backward with the front phase)");
   return ROVIT_OK;
+}
+extern "C" int rovit_block_bwd_fused(const void* dqkv, const void* xhat1, const float* rstd1, const void* xmid_in, void* xout,
+                                     const void* wstream_bwd, const void* dact, void* dpre, const void* xhat2, const float* rstd2,
+                                     void* dXb, int M, rovit_stream_t stream) {
+  return block_bwd_fused_impl(dqkv, xhat1, rstd1, xmid_in, 0, xout, wstream_bwd, dact, dpre, xhat2, rstd2, dXb, M, stream);
+}
+extern "C" int rovit_block_bwd_fused_cls(const void* dqkv, const void* xhat1, const float* rstd1, const void* xmid_in, int xmid_step,
+                                         void* xout, const void* wstream_bwd, const void* dact, void* dpre, const void* xhat2,
+                                         const float* rstd2, void* dXb, int M, rovit_stream_t stream) {
+  return block_bwd_fused_impl(dqkv, xhat1, rstd1, xmid_in, xmid_step, xout, wstream_bwd, dact, dpre, xhat2, rstd2, dXb, M, stream);
 }
 
 #ifdef ROVIT_DEV      // round 3's backward block tail: measured slower in the step (4.87 against 4.78 ms), developer library only

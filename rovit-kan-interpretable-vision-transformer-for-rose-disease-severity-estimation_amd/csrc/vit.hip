@@ -706,6 +706,23 @@ int vit_backward_impl(const float* images, const float* d_features, const float*
   // it, the x0 buffer it writes was last read by block i + 3's weight gradients, and the one hand-over per block still follows the launch
   // that produces dpre, xmid and the gradient rows.  The one WAIT per block did move: see the loop.
   int a5_pending = -1;
+  // Round 6, the two ends of the chain.
+  // TOP: the class-token block's A5 (rovit_gemm_ln_bwd_cls) rides in front of block depth - 2's MLP dgrad like every other block's
+  // (rovit_block_bwd_fused_cls, xmid_step = T: the rows of the mid-block gradient that are no class-token rows are zeros by a select).
+  // No wait moves: the fused launch sits where the two launches sat, back to back on the caller's stream; it READS dqkv[(depth-1)&1]
+  // and x1[(depth-1)&1] (which the class-token weight gradients on the side stream also only read) and WRITES x0, dpre and x1 of the
+  // other parities, as the MLP launch of block depth - 2 always did.  It stays a launch of its own where the range ends at block
+  // depth - 1, on the two-launch path, and in rovit_vit_gradcam* (no norm1 backward there).  The class-token block also enqueues its
+  // attention backward BEFORE the side stream's four launches: the backward starts with the device waiting for the host (the head
+  // phase's Python), and the dgrad chain was held up by the host time of launches that belong to the other stream.
+  // BOTTOM: the last block of a range releases its qkv weight gradient (dqkv, xhat1: final when A4 ends) to the side stream behind A4,
+  // not behind A5, which it does not read (`flushed`).  Same launches, slabs and reduce descriptors.
+  // developer library: bit 0 fused class-token A5, bit 1 early release, bit 2 block 0's lone weight gradient serial on the caller's stream,
+  // bit 3 the class-token block's attention backward enqueued first
+  const int ends = ROVIT_KNOB(ROVIT_KNOB_BWD_ENDS, 11);
+  const bool cls_fuse = (ends & 1) != 0, early_release = (ends & 2) != 0, a4_early = (ends & 8) != 0;
+  const bool serial_bottom = (ends & 4) != 0 && last_block == 0;
+  bool flushed = false;                               // the range's last qkv weight gradient is already on the side stream
 #define EVFAIL(what) do { rovit_set_error("vit_backward: " what " failed"); return ROVIT_ERR_LAUNCH; } while (0)
   // never more splits than the slab buffers were sized for (small batches have few 64-row steps)
   const int S_MERGE = std::min(std::min(ROVIT_KNOB(ROVIT_KNOB_WGRAD_SPLITS, 16), L.s_fc1), std::min(std::min(L.s_fc2, L.s_qkv), L.s_proj));
@@ -721,10 +738,11 @@ int vit_backward_impl(const float* images, const float* d_features, const float*
   auto issue_qkv = [&](int i) -> int {
     char* s = ws + L.blk0 + (size_t)i * L.blk_stride;
     const RovitWgradDesc wd = {ws + L.dqkv[i & 1], 3 * D, s + L.xhat1, D, 3 * D, D, (float*)(ws + L.slab_qkv)};
-    RUN(rovit_wgrad_batch(&wd, 1, M, S_MERGE, sB));
+    hipStream_t sQ = serial_bottom ? sA : sB;
+    RUN(rovit_wgrad_batch(&wd, 1, M, S_MERGE, sQ));
     const RovitReduceDesc rd = qkv_reduce_desc(i, S_MERGE);
-    RUN(rovit_wgrad_reduce_batch(&rd, 1, sB));
-    if (ss && !(ev_bdone[i] = hand_over(ss, sB, nullptr, true))) EVFAIL("event record");
+    RUN(rovit_wgrad_reduce_batch(&rd, 1, sQ));
+    if (ss && !(ev_bdone[i] = hand_over(ss, sQ, nullptr, true))) EVFAIL("event record");
     return ROVIT_OK;
   };
   // merged B-stream work of one iteration: [qkv wgrad of `prev`] + fc2, fc1, proj wgrad of block i, then one reduce
@@ -753,6 +771,14 @@ int vit_backward_impl(const float* images, const float* d_features, const float*
     if (prev >= 0 && ss && !(ev_bdone[prev] = hand_over(ss, sB, nullptr, true))) EVFAIL("event record");
     return ROVIT_OK;
   };
+  // Round 6: the flush of the range's last block, issued behind its attention backward (two streams, weight gradients on)
+  auto release_early = [&](int i) -> int {
+    if (!(early_release && !serial_bottom && ss && wgrad && i == last_block)) return ROVIT_OK;
+    if (!hand_over(ss, sA, sB)) EVFAIL("event hand-over");
+    RUN(issue_qkv(i));
+    flushed = true;
+    return ROVIT_OK;
+  };
   for (int i = first_block; i >= last_block; --i) {
     const char* q = pb + P.blk0 + (size_t)i * P.blk_stride;
     char* s = ws + L.blk0 + (size_t)i * L.blk_stride;
@@ -779,6 +805,10 @@ int vit_backward_impl(const float* images, const float* d_features, const float*
       // (no zero fills, round 4: only the CLS rows of dO and of the mid-block gradient carry gradient; the attention backward and the
       // qkv dgrad below are told so and treat the other rows as zeros without reading them)
       if (ss && !hand_over(ss, sA, sB)) EVFAIL("event hand-over");
+      // only the class token's row of dO carries gradient: a rank-one backward (attention.hip), which also zeroes the other queries' dQ rows.
+      // Enqueued in front of the side stream's launches (which it neither feeds nor reads): see "Round 6" above.
+      const bool a4_first = ss && a4_early;
+      if (a4_first) RUN(rovit_attention_cls_bwd(s + L.qkv, s + L.o, (const float*)(s + L.lse), ws + L.dO, dq, batch, T, H, D / H, 0.125f, stream));
       // the final norm's dgamma / dbeta: sample sums off the dgrad chain -> the weight-gradient stream
       if (wgrad) RUN(rovit_cls_norm_affine_grad(d_features, (const float*)(ws + L.xhat_cls), grads[P_NORM_W], grads[P_NORM_B], batch, sB));
       if (wgrad) {
@@ -796,9 +826,13 @@ int vit_backward_impl(const float* images, const float* d_features, const float*
             {(const float*)(ws + L.slab_proj), sc, D, D, nullptr, nullptr, nullptr, bg[B_PROJW], bg[B_PROJB], nullptr, nullptr, nullptr}};
         RUN(rovit_wgrad_reduce_batch(rd, 3, sB));
       }
-      // only the class token's row of dO carries gradient: a rank-one backward (attention.hip), which also zeroes the other queries' dQ rows
-      RUN(rovit_attention_cls_bwd(s + L.qkv, s + L.o, (const float*)(s + L.lse), ws + L.dO, dq, batch, T, H, D / H, 0.125f, stream));
-      RUN(rovit_gemm_ln_bwd_cls(dq, 3 * D, q + P.wqkvT, 3 * D, M, 3 * D, s + L.xhat1, (const float*)(s + L.rstd1), xmc, T, xout, stream));
+      if (!a4_first) RUN(rovit_attention_cls_bwd(s + L.qkv, s + L.o, (const float*)(s + L.lse), ws + L.dO, dq, batch, T, H, D / H, 0.125f, stream));
+      if (one_launch && cls_fuse && i > last_block) {
+        a5_pending = i;                         // A5 rides in front of block depth - 2's MLP dgrad (rovit_block_bwd_fused_cls)
+      } else {
+        RUN(release_early(i));
+        RUN(rovit_gemm_ln_bwd_cls(dq, 3 * D, q + P.wqkvT, 3 * D, M, 3 * D, s + L.xhat1, (const float*)(s + L.rstd1), xmc, T, xout, stream));
+      }
       // the (full-size) qkv weight gradient of this block goes the way of every other block's: as `pending`, into the next block's
       // merged launch on the weight-gradient stream (or the flush behind the loop) instead of 50 us of serial work here
       pending = i;
@@ -824,8 +858,9 @@ int vit_backward_impl(const float* images, const float* d_features, const float*
     // tools/attic)
     if (one_launch && a5_pending == i + 1) {      // [A5 of block i + 1] + [A1 + A2]: xin is written by this launch
       char* su = ws + L.blk0 + (size_t)(i + 1) * L.blk_stride;
-      RUN(rovit_block_bwd_fused(ws + L.dqkv[(i + 1) & 1], su + L.xhat1, (const float*)(su + L.rstd1), ws + L.x1[(i + 1) & 1], xin, q + P.wmlpb,
-                                s + L.dact, dp, s + L.xhat2, (const float*)(s + L.rstd2), xmid, M, sA));
+      RUN(rovit_block_bwd_fused_cls(ws + L.dqkv[(i + 1) & 1], su + L.xhat1, (const float*)(su + L.rstd1), ws + L.x1[(i + 1) & 1],
+                                    i + 1 == depth - 1 ? T : 0, xin, q + P.wmlpb, s + L.dact, dp, s + L.xhat2, (const float*)(s + L.rstd2),
+                                    xmid, M, sA));
       a5_pending = -1;
     } else if (one_launch) {
       RUN(rovit_mlp_fused_bwd(xin, q + P.wmlpb, s + L.dact, dp, s + L.xhat2, (const float*)(s + L.rstd2), nullptr, xmid, M, sA));
@@ -851,13 +886,22 @@ int vit_backward_impl(const float* images, const float* d_features, const float*
     if (wait_b && !wait_early && hipStreamWaitEvent(sA, ev_bdone[i + 2], 0) != hipSuccess) EVFAIL("event wait");
     RUN(rovit_attention_bwd(s + L.qkv, s + L.o, (const float*)(s + L.lse), ws + L.dO, dq, batch, T, H, D / H, 0.125f, sA));       // A4
     // qkv dgrad fused with the backward of norm1
+    RUN(release_early(i));
     if (one_launch && i > last_block) {
       a5_pending = i;                           // A5 rides in front of block i - 1's MLP dgrad
     } else if (one_launch && i > 0) {           // the range ends here: the fused kernel's front part alone (its weight fragments: block i - 1's image)
       RUN(rovit_block_bwd_fused(dq, s + L.xhat1, (const float*)(s + L.rstd1), xmid, xout, q - P.blk_stride + P.wmlpb, nullptr, nullptr, nullptr,
                                 nullptr, nullptr, M, sA));
     } else {
-      RUN(rovit_gemm_ln_bwd(dq, 3 * D, q + P.wqkvT, 3 * D, M, 3 * D, s + L.xhat1, (const float*)(s + L.rstd1), nullptr, xmid, xout, sA));   // A5
+      // Behind an early release the persistent grid is sized for 160 CUs (one workgroup per CU; the tiles and their sums are the same): the
+      // released launch's workgroups then find free CUs at once instead of queueing behind a grid that holds every CU, and are done
+      // before the patch-embedding weight gradient wants the chip (A/B of 160 / 192 / 208 / 256: DESIGN.md section 5, round 6).
+      const int cus = flushed ? ROVIT_KNOB(ROVIT_KNOB_BOTTOM_A5_CUS, 160) : 256;
+      if (cus != 256) rovit_set_cu_budget(cus);
+      const int rc_a5 = rovit_gemm_ln_bwd(dq, 3 * D, q + P.wqkvT, 3 * D, M, 3 * D, s + L.xhat1, (const float*)(s + L.rstd1), nullptr, xmid, xout,
+                                          sA);                                                                     // A5
+      if (cus != 256) rovit_set_cu_budget(256);
+      if (rc_a5 != ROVIT_OK) return rc_a5;
     }
     pending = i;
   }
@@ -875,8 +919,10 @@ int vit_backward_impl(const float* images, const float* d_features, const float*
   };
   bool patch_done = false;
   if (pending >= 0 && wgrad) {
-    if (ss && !hand_over(ss, sA, sB)) EVFAIL("event hand-over");
-    RUN(issue_qkv(pending));
+    if (!flushed) {
+      if (ss && !hand_over(ss, sA, sB)) EVFAIL("event hand-over");
+      RUN(issue_qkv(pending));
+    }
     // the patch-embedding weight gradient (58 us, needs only the dgrad chain's final dX) runs on the caller's stream BESIDE block 0's
     // last weight gradients on the side stream instead of behind the join
     if (ss && last_block == 0) { RUN(patch_grads()); RUN(pixel_grads()); patch_done = true; }

@@ -82,6 +82,8 @@ SIGNATURES = {
     'rovit_mlp_fused_bwd': (_i, [_vp] * 8 + [_i, _vp]),
     'rovit_mlp_prepare_stream_bwd': (_i, [_vp] * 5),
     'rovit_block_bwd_fused': (_i, [_vp] * 11 + [_i, _vp]),
+    'rovit_block_bwd_fused_cls': (_i, [_vp] * 4 + [_i] + [_vp] * 7 + [_i, _vp]),
+    'rovit_gemm_ln_bwd_cls': (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     'rovit_gemm_ln_bwd': (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     'rovit_wgrad_splits': (_i, [_i, _i, _i]),
     'rovit_wgrad_workspace_bytes': (_sz, [_i, _i, _i]),

@@ -3,6 +3,9 @@ append JSON lines to profiles/block_bwd_time.jsonl.
 
     python tools/time_block_bwd.py parent=/path/to/parent/librovit_hip.so stage1=/path/to/this/librovit_hip.so [NAME=LIB ...]
 
+An arm may also be NAME=LIB@ID=VALUE,ID=VALUE: LIB is then the developer library (make -C csrc dev) and the child runs with those knobs
+(common.h RovitKnob ids, through ROVIT_DEV_KNOBS) -- several schedules of one build against each other.
+
 One process tree on one box: this process starts ONE child per arm (``--child``, ROVIT_HIP_LIB = that arm's library), every child builds
 bench.py's workload -- full RoViT-KAN, batch 256, curriculum stage 4, one resident randn batch, step = forward + JointLoss + zero_grad +
 backward + GradSync.finish + RoViTAdamW.step -- and warms it, then waits.  The parent hands out the repeats one at a time, arm after
@@ -89,12 +92,18 @@ def main():
     if a.child:
         return child(a)
     arms = [x.split('=', 1) for x in a.arms]
+    knobs = {}
+    for x in arms:
+        if len(x) == 2 and '@' in x[1]:
+            x[1], knobs[x[0]] = x[1].split('@', 1)
     if len(arms) < 2 or any(len(x) != 2 or not os.path.exists(x[1]) for x in arms):
         raise SystemExit('usage: time_block_bwd.py parent=LIB stage1=LIB [...]: at least two existing libraries, the parent first')
     procs = {}
     try:
         for name, lib in arms:          # one after the other: a child is warm and idle before the next one starts
             env = dict(os.environ, ROVIT_HIP_LIB=os.path.abspath(lib))
+            if name in knobs:
+                env['ROVIT_DEV_KNOBS'] = knobs[name]
             p = subprocess.Popen([sys.executable, os.path.abspath(__file__), '--child', '--batch', str(a.batch), '--steps', str(a.steps)],
                                  stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True, env=env)
             procs[name] = p
@@ -132,6 +141,8 @@ def main():
         rec = {'case': 'step', 'arm': name, 'batch': a.batch, 'stage': 4, 'steps_per_repeat': a.steps, 'repeats': len(times[name]),
                'median_ms_per_step': round(m * 1e3, 4), 'min_ms_per_step': round(lo * 1e3, 4), 'max_ms_per_step': round(hi * 1e3, 4),
                'spread': round((hi - lo) / m, 4), 'final_loss': round(loss[name], 5), 'device': device}
+        if name in knobs:
+            rec['dev_knobs'] = knobs[name]
         if name != base:
             rec['median_minus_%s_us' % base] = round((med[name] - med[base]) * 1e6, 2)
         lines.append(rec)
