@@ -20,27 +20,12 @@
 #include <math.h>
 
 #include "common.h"
+#include "philox.h"
 
 namespace {
 
 constexpr int AB_NT = 256;
 constexpr int AB_ROW = 12;                       // floats per parameter row
-
-// Philox4x32-10 (Salmon et al. 2011), as in head_phase.hip: key = seed, counter = (c0, c1, offset lo, offset hi)
-struct U4 { unsigned x, y, z, w; };
-__device__ __forceinline__ U4 philox4x32_10(unsigned long long seed, unsigned c0, unsigned c1, unsigned long long offset) {
-  unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-  U4 c = {c0, c1, (unsigned)offset, (unsigned)(offset >> 32)};
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
-    const unsigned hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
-    c = U4{hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0};
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  return c;
-}
-__device__ __forceinline__ float u01(unsigned x) { return (float)(x >> 8) * (1.0f / 16777216.0f); }
 
 struct AugArgs {
   const unsigned char* src; const long long* indices; const float* params; float* params_out; float* out;
@@ -91,9 +76,10 @@ __device__ void setup_sample(const AugArgs& a, int n, bool write_row, AugSample&
     for (int k = 0; k < AB_ROW; ++k) row[k] = a.params[(size_t)n * AB_ROW + k];
   } else {
     const rovit_augment_config& c = a.cfg;
-    const U4 r0 = philox4x32_10(a.seed, (unsigned)image, 0u, a.epoch);
-    const U4 r1 = philox4x32_10(a.seed, (unsigned)image, 1u, a.epoch);
-    const U4 r2 = philox4x32_10(a.seed, (unsigned)image, 2u, a.epoch);
+    const unsigned e_lo = (unsigned)a.epoch, e_hi = (unsigned)(a.epoch >> 32);
+    const U4 r0 = philox4x32_10(a.seed, (unsigned)image, 0u, e_lo, e_hi);
+    const U4 r1 = philox4x32_10(a.seed, (unsigned)image, 1u, e_lo, e_hi);
+    const U4 r2 = philox4x32_10(a.seed, (unsigned)image, 2u, e_lo, e_hi);
     row[0] = u01(r0.x) < c.p_hflip ? 1.f : 0.f;
     row[1] = u01(r0.y) < c.p_vflip ? 1.f : 0.f;
     row[2] = c.scale_lo + u01(r0.z) * (c.scale_hi - c.scale_lo);

@@ -124,20 +124,6 @@ __global__ __launch_bounds__(NT) void cal_search_kernel(const Args a, int round)
   }
 }
 
-template <typename T>
-__device__ __forceinline__ T wave_sum_t(T v) {
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
-  return v;
-}
-__device__ __forceinline__ double block_sum(double v, double* s4) {
-  v = wave_sum_t(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((s4[0] + s4[1]) + s4[2]) + s4[3];
-}
-
 __global__ __launch_bounds__(NT) void cal_reg_kernel(const Args a) {
   __shared__ double s4[4];
   __shared__ double sHw[ML];
@@ -170,8 +156,8 @@ __global__ __launch_bounds__(NT) void cal_reg_kernel(const Args a) {
       if (nv) atomicAdd(&sCnt[0], nv);
       if (nb) atomicAdd(&sCnt[1], nb);
     }
-    const double sz = block_sum(z2, s4);
-    const double sl = block_sum(ls, s4);                    // its first barrier also orders the LDS atomics above
+    const double sz = block_sum_t<4>(z2, s4);
+    const double sl = block_sum_t<4>(ls, s4);               // its first barrier also orders the LDS atomics above
     if (tid == 0) {
       a.regp[(size_t)w * 2] = sz;
       a.regp[(size_t)w * 2 + 1] = sl;
@@ -231,8 +217,8 @@ __global__ __launch_bounds__(NT) void cal_step_kernel(const Args a, int round, i
         sz += a.regp[(size_t)c * 2];
         sl += a.regp[(size_t)c * 2 + 1];
       }
-      sz = block_sum(sz, s4);
-      sl = block_sum(sl, s4);
+      sz = block_sum_t<4>(sz, s4);
+      sl = block_sum_t<4>(sl, s4);
     }
     if (tid != 0) return;
     long long* res = (long long*)a.result;
@@ -276,17 +262,15 @@ __global__ __launch_bounds__(NT) void recalibrate_kernel(const rovit_eval_recal 
   }
 }
 
-static inline bool aligned_to(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 static inline bool limits_ok(int n, int C) { return n >= 1 && n <= ROVIT_EVAL_MAX_ROWS && C >= 2 && C <= MC; }
 struct Layout { size_t state, partial, regp, total; };
-static inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 static inline Layout layout(int n) {
   const size_t chunks = ((size_t)n + NT - 1) / NT;
   Layout l;
   l.state = 0;
-  l.partial = up16(sizeof(State));
-  l.regp = l.partial + up16(chunks * NC * 8);
-  l.total = l.regp + up16(chunks * 2 * 8);
+  l.partial = rovit_up16(sizeof(State));
+  l.regp = l.partial + rovit_up16(chunks * NC * 8);
+  l.total = l.regp + rovit_up16(chunks * 2 * 8);
   return l;
 }
 
@@ -310,7 +294,7 @@ extern "C" int rovit_eval_calibrate(const rovit_eval_cal* p, rovit_stream_t stre
   ROVIT_CHECK_ARG(p->workspace && p->result, ROVIT_ERR_NULL, "%s: the workspace or the result block is missing (null pointer)", who);
   ROVIT_CHECK_ARG(rovit_aligned16(p->probs) && rovit_aligned16(p->label) && rovit_aligned16(p->sev_true) && rovit_aligned16(p->uncertainty),
                   ROVIT_ERR_ALIGN, "%s: a record array is not 16-byte aligned", who);
-  ROVIT_CHECK_ARG(aligned_to(p->mu, 4) && aligned_to(p->half_widths, 8) && rovit_aligned16(p->workspace) && aligned_to(p->result, 8),
+  ROVIT_CHECK_ARG(rovit_aligned(p->mu, 4) && rovit_aligned(p->half_widths, 8) && rovit_aligned16(p->workspace) && rovit_aligned(p->result, 8),
                   ROVIT_ERR_ALIGN, "%s: mu, the half-widths, the workspace or the result block is not aligned", who);
   const Layout l = layout(p->n);
   ROVIT_CHECK_ARG(p->workspace_bytes >= l.total, ROVIT_ERR_SHAPE, "%s: the workspace holds %zu bytes, %zu are needed", who, p->workspace_bytes,
@@ -358,7 +342,7 @@ extern "C" int rovit_eval_recalibrate(const rovit_eval_recal* p, rovit_stream_t 
   ROVIT_CHECK_ARG(p->probs && p->probs_out, ROVIT_ERR_NULL, "%s: probs or probs_out is missing (null pointer)", who);
   ROVIT_CHECK_ARG((p->uncertainty != nullptr) == (p->uncertainty_out != nullptr), ROVIT_ERR_NULL,
                   "%s: uncertainty and uncertainty_out go together", who);
-  ROVIT_CHECK_ARG(aligned_to(p->probs, 4) && aligned_to(p->probs_out, 4) && aligned_to(p->uncertainty, 4) && aligned_to(p->uncertainty_out, 4),
+  ROVIT_CHECK_ARG(rovit_aligned(p->probs, 4) && rovit_aligned(p->probs_out, 4) && rovit_aligned(p->uncertainty, 4) && rovit_aligned(p->uncertainty_out, 4),
                   ROVIT_ERR_ALIGN, "%s: an array is not aligned to its element size", who);
   const int blocks = (p->n + NT - 1) / NT;
   hipLaunchKernelGGL(recalibrate_kernel, dim3((unsigned)blocks), dim3(NT), 0, (hipStream_t)stream, *p);

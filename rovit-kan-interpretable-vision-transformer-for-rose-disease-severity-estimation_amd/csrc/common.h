@@ -39,6 +39,8 @@ void rovit_set_error(const char* fmt, ...);
 bool rovit_set_max_lds(const void* fn, size_t bytes);
 
 static inline bool rovit_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+static inline bool rovit_aligned(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }   // a: a power of two
+constexpr size_t rovit_up16(size_t v) { return (v + 15) & ~(size_t)15; }          // workspace sections start on 16 bytes
 
 
 // ---- developer knobs (A/B timing, ablations) ------------------------------------------------------------
@@ -156,6 +158,35 @@ __device__ __forceinline__ float wave_sum64(float v) {
   v = wave_sum16(v); v += __shfl_xor(v, 16); v += __shfl_xor(v, 32);
   return v;
 }
+
+// ---- the fixed-order sums of the evaluation, calibration, conformal, density and training-record kernels, any T
+// (double, long long, int, unsigned).  Their bit-identity claims rest on these two functions:
+//   * every lane (of the wave / of the workgroup) receives the same value: at each butterfly step both partners add
+//     the same two operands, and every thread reads the same NW partials in the same order;
+//   * the tree is fixed: lane l starts from its own v, adds the lanes l^1, l^2, ... l^32, then the wave partials are
+//     added in wave order, ((s[0] + s[1]) + s[2]) + ...; the result depends on the values and their lanes only
+//     (the compiler may reorder the adds of an integer T, which changes no bit);
+//   * block_sum_t has two barriers, so every thread of the NW-wave workgroup must call it.  The first one also
+//     orders whatever LDS traffic preceded the call (the previous call's reads of s included, so calls may share s),
+//     and callers rely on that; the second publishes s.  s: NW values of LDS.
+template <typename T>
+__device__ __forceinline__ T wave_sum_t(T v) {
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
+  return v;
+}
+template <int NW = 4, typename T>
+__device__ __forceinline__ T block_sum_t(T v, T* s) {
+  v = wave_sum_t(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
+  __syncthreads();
+  T t = s[0];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) t += s[w];
+  return t;
+}
+
 // reduce over the 4 lane groups (lanes l, l^16, l^32, l^48)
 __device__ __forceinline__ float group4_sum(float v) { v += __shfl_xor(v, 16); v += __shfl_xor(v, 32); return v; }
 __device__ __forceinline__ float group4_max(float v) {

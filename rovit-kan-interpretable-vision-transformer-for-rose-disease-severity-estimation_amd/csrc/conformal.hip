@@ -28,18 +28,17 @@ constexpr int EW = ROVIT_EVAL_CONF_ENTRY_WORDS;
 struct Layout {                          // byte offsets inside the fit's workspace; every section starts on 16 bytes
   size_t x, flags, cnt, prefix, krem, trivial, hist, total;
 };
-inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 inline Layout layout(int n, int M, int G, int A) {
   const size_t E = (size_t)M * G * A;
   Layout l;
   l.x = 0;
-  l.flags = l.x + up16((size_t)M * n * 4);
-  l.cnt = l.flags + up16((size_t)n * 2);
-  l.prefix = l.cnt + up16(NCNT * 4);          // cnt .. hist are contiguous: one memset covers them
-  l.krem = l.prefix + up16(E * 4);
-  l.trivial = l.krem + up16(E * 4);
-  l.hist = l.trivial + up16(E * 4);
-  l.total = l.hist + up16(E * 256 * 4);
+  l.flags = l.x + rovit_up16((size_t)M * n * 4);
+  l.cnt = l.flags + rovit_up16((size_t)n * 2);
+  l.prefix = l.cnt + rovit_up16(NCNT * 4);    // cnt .. hist are contiguous: one memset covers them
+  l.krem = l.prefix + rovit_up16(E * 4);
+  l.trivial = l.krem + rovit_up16(E * 4);
+  l.hist = l.trivial + rovit_up16(E * 4);
+  l.total = l.hist + rovit_up16(E * 256 * 4);
   return l;
 }
 
@@ -217,16 +216,6 @@ __global__ __launch_bounds__(64) void conf_step_kernel(const Fit f, int round) {
 
 // ---- the application ---------------------------------------------------------------------------------------------------------
 
-template <typename T>
-__device__ __forceinline__ T block_sum_t(T v, T* s4) {
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((s4[0] + s4[1]) + s4[2]) + s4[3];
-}
-
 // dynamic LDS: the tallies of one chunk, M (16 + 32 A) counters
 __global__ __launch_bounds__(NT) void conf_apply_kernel(const rovit_eval_conf a, double* __restrict__ partials, int chunks, int G, int Mcls) {
   extern __shared__ unsigned s_dyn[];
@@ -345,7 +334,6 @@ __global__ __launch_bounds__(NT) void conf_apply_final_kernel(const rovit_eval_c
   }
 }
 
-static inline bool aligned_to(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 static inline bool limits_ok(int n, int M, int G, int A) {
   return n >= 1 && n <= ROVIT_EVAL_MAX_ROWS && M >= 1 && M <= MS && A >= 1 && A <= MA && G >= 1 && G <= 1 + MAXC;
 }
@@ -368,7 +356,7 @@ static int check_common(const rovit_eval_conf* p, const char* who, bool fit) {
     ROVIT_CHECK_ARG(kind >= ROVIT_EVAL_CONF_LAC && kind <= ROVIT_EVAL_CONF_COLUMN, ROVIT_ERR_SHAPE, "%s: score %d has the unknown kind %d", who, m, kind);
     ROVIT_CHECK_ARG(labelled || kind <= ROVIT_EVAL_CONF_RAPS, ROVIT_ERR_NULL, "%s: score %d needs the labels (null pointer)", who, m);
     ROVIT_CHECK_ARG(kind != ROVIT_EVAL_CONF_COLUMN || p->score_column[m], ROVIT_ERR_NULL, "%s: score %d is a column with a null pointer", who, m);
-    ROVIT_CHECK_ARG(kind != ROVIT_EVAL_CONF_COLUMN || aligned_to(p->score_column[m], 4), ROVIT_ERR_ALIGN,
+    ROVIT_CHECK_ARG(kind != ROVIT_EVAL_CONF_COLUMN || rovit_aligned(p->score_column[m], 4), ROVIT_ERR_ALIGN,
                     "%s: the column of score %d is not aligned to its element size", who, m);
     need_kan |= kind == ROVIT_EVAL_CONF_KAN_ABS;
     need_mu |= kind == ROVIT_EVAL_CONF_MU_ABS || kind == ROVIT_EVAL_CONF_MU_SCALED;
@@ -377,11 +365,11 @@ static int check_common(const rovit_eval_conf* p, const char* who, bool fit) {
   ROVIT_CHECK_ARG(p->probs && (!fit || p->label) && (!need_kan || (p->sev_pred && p->sev_true)) && (!need_mu || (p->mu && p->sev_true)) &&
                       (!need_sigma || p->uncertainty),
                   ROVIT_ERR_NULL, "%s: a record array is missing (null pointer)", who);
-  ROVIT_CHECK_ARG(rovit_aligned16(p->probs) && aligned_to(p->label, 4) && aligned_to(p->sev_pred, 4) && aligned_to(p->sev_true, 4) &&
-                      aligned_to(p->uncertainty, 4) && aligned_to(p->mu, 4),
+  ROVIT_CHECK_ARG(rovit_aligned16(p->probs) && rovit_aligned(p->label, 4) && rovit_aligned(p->sev_pred, 4) && rovit_aligned(p->sev_true, 4) &&
+                      rovit_aligned(p->uncertainty, 4) && rovit_aligned(p->mu, 4),
                   ROVIT_ERR_ALIGN, "%s: a record array is not aligned (probs to 16 bytes, the columns to 4)", who);
   ROVIT_CHECK_ARG(!labelled || (p->workspace && p->result), ROVIT_ERR_NULL, "%s: the workspace or the result block is missing (null pointer)", who);
-  ROVIT_CHECK_ARG(rovit_aligned16(p->workspace) && aligned_to(p->result, 8), ROVIT_ERR_ALIGN, "%s: the workspace or the result block is not aligned",
+  ROVIT_CHECK_ARG(rovit_aligned16(p->workspace) && rovit_aligned(p->result, 8), ROVIT_ERR_ALIGN, "%s: the workspace or the result block is not aligned",
                   who);
   return ROVIT_OK;
 }
@@ -398,7 +386,7 @@ extern "C" int rovit_eval_conformal(const rovit_eval_conf* p, rovit_stream_t str
   for (int lvl = 0; lvl < A; ++lvl)
     ROVIT_CHECK_ARG(p->alpha_num[lvl] >= 1 && p->alpha_num[lvl] < p->alpha_den[lvl] && p->alpha_den[lvl] <= ROVIT_EVAL_CONF_MAX_DEN, ROVIT_ERR_SHAPE,
                     "%s: level %d is %u/%u (0 < num < den <= %u)", who, lvl, p->alpha_num[lvl], p->alpha_den[lvl], ROVIT_EVAL_CONF_MAX_DEN);
-  ROVIT_CHECK_ARG(aligned_to(p->scores_out, 4) && aligned_to(p->u_out, 4), ROVIT_ERR_ALIGN, "%s: a matrix to leave behind is not aligned", who);
+  ROVIT_CHECK_ARG(rovit_aligned(p->scores_out, 4) && rovit_aligned(p->u_out, 4), ROVIT_ERR_ALIGN, "%s: a matrix to leave behind is not aligned", who);
   const Layout l = layout(n, M, G, A);
   ROVIT_CHECK_ARG(p->workspace_bytes >= l.total, ROVIT_ERR_SHAPE, "%s: the workspace holds %zu bytes, %zu are needed", who, p->workspace_bytes,
                   l.total);
@@ -441,7 +429,7 @@ extern "C" int rovit_eval_conformal(const rovit_eval_conf* p, rovit_stream_t str
 }
 
 extern "C" size_t rovit_eval_conformal_apply_workspace_bytes(int n, int M) {
-  return limits_ok(n, M, 1, 1) ? up16((size_t)M * ((n + NT - 1) / NT) * 8) : 0;
+  return limits_ok(n, M, 1, 1) ? rovit_up16((size_t)M * ((n + NT - 1) / NT) * 8) : 0;
 }
 
 extern "C" int rovit_eval_conformal_apply(const rovit_eval_conf* p, rovit_stream_t stream) {
@@ -450,10 +438,10 @@ extern "C" int rovit_eval_conformal_apply(const rovit_eval_conf* p, rovit_stream
   if (rc != ROVIT_OK) return rc;
   const int n = p->n, M = p->num_scores, A = p->num_levels, G = p->class_conditional ? 1 + p->num_classes : 1;
   ROVIT_CHECK_ARG(p->thresholds, ROVIT_ERR_NULL, "%s: the thresholds are missing (null pointer)", who);
-  ROVIT_CHECK_ARG(aligned_to(p->thresholds, 4), ROVIT_ERR_ALIGN, "%s: the thresholds are not aligned", who);
+  ROVIT_CHECK_ARG(rovit_aligned(p->thresholds, 4), ROVIT_ERR_ALIGN, "%s: the thresholds are not aligned", who);
   ROVIT_CHECK_ARG(p->label || p->member_out, ROVIT_ERR_NULL, "%s: neither labels nor a membership matrix: nothing to do (null pointer)", who);
   const bool tally = p->label != nullptr;
-  const size_t need = up16((size_t)M * ((n + NT - 1) / NT) * 8);
+  const size_t need = rovit_up16((size_t)M * ((n + NT - 1) / NT) * 8);
   ROVIT_CHECK_ARG(!tally || p->workspace_bytes >= need, ROVIT_ERR_SHAPE, "%s: the workspace holds %zu bytes, %zu are needed", who,
                   p->workspace_bytes, need);
   int Mcls = 0;

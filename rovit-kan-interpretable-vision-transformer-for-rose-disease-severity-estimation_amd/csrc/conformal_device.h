@@ -3,29 +3,15 @@
 // Definitions: include/rovit_hip.h, the rovit_eval_conf comment.
 #pragma once
 #include "common.h"
+#include "philox.h"
 
 namespace conformal {
 
 constexpr int MAXC = ROVIT_EVAL_MAX_CLASSES;
 
-struct U4 { unsigned x, y, z, w; };
-// Philox4x32-10 (Salmon et al. 2011), counter (c0, c1, c2, 0), key = seed, as in eval_bootstrap.hip
-__device__ __forceinline__ U4 philox4x32_10(unsigned long long seed, unsigned c0, unsigned c1, unsigned c2) {
-  unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-  U4 c = {c0, c1, c2, 0u};
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
-    const unsigned hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
-    c = U4{hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0};
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  return c;
-}
-
 // u of one row: ((w >> 8) + 0.5) 2^-24 in two fp32 operations (the product is by a power of two: exact)
 __device__ __forceinline__ float draw_u(unsigned long long seed, unsigned row) {
-  const unsigned w = philox4x32_10(seed, row, 0u, ROVIT_EVAL_CONF_STREAM).x;
+  const unsigned w = philox4x32_10(seed, row, 0u, ROVIT_EVAL_CONF_STREAM, 0u).x;
   return ((float)(w >> 8) + 0.5f) * 5.9604644775390625e-8f;
 }
 

@@ -16,7 +16,7 @@
 //   8x8 codec  jpeg: a wave owns one 8 x 8 block of all three planes (the colour conversion couples them); both passes of the forward and
 //              of the inverse transform go through LDS; integers end to end.
 //
-// Every draw is Philox4x32-10 keyed by the image's index in the STORE and the pixel's index in the image, a pixel's arithmetic depends on
+// Every draw is Philox4x32-10 (philox.h) keyed by the image's index in the STORE and the pixel's index in the image, a pixel's arithmetic depends on
 // nothing else, and the only cross-thread reduction (the plane sums of `contrast`) is an integer sum: a corrupted image has the same
 // bits for every batch size, order and split, and from run to run.  There is no floating-point atomic in this file.
 //
@@ -24,6 +24,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "philox.h"
 
 namespace {
 
@@ -33,22 +34,6 @@ constexpr int ST_TW = 64, ST_TH = 32;                    // stencil tile: 32 row
 constexpr int ST_PW = ST_TW + 2 * CB_HALO, ST_PH = ST_TH + 2 * CB_HALO;
 constexpr int ST_TAPS = 2 * CB_HALO + 1;
 
-// Philox4x32-10 (Salmon et al. 2011), as in augment_batch.hip: key = seed, counter = (c0, c1, c2, c3)
-struct U4 { unsigned x, y, z, w; };
-__device__ __forceinline__ U4 philox4x32_10(unsigned long long seed, unsigned c0, unsigned c1, unsigned c2, unsigned c3) {
-  unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-  U4 c = {c0, c1, c2, c3};
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
-    const unsigned hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
-    c = U4{hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0};
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  return c;
-}
-__device__ __forceinline__ float u01(unsigned x) { return (float)(x >> 8) * (1.0f / 16777216.0f); }            // [0, 1)
-__device__ __forceinline__ float u01_open(unsigned x) { return (float)((x >> 8) + 1u) * (1.0f / 16777216.0f); }  // (0, 1]
 constexpr float TWO_PI = 6.283185307179586f;
 
 struct CorArgs {

@@ -18,10 +18,11 @@
 // rovit_density_score, one kernel: a workgroup stages 64 feature rows in LDS; per 32-row tile of W and W0 it stages the tile's columns up
 //   to the diagonal (the zero upper triangle is never multiplied: exact zeros either way), waves 0-1 form z = W f of row tiles 0-1, waves
 //   2-3 z0 = W0 f; the accumulators hold one feature row per lane, so ||z - M_c||^2 is an in-lane sum plus one cross-half add.
-// rovit_ood_metrics, three kernels: counted ranks as selective.hip counts them (uint32, integer atomics over the split j range), the per-row
+// rovit_ood_metrics, three kernels: counted ranks on the tile of rank_count.h (uint32, integer atomics over the split j range), the per-row
 //   terms with fixed-tree chunk sums, one fold.
 // Work items are walked with a stride of the grid, and no item's result depends on which workgroup computes it.  No floating-point atomics.
 #include "common.h"
+#include "rank_count.h"
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 
@@ -32,28 +33,11 @@ constexpr int SLAB = 32;                // rows of one centred LDS slab of the s
 constexpr int MAXC = ROVIT_EVAL_MAX_CLASSES;
 constexpr int MAX_CHUNKS = 256;         // the chunk length grows with n so that never more partials than this exist
 constexpr int SCORE_ROWS = ROVIT_DENSITY_SCORE_TILE;
-constexpr int RT = 1024;                // x_j per LDS tile of the rank kernel
 static_assert(SCORE_ROWS == 64, "two row tiles of 32 per workgroup");
+static_assert(NT == RANK_NT, "rank_stage_tile strides by RANK_NT");
 
-__host__ __device__ inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 inline int density_chunk_rows(int n) { return ROVIT_DENSITY_CHUNK_ROWS * ((n + ROVIT_DENSITY_CHUNK_ROWS * MAX_CHUNKS - 1) / (ROVIT_DENSITY_CHUNK_ROWS * MAX_CHUNKS)); }
 inline int upper_tiles(int E) { const int T = E / 32; return T * (T + 1) / 2; }
-static inline bool aligned_to(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
-template <typename T>
-__device__ __forceinline__ T wave_sum_t(T v) {
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
-  return v;
-}
-template <typename T>
-__device__ __forceinline__ T block_sum_t(T v, T* s4) {          // the fixed tree of selective.hip's block_sum_t
-  v = wave_sum_t(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((s4[0] + s4[1]) + s4[2]) + s4[3];
-}
 
 // ---- moments -------------------------------------------------------------------------------------------------------------------------
 
@@ -62,11 +46,11 @@ inline MomLayout mom_layout(int n, int E, int C) {
   const size_t R = density_chunk_rows(n), chunks = ((size_t)n + R - 1) / R;
   MomLayout l;
   l.cls = 0;
-  l.csum = l.cls + up16((size_t)n * 4);
-  l.ccnt = l.csum + up16(chunks * C * E * 8);
-  l.mean32 = l.ccnt + up16(chunks * (C + 2) * 8);
-  l.part = l.mean32 + up16((size_t)C * E * 4);
-  l.total = l.part + up16(chunks * upper_tiles(E) * 1024 * 4);
+  l.csum = l.cls + rovit_up16((size_t)n * 4);
+  l.ccnt = l.csum + rovit_up16(chunks * C * E * 8);
+  l.mean32 = l.ccnt + rovit_up16(chunks * (C + 2) * 8);
+  l.part = l.mean32 + rovit_up16((size_t)C * E * 4);
+  l.total = l.part + rovit_up16(chunks * upper_tiles(E) * 1024 * 4);
   return l;
 }
 
@@ -346,8 +330,8 @@ inline OodLayout ood_layout(int n_in, int n_out) {
   const size_t N = (size_t)n_in + n_out, chunks = (N + NT - 1) / NT;
   OodLayout l;
   l.cnt = 0;
-  l.part = l.cnt + up16(4 * N * 4);
-  l.total = l.part + up16(2 * chunks * 8);
+  l.part = l.cnt + rovit_up16(4 * N * 4);
+  l.total = l.part + rovit_up16(2 * chunks * 8);
   return l;
 }
 
@@ -364,9 +348,9 @@ struct OodArgs {
 __device__ __forceinline__ float ood_row(const OodArgs& a, int i) { return i < a.n_in ? a.s_in[i] : a.s_out[i - a.n_in]; }
 
 __global__ __launch_bounds__(NT) void ood_rank_kernel(const OodArgs a, int splits, int tiles_per_split) {
-  __shared__ __attribute__((aligned(16))) float sX[RT];
+  __shared__ __attribute__((aligned(16))) float sX[RANK_RT];
   const int tid = threadIdx.x, N = a.N;
-  const int tin = (a.n_in + RT - 1) / RT, ntiles = tin + (a.n_out + RT - 1) / RT;
+  const int tin = (a.n_in + RANK_RT - 1) / RANK_RT, ntiles = tin + (a.n_out + RANK_RT - 1) / RANK_RT;
   const int items = a.chunks * splits;
   for (int w = blockIdx.x; w < items; w += gridDim.x) {
     const int chunk = w % a.chunks, split = w / a.chunks;
@@ -375,18 +359,13 @@ __global__ __launch_bounds__(NT) void ood_rank_kernel(const OodArgs a, int split
     unsigned less[2] = {0, 0}, eq[2] = {0, 0};
     const int t0 = split * tiles_per_split, t1 = min(ntiles, t0 + tiles_per_split);
     for (int t = t0; t < t1; ++t) {
-      const int side = t >= tin, j0 = (side ? t - tin : t) * RT, lim = side ? a.n_out : a.n_in;
+      const int side = t >= tin, j0 = (side ? t - tin : t) * RANK_RT, lim = side ? a.n_out : a.n_in;
       const float* X = side ? a.s_out : a.s_in;
       __syncthreads();
-      for (int k = tid; k < RT; k += NT) sX[k] = j0 + k < lim ? X[j0 + k] : __builtin_nanf("");   // NaN is neither below nor equal to anything
+      rank_stage_tile(sX, X, j0, lim);
       __syncthreads();
       unsigned l = 0, e = 0;
-#pragma unroll 4
-      for (int k = 0; k < RT / 4; ++k) {
-        const float4 v = reinterpret_cast<const float4*>(sX)[k];
-        l += (v.x < xi) + (v.y < xi) + (v.z < xi) + (v.w < xi);
-        e += (v.x == xi) + (v.y == xi) + (v.z == xi) + (v.w == xi);
-      }
+      rank_count_tile(sX, xi, l, e);
       if (side) { less[1] += l; eq[1] += e; } else { less[0] += l; eq[0] += e; }
     }
     if (i < N) {
@@ -483,7 +462,7 @@ extern "C" int rovit_density_moments(const rovit_density_fit* p, rovit_stream_t 
   ROVIT_CHECK_ARG(p->num_classes >= 2 && p->num_classes <= MAXC, ROVIT_ERR_SHAPE, "%s: %d classes (2..%d)", who, p->num_classes, MAXC);
   ROVIT_CHECK_ARG(p->max_workgroups >= 0, ROVIT_ERR_SHAPE, "%s: max_workgroups %d (>= 0)", who, p->max_workgroups);
   ROVIT_CHECK_ARG(p->features && p->labels && p->workspace && p->result, ROVIT_ERR_NULL, "%s: a null pointer", who);
-  ROVIT_CHECK_ARG(rovit_aligned16(p->features) && aligned_to(p->labels, 4) && rovit_aligned16(p->workspace) && aligned_to(p->result, 8),
+  ROVIT_CHECK_ARG(rovit_aligned16(p->features) && rovit_aligned(p->labels, 4) && rovit_aligned16(p->workspace) && rovit_aligned(p->result, 8),
                   ROVIT_ERR_ALIGN, "%s: the features or the workspace are not 16-byte aligned, or the labels or the result block not to their words", who);
   const int n = p->n, E = p->embed, C = p->num_classes;
   const MomLayout l = mom_layout(n, E, C);
@@ -537,10 +516,10 @@ extern "C" int rovit_density_score(const rovit_density_scores* p, rovit_stream_t
   ROVIT_CHECK_ARG(!p->cls_logits || (p->energy && p->max_prob_score), ROVIT_ERR_NULL, "%s: logits without the energy and max_prob_score outputs", who);
   ROVIT_CHECK_ARG(rovit_aligned16(p->features) && rovit_aligned16(p->whitening) && rovit_aligned16(p->background_whitening), ROVIT_ERR_ALIGN,
                   "%s: the features or a whitening matrix are not 16-byte aligned", who);
-  ROVIT_CHECK_ARG(aligned_to(p->class_means, 4) && aligned_to(p->background_mean, 4) && aligned_to(p->cls_logits, 4) &&
-                      aligned_to(p->class_distances, 4) && aligned_to(p->background_distance, 4) && aligned_to(p->mahalanobis, 4) &&
-                      aligned_to(p->nearest_class, 4) && aligned_to(p->relative_mahalanobis, 4) && aligned_to(p->energy, 4) &&
-                      aligned_to(p->max_prob_score, 4),
+  ROVIT_CHECK_ARG(rovit_aligned(p->class_means, 4) && rovit_aligned(p->background_mean, 4) && rovit_aligned(p->cls_logits, 4) &&
+                      rovit_aligned(p->class_distances, 4) && rovit_aligned(p->background_distance, 4) && rovit_aligned(p->mahalanobis, 4) &&
+                      rovit_aligned(p->nearest_class, 4) && rovit_aligned(p->relative_mahalanobis, 4) && rovit_aligned(p->energy, 4) &&
+                      rovit_aligned(p->max_prob_score, 4),
                   ROVIT_ERR_ALIGN, "%s: an array is not aligned to its element size", who);
   const size_t lds = score_lds_bytes(p->embed, p->num_classes);
   ROVIT_CHECK_ARG(rovit_set_max_lds((const void*)dens_score_kernel, lds), ROVIT_ERR_LAUNCH, "%s: cannot raise the LDS limit", who);
@@ -565,7 +544,7 @@ extern "C" int rovit_ood_metrics(const rovit_ood* p, rovit_stream_t stream) {
                     p->tpr_levels[l]);
   ROVIT_CHECK_ARG(p->max_workgroups >= 0, ROVIT_ERR_SHAPE, "%s: max_workgroups %d (>= 0)", who, p->max_workgroups);
   ROVIT_CHECK_ARG(p->scores_in && p->scores_out && p->workspace && p->result, ROVIT_ERR_NULL, "%s: a null pointer", who);
-  ROVIT_CHECK_ARG(aligned_to(p->scores_in, 4) && aligned_to(p->scores_out, 4) && rovit_aligned16(p->workspace) && aligned_to(p->result, 8),
+  ROVIT_CHECK_ARG(rovit_aligned(p->scores_in, 4) && rovit_aligned(p->scores_out, 4) && rovit_aligned16(p->workspace) && rovit_aligned(p->result, 8),
                   ROVIT_ERR_ALIGN, "%s: the scores, the workspace or the result block are not aligned", who);
   const OodLayout l = ood_layout(p->n_in, p->n_out);
   ROVIT_CHECK_ARG(p->workspace_bytes >= l.total, ROVIT_ERR_SHAPE, "%s: the workspace holds %zu bytes, %zu are needed", who, p->workspace_bytes,
@@ -588,7 +567,7 @@ extern "C" int rovit_ood_metrics(const rovit_ood* p, rovit_stream_t stream) {
   }
   const long long cap = p->max_workgroups > 0 ? p->max_workgroups : (1ll << 30);
   auto grid = [&](long long items) { return dim3((unsigned)(items < cap ? items : cap)); };
-  const int ntiles = (a.n_in + RT - 1) / RT + (a.n_out + RT - 1) / RT;
+  const int ntiles = (a.n_in + RANK_RT - 1) / RANK_RT + (a.n_out + RANK_RT - 1) / RANK_RT;
   // split the j range until about 1024 workgroups exist; the counts are integers, so the split changes nothing
   int splits = (1024 + a.chunks - 1) / a.chunks;
   splits = splits < 1 ? 1 : (splits > ntiles ? ntiles : splits);

@@ -6,7 +6,7 @@
 // Tibshirani 1993) supplies both, and needs one full score card per resample.
 //
 // One workgroup per replicate, persistent over r = blockIdx.x, += gridDim.x.
-//   draws   Philox4x32-10, key = seed, counter = (j / 4, r, ROVIT_EVAL_BOOT_STREAM, 0); word j % 4 gives idx = (word * n) >> 32.  A thread
+//   draws   Philox4x32-10 (philox.h), key = seed, counter = (j / 4, r, ROVIT_EVAL_BOOT_STREAM, 0); word j % 4 gives idx = (word * n) >> 32.  A thread
 //           owns quads q = tid, tid + BT, ...: one Philox call serves four draws, and pass 2 calls it again instead of storing them.
 //   pass 1  gathers the rows; integer histograms (confusion matrix, calibration bins, non-finite, bad labels) and the two rank
 //           histograms H_a, H_b [less[idx]] += 1 through integer atomics; Brier and |severity error| as fp64 sums private to a thread in
@@ -22,6 +22,7 @@
 // Every index that reaches memory is clamped (draw, less value, predicted class, stratification tables), so no record content can
 // send a thread out of bounds.
 #include "common.h"
+#include "philox.h"
 
 namespace {
 
@@ -29,21 +30,6 @@ constexpr int EC = ROVIT_EVAL_MAX_CLASSES, EB = ROVIT_EVAL_MAX_BINS;
 constexpr int BT = 512, BW = BT / 64;       // threads and waves per workgroup
 constexpr int NH = 3 * 64 + 3;              // counters, as in evaluate.hip: confusion | bin count | bin correct | non-finite a, b | bad labels
 constexpr int LDS_GRID = 1024;              // workgroups at most while H is in LDS (four per CU)
-
-struct U4 { unsigned x, y, z, w; };
-// Philox4x32-10 (Salmon et al. 2011), counter (c0, c1, c2, 0), key = seed
-__device__ __forceinline__ U4 philox4x32_10(unsigned long long seed, unsigned c0, unsigned c1, unsigned c2) {
-  unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-  U4 c = {c0, c1, c2, 0u};
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
-    const unsigned hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
-    c = U4{hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0};
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  return c;
-}
 
 template <bool G> __device__ __forceinline__ unsigned h_load(const unsigned* p) {
   if (G) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -61,26 +47,6 @@ template <bool G> __device__ __forceinline__ void h_sync() {
 template <bool G> __device__ __forceinline__ void h_inc(unsigned* p) {
   if (G) __hip_atomic_fetch_add(p, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   else atomicAdd(p, 1u);
-}
-
-// all 64 lanes receive the same sum: at every step both partners add the same two values
-template <typename T>
-__device__ __forceinline__ T wave_sum_t(T v) {
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
-  return v;
-}
-// sum over the workgroup's waves in wave order; s: BW values of LDS
-template <typename T>
-__device__ __forceinline__ T block_sum_t(T v, T* s) {
-  v = wave_sum_t(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-  __syncthreads();
-  T t = s[0];
-#pragma unroll
-  for (int w = 1; w < BW; ++w) t += s[w];
-  return t;
 }
 
 // the row of draw j of replicate r from its Philox word
@@ -133,7 +99,7 @@ __global__ __launch_bounds__(BT) void eval_bootstrap_kernel(const rovit_eval_boo
     for (int q0 = 0; q0 < quads; q0 += BT) {              // uniform trip count: the wave sums below need every lane
       const int q = q0 + tid;
       U4 w4 = {0u, 0u, 0u, 0u};
-      if (q < quads) w4 = philox4x32_10(a.seed, (unsigned)q, (unsigned)r, ROVIT_EVAL_BOOT_STREAM);
+      if (q < quads) w4 = philox4x32_10(a.seed, (unsigned)q, (unsigned)r, ROVIT_EVAL_BOOT_STREAM, 0u);
       const unsigned words[4] = {w4.x, w4.y, w4.z, w4.w};
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -178,8 +144,8 @@ __global__ __launch_bounds__(BT) void eval_bootstrap_kernel(const rovit_eval_boo
       }
     }
     h_sync<G>();                                          // H, s_hist and s_conf complete
-    const double sum_brier = block_sum_t(brier, s_d);
-    const double sum_aerr = block_sum_t(aerr, s_d);
+    const double sum_brier = block_sum_t<BW>(brier, s_d);
+    const double sum_aerr = block_sum_t<BW>(aerr, s_d);
 
     // ---- scan: H[v] <- 2 P[v] + H[v] + 1 ----
     if (tid < 2) s_carry[tid] = 0;
@@ -213,7 +179,7 @@ __global__ __launch_bounds__(BT) void eval_bootstrap_kernel(const rovit_eval_boo
     // ---- pass 2 ----
     long long rab = 0, raa = 0, rbb = 0;
     for (int q = tid; q < quads; q += BT) {
-      const U4 w4 = philox4x32_10(a.seed, (unsigned)q, (unsigned)r, ROVIT_EVAL_BOOT_STREAM);
+      const U4 w4 = philox4x32_10(a.seed, (unsigned)q, (unsigned)r, ROVIT_EVAL_BOOT_STREAM, 0u);
       const unsigned words[4] = {w4.x, w4.y, w4.z, w4.w};
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -226,9 +192,9 @@ __global__ __launch_bounds__(BT) void eval_bootstrap_kernel(const rovit_eval_boo
         }
       }
     }
-    rab = block_sum_t(rab, s_l);
-    raa = block_sum_t(raa, s_l);
-    rbb = block_sum_t(rbb, s_l);
+    rab = block_sum_t<BW>(rab, s_l);
+    raa = block_sum_t<BW>(raa, s_l);
+    rbb = block_sum_t<BW>(rbb, s_l);
     const bool finite = s_hist[192] == 0 && s_hist[193] == 0;
     if (!finite) rab = raa = rbb = 0;                     // the host restatement's convention: no rank sums beside a non-finite value
 
@@ -300,8 +266,6 @@ __global__ __launch_bounds__(BT) void eval_bootstrap_kernel(const rovit_eval_boo
   }
 }
 
-static inline bool aligned_to(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 static inline int ws_grid(int R, int cap) {
   int g = R < ROVIT_EVAL_BOOT_WORKSPACE_GRID ? R : ROVIT_EVAL_BOOT_WORKSPACE_GRID;
   return cap > 0 && cap < g ? cap : g;
@@ -333,8 +297,8 @@ extern "C" int rovit_eval_bootstrap(const rovit_eval_boot* p, rovit_stream_t str
   ROVIT_CHECK_ARG(rovit_aligned16(p->probs) && rovit_aligned16(p->pred) && rovit_aligned16(p->label) && rovit_aligned16(p->sev_pred) &&
                       rovit_aligned16(p->sev_true),
                   ROVIT_ERR_ALIGN, "%s: a record array is not 16-byte aligned", who);
-  ROVIT_CHECK_ARG(aligned_to(p->bin_edges, 8) && rovit_aligned16(p->rank_counts) && aligned_to(p->table, 8) && aligned_to(p->blocks, 8) &&
-                      aligned_to(p->perm, 4) && aligned_to(p->starts, 4) && aligned_to(p->workspace, 4),
+  ROVIT_CHECK_ARG(rovit_aligned(p->bin_edges, 8) && rovit_aligned16(p->rank_counts) && rovit_aligned(p->table, 8) && rovit_aligned(p->blocks, 8) &&
+                      rovit_aligned(p->perm, 4) && rovit_aligned(p->starts, 4) && rovit_aligned(p->workspace, 4),
                   ROVIT_ERR_ALIGN, "%s: bin edges, rank counts, a stratification table, the workspace or an output is not aligned", who);
   const int n = p->n, R = p->num_resamples;
   hipStream_t s = (hipStream_t)stream;

@@ -23,25 +23,11 @@
 #include "common.h"
 #include "kan_device.h"
 #include "head_phase.h"
+#include "philox.h"
 
 namespace {
 
 constexpr int HP_NT = 1024;
-
-// Philox4x32-10 (Salmon et al. 2011): counter (c0, 0, offset lo, offset hi), key = seed
-struct U4 { unsigned x, y, z, w; };
-__device__ __forceinline__ U4 philox4x32_10(unsigned long long seed, unsigned c0, unsigned long long offset) {
-  unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-  U4 c = {c0, 0u, (unsigned)offset, (unsigned)(offset >> 32)};
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
-    const unsigned hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
-    c = U4{hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0};
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  return c;
-}
 
 __device__ __forceinline__ int hp_nheads(int stage) { return stage >= 3 ? 3 : (stage >= 2 ? 2 : 1); }
 
@@ -173,7 +159,7 @@ __global__ __launch_bounds__(HP_NT) void head_phase_fwd_kernel(const rovit_head_
           float v = fmaxf(acc + b1[k], 0.f);                                  // Linear -> ReLU (heads.py:18-19)
           if (mk) v *= mk[(size_t)b * hid + k];                               // -> Dropout (:20): given keep-mask ...
           else if (p.drop_p > 0.f) {                                          // ... or drawn here
-            const U4 rr = philox4x32_10(p.seed, (unsigned)(b * hid + k), p.offset);
+            const U4 rr = philox4x32_10(p.seed, (unsigned)(b * hid + k), 0u, (unsigned)p.offset, (unsigned)(p.offset >> 32));
             const unsigned u = h == 0 ? rr.x : (h == 1 ? rr.y : rr.z);
             v = (float)(u >> 8) * (1.f / 16777216.f) < 1.f - p.drop_p ? v * inv_keep : 0.f;
           }

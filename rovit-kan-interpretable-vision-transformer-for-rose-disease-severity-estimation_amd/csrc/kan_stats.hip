@@ -320,8 +320,6 @@ __global__ __launch_bounds__(NT) void kan_curves_kernel(const float* __restrict_
   ys[idx] = s;
 }
 
-static inline bool aligned_to(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 static bool shape_ok(int in_f, int out_f, int nk) { return in_f >= 1 && out_f >= 1 && nk >= 5 && nk <= KAN_MAX_KNOTS; }
 
 template <int TI>
@@ -362,8 +360,8 @@ extern "C" int rovit_kan_edge_stats(const rovit_kan_stats* p, rovit_stream_t str
   ROVIT_CHECK_ARG((size_t)p->in_f * p->out_f <= ((size_t)1 << 26), ROVIT_ERR_SHAPE, "%s: %d x %d edges exceed 2^26", who, p->in_f, p->out_f);
   ROVIT_CHECK_ARG(p->x && p->spline_w && p->knots && p->lin_w && p->lin_b, ROVIT_ERR_NULL, "%s: an input or a parameter is missing (null pointer)", who);
   ROVIT_CHECK_ARG(p->partials && p->result, ROVIT_ERR_NULL, "%s: the workspace or the result section is missing (null pointer)", who);
-  ROVIT_CHECK_ARG(aligned_to(p->x, 4) && aligned_to(p->spline_w, 4) && aligned_to(p->knots, 4) && aligned_to(p->lin_w, 4) && aligned_to(p->lin_b, 4) &&
-                      aligned_to(p->partials, 8) && aligned_to(p->result, 8),
+  ROVIT_CHECK_ARG(rovit_aligned(p->x, 4) && rovit_aligned(p->spline_w, 4) && rovit_aligned(p->knots, 4) && rovit_aligned(p->lin_w, 4) && rovit_aligned(p->lin_b, 4) &&
+                      rovit_aligned(p->partials, 8) && rovit_aligned(p->result, 8),
                   ROVIT_ERR_ALIGN, "%s: a pointer is not aligned to its element size", who);
   const Geometry g = geometry(p->n, p->in_f, p->out_f, p->n_knots);
   ROVIT_CHECK_ARG(g.lds <= 64 * 1024, ROVIT_ERR_SHAPE, "%s: %zu bytes of LDS", who, g.lds);
@@ -383,7 +381,7 @@ extern "C" int rovit_kan_curves(const float* xs, const float* spline_w, const fl
   ROVIT_CHECK_ARG(shape_ok(in_f, out_f, n_knots) && num_points >= 1, ROVIT_ERR_SHAPE, "%s: layer %d -> %d with %d knots, %d points", who, in_f, out_f,
                   n_knots, num_points);
   ROVIT_CHECK_ARG(xs && spline_w && knots && ys, ROVIT_ERR_NULL, "%s: the grid, a parameter or the output is missing (null pointer; lin_w alone may be)", who);
-  ROVIT_CHECK_ARG(aligned_to(xs, 4) && aligned_to(spline_w, 4) && aligned_to(knots, 4) && aligned_to(lin_w, 4) && aligned_to(ys, 4), ROVIT_ERR_ALIGN,
+  ROVIT_CHECK_ARG(rovit_aligned(xs, 4) && rovit_aligned(spline_w, 4) && rovit_aligned(knots, 4) && rovit_aligned(lin_w, 4) && rovit_aligned(ys, 4), ROVIT_ERR_ALIGN,
                   "%s: a pointer is not aligned to its element size", who);
   const size_t total = (size_t)in_f * out_f * num_points;
   ROVIT_CHECK_ARG(total <= ((size_t)1 << 31), ROVIT_ERR_SHAPE, "%s: %zu values exceed 2^31", who, total);

@@ -7,7 +7,7 @@
 //   (A) features row -> LDS; the output linears of the active heads -> LDS (read T times below)
 //   (B) relu(fc1(x)) of every active head ONCE, with the dense-row arithmetic of head_phase_fwd_kernel step (C) (4 lanes per row,
 //       16-byte loads, the same sum order), kept in LDS
-//   (C) wave w takes the samples t = w, w + NW, ...: lanes cover hid and draw the masks (Philox4x32-10, key = seed, counter
+//   (C) wave w takes the samples t = w, w + NW, ...: lanes cover hid and draw the masks (Philox4x32-10 of philox.h, key = seed, counter
 //       (b * hid + k, t, offset lo, offset hi), words x / y / z -> heads 0 / 1 / 2; kept and scaled as head_phase_fwd_kernel does, so
 //       sample 0 is the training head phase's draw); the masked hidden rows go to the wave's LDS slice; 16 lanes per output row with the
 //       head phase's step (D) arithmetic (models/heads.py:17-22, 38-43, 91-102 with the +-10 log_var clamp of :100)
@@ -18,6 +18,7 @@
 // Every sum has a fixed order and no atomics are used: reruns are bit-identical, and an image's statistics depend only on (its features,
 // its index b, seed, offset).
 #include "common.h"
+#include "philox.h"
 
 namespace {
 
@@ -27,21 +28,6 @@ constexpr int MC_MAX_ROWS = 2 * MC_MAX_CLS + 1;   // C class logits + C - 1 thre
 // Welford slots of a sample (lane = slot): [0, 8) softmax probability of class c; [8, 16) ordinal probability of level c;
 // 16 entropy of the sample's softmax; 17 ordinal severity sum_c c * p_ord_c; 18 mu; 19 exp(log_var)
 constexpr int MC_SLOTS = 20, MC_S_ENT = 16, MC_S_SEV = 17, MC_S_MU = 18, MC_S_ALEA = 19;
-
-struct U4 { unsigned x, y, z, w; };
-// Philox4x32-10 (Salmon et al. 2011), counter (c0, c1, offset lo, offset hi), key = seed; c1 == 0 is head_phase.hip's stream
-__device__ __forceinline__ U4 philox4x32_10(unsigned long long seed, unsigned c0, unsigned c1, unsigned long long offset) {
-  unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-  U4 c = {c0, c1, (unsigned)offset, (unsigned)(offset >> 32)};
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
-    const unsigned hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
-    c = U4{hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0};
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  return c;
-}
 
 __device__ __forceinline__ int mc_nheads(int stage) { return stage >= 3 ? 3 : (stage >= 2 ? 2 : 1); }
 
@@ -125,7 +111,7 @@ __global__ __launch_bounds__(MC_NT) void head_mc_fwd_kernel(const rovit_head_mc 
       for (int k = lane; k < hid; k += ROVIT_WAVE) {
         float v0 = s_h[k], v1 = nheads >= 2 ? s_h[hid + k] : 0.f, v2 = nheads >= 3 ? s_h[2 * hid + k] : 0.f;
         if (drop_p > 0.f) {                                                             // -> Dropout (heads.py:20)
-          const U4 rr = philox4x32_10(p.seed, (unsigned)(b * hid + k), (unsigned)t, p.offset);
+          const U4 rr = philox4x32_10(p.seed, (unsigned)(b * hid + k), (unsigned)t, (unsigned)p.offset, (unsigned)(p.offset >> 32));
           v0 = (float)(rr.x >> 8) * (1.f / 16777216.f) < keep ? v0 * inv_keep : 0.f;
           v1 = (float)(rr.y >> 8) * (1.f / 16777216.f) < keep ? v1 * inv_keep : 0.f;
           v2 = (float)(rr.z >> 8) * (1.f / 16777216.f) < keep ? v2 * inv_keep : 0.f;

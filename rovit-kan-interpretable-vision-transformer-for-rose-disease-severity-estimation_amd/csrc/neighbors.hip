@@ -41,8 +41,6 @@ constexpr int MAX_T = 8;                         // embed / 32
 constexpr u64 EMPTY = ~0ull;                     // above every real key: its distance bits would be a NaN's
 static_assert(QT == 64 && RT == 64, "2 x 2 sub-tiles of 32 per workgroup, one per wave");
 
-__host__ __device__ inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
-static inline bool aligned_to(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 inline int bucket_of(int k) { return k <= 8 ? 8 : (k <= 16 ? 16 : 32); }
 
 struct Plan { int qtiles, rtiles, splits, tps, kb; };
@@ -64,9 +62,9 @@ struct Layout { size_t qnorm, qok, keys, total; };
 inline Layout layout_of(int B, const Plan& p) {
   Layout l;
   l.qnorm = 0;
-  l.qok = l.qnorm + up16((size_t)B * 4);
-  l.keys = l.qok + up16((size_t)B * 4);
-  l.total = l.keys + up16((size_t)B * p.splits * p.kb * 8);
+  l.qok = l.qnorm + rovit_up16((size_t)B * 4);
+  l.keys = l.qok + rovit_up16((size_t)B * 4);
+  l.total = l.keys + rovit_up16((size_t)B * p.splits * p.kb * 8);
   return l;
 }
 
@@ -432,8 +430,8 @@ extern "C" int rovit_knn_build(const rovit_knn_index* p, rovit_stream_t stream) 
   ROVIT_CHECK_ARG(p->features && p->norms && p->valid && p->result, ROVIT_ERR_NULL, "%s: a null pointer", who);
   ROVIT_CHECK_ARG((p->metric == ROVIT_KNN_COSINE) == (p->normalized != nullptr), ROVIT_ERR_NULL,
                   "%s: the normalized copy goes with the cosine metric and with no other", who);
-  ROVIT_CHECK_ARG(rovit_aligned16(p->features) && rovit_aligned16(p->normalized) && aligned_to(p->norms, 4) && aligned_to(p->valid, 4) &&
-                      aligned_to(p->result, 8),
+  ROVIT_CHECK_ARG(rovit_aligned16(p->features) && rovit_aligned16(p->normalized) && rovit_aligned(p->norms, 4) && rovit_aligned(p->valid, 4) &&
+                      rovit_aligned(p->result, 8),
                   ROVIT_ERR_ALIGN, "%s: the rows are not 16-byte aligned, or an array not to its words", who);
   hipStream_t s = (hipStream_t)stream;
   if (hipMemsetAsync(p->result, 0, ROVIT_KNN_WORDS * 8, s) != hipSuccess) {
@@ -471,10 +469,10 @@ extern "C" int rovit_knn_search(const rovit_knn_query* p, rovit_stream_t stream)
                   ROVIT_ERR_NULL, "%s: class_probs and cls go together, with ref_labels and num_classes >= 1", who);
   ROVIT_CHECK_ARG(rovit_aligned16(p->queries) && rovit_aligned16(p->rows) && rovit_aligned16(p->workspace), ROVIT_ERR_ALIGN,
                   "%s: the queries, the rows or the workspace are not 16-byte aligned", who);
-  ROVIT_CHECK_ARG(aligned_to(p->norms, 4) && aligned_to(p->valid, 4) && aligned_to(p->exclude, 4) && aligned_to(p->ref_labels, 4) &&
-                      aligned_to(p->ref_severity, 4) && aligned_to(p->distances, 4) && aligned_to(p->indices, 4) && aligned_to(p->labels, 4) &&
-                      aligned_to(p->severities, 4) && aligned_to(p->class_probs, 4) && aligned_to(p->cls, 4) && aligned_to(p->severity, 4) &&
-                      aligned_to(p->kth_distance, 4) && aligned_to(p->mean_distance, 4),
+  ROVIT_CHECK_ARG(rovit_aligned(p->norms, 4) && rovit_aligned(p->valid, 4) && rovit_aligned(p->exclude, 4) && rovit_aligned(p->ref_labels, 4) &&
+                      rovit_aligned(p->ref_severity, 4) && rovit_aligned(p->distances, 4) && rovit_aligned(p->indices, 4) && rovit_aligned(p->labels, 4) &&
+                      rovit_aligned(p->severities, 4) && rovit_aligned(p->class_probs, 4) && rovit_aligned(p->cls, 4) && rovit_aligned(p->severity, 4) &&
+                      rovit_aligned(p->kth_distance, 4) && rovit_aligned(p->mean_distance, 4),
                   ROVIT_ERR_ALIGN, "%s: an array is not aligned to its element size", who);
   const int B = p->batch, N = p->n, E = p->embed;
   const Plan pl = plan_of(B, N, p->k);

@@ -21,29 +21,29 @@
 // A pair is (score s, risk k), q = s K + k, or (risk k, risk k), q = S K + k: the oracle.  Work items are walked with a stride of the
 // grid, and no item's result depends on which workgroup computes it: the grid cap changes nothing.  No floating-point atomics.
 #include "common.h"
+#include "rank_count.h"
 
 namespace {
 
 constexpr int NT = 256;                 // threads per workgroup = slots per chunk
-constexpr int RT = 1024;                // x_j per LDS tile
 constexpr int MS = ROVIT_EVAL_SEL_MAX_SCORES, MK = ROVIT_EVAL_SEL_MAX_RISKS, MP = ROVIT_EVAL_SEL_MAX_COVERAGES;
 static_assert(NT == 256, "prefix_at shifts a slot by 8 to find its chunk");
+static_assert(NT == RANK_NT, "rank_stage_tile strides by RANK_NT");
 constexpr int OFFS_PER_THREAD = (ROVIT_EVAL_MAX_ROWS / NT + NT - 1) / NT;          // 16 chunk totals per thread at the row limit
 
 struct Layout {                          // byte offsets inside the workspace; every section starts on 16 bytes
   size_t x, cnt, perm, local, csum, rsum, total;
 };
-__host__ __device__ inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 inline Layout layout(int n, int S, int K) {
   const size_t cols = (size_t)S + K, Q = (size_t)S * K + K, chunks = ((size_t)n + NT - 1) / NT;
   Layout l;
   l.x = 0;
-  l.cnt = l.x + up16(cols * n * 4);
-  l.perm = l.cnt + up16(3 * cols * n * 4);          // cnt and perm are contiguous: one memset covers both
-  l.local = l.perm + up16(cols * n * 4);
-  l.csum = l.local + up16(Q * n * 8);
-  l.rsum = l.csum + up16(Q * chunks * 8);
-  l.total = l.rsum + up16(Q * chunks * 8);
+  l.cnt = l.x + rovit_up16(cols * n * 4);
+  l.perm = l.cnt + rovit_up16(3 * cols * n * 4);    // cnt and perm are contiguous: one memset covers both
+  l.local = l.perm + rovit_up16(cols * n * 4);
+  l.csum = l.local + rovit_up16(Q * n * 8);
+  l.rsum = l.csum + rovit_up16(Q * chunks * 8);
+  l.total = l.rsum + rovit_up16(Q * chunks * 8);
   return l;
 }
 
@@ -61,20 +61,6 @@ struct Args {                            // what every kernel after the prepare 
 __device__ __forceinline__ int pair_column(const Args& a, int q) { return q < a.S * a.K ? q / a.K : a.S + (q - a.S * a.K); }
 __device__ __forceinline__ int pair_risk(const Args& a, int q) { return q < a.S * a.K ? q % a.K : q - a.S * a.K; }
 
-template <typename T>
-__device__ __forceinline__ T wave_sum_t(T v) {
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
-  return v;
-}
-template <typename T>
-__device__ __forceinline__ T block_sum_t(T v, T* s4) {
-  v = wave_sum_t(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((s4[0] + s4[1]) + s4[2]) + s4[3];
-}
 // inclusive prefix sums of one value per thread over the workgroup: Kogge-Stone in LDS, the same tree for every launch
 __device__ __forceinline__ double block_scan(double v, double* s) {
   const int tid = threadIdx.x;
@@ -146,9 +132,9 @@ __global__ __launch_bounds__(NT) void sel_prepare_kernel(const rovit_eval_sel a,
 }
 
 __global__ __launch_bounds__(NT) void sel_rank_kernel(const Args a, int splits, int tiles_per_split) {
-  __shared__ __attribute__((aligned(16))) float sX[RT];
+  __shared__ __attribute__((aligned(16))) float sX[RANK_RT];
   const int n = a.n, tid = threadIdx.x, cols = a.S + a.K;
-  const int ntiles = (n + RT - 1) / RT;
+  const int ntiles = (n + RANK_RT - 1) / RANK_RT;
   const int items = a.chunks * splits * cols;
   for (int w = blockIdx.x; w < items; w += gridDim.x) {
     const int chunk = w % a.chunks, split = (w / a.chunks) % splits, col = w / (a.chunks * splits);
@@ -159,31 +145,15 @@ __global__ __launch_bounds__(NT) void sel_rank_kernel(const Args a, int splits, 
     const int t0 = split * tiles_per_split, t1 = min(ntiles, t0 + tiles_per_split);
     for (int t = t0; t < t1; ++t) {
       __syncthreads();
-      for (int k = tid; k < RT; k += NT) {
-        const int j = t * RT + k;
-        sX[k] = j < n ? X[j] : __builtin_nanf("");            // NaN is neither below nor equal to anything
-      }
+      const int j0 = t * RANK_RT;
+      rank_stage_tile(sX, X, j0, n);
       __syncthreads();
-      const int j0 = t * RT;
       unsigned e = 0;
-      if (j0 + RT <= i0 || j0 >= i0 + NT) {                    // every j of the tile lies before, or after, every row of the block
-#pragma unroll 4
-        for (int k = 0; k < RT / 4; ++k) {
-          const float4 v = reinterpret_cast<const float4*>(sX)[k];
-          less += (v.x < xi) + (v.y < xi) + (v.z < xi) + (v.w < xi);
-          e += (v.x == xi) + (v.y == xi) + (v.z == xi) + (v.w == xi);
-        }
-        if (j0 + RT <= i0) before += e;
+      if (j0 + RANK_RT <= i0 || j0 >= i0 + NT) {          // every j of the tile lies before, or after, every row of the block
+        rank_count_tile(sX, xi, less, e);
+        if (j0 + RANK_RT <= i0) before += e;
       } else {
-        const int d = i - j0;                                  // j < i  <=>  k < d
-#pragma unroll 4
-        for (int k = 0; k < RT / 4; ++k) {
-          const float4 v = reinterpret_cast<const float4*>(sX)[k];
-          const int k4 = 4 * k;
-          less += (v.x < xi) + (v.y < xi) + (v.z < xi) + (v.w < xi);
-          e += (v.x == xi) + (v.y == xi) + (v.z == xi) + (v.w == xi);
-          before += ((v.x == xi) & (k4 < d)) + ((v.y == xi) & (k4 + 1 < d)) + ((v.z == xi) & (k4 + 2 < d)) + ((v.w == xi) & (k4 + 3 < d));
-        }
+        rank_count_tile<true>(sX, xi, less, e, &before, i - j0);          // j < i  <=>  k < i - j0
       }
       eq += e;
     }
@@ -307,7 +277,6 @@ __global__ __launch_bounds__(NT) void sel_final_kernel(const Args a) {
   }
 }
 
-static inline bool aligned_to(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 static inline bool limits_ok(int n, int S, int K) {
   return n >= 1 && n <= ROVIT_EVAL_MAX_ROWS && S >= 1 && S <= MS && K >= 1 && K <= MK;
 }
@@ -333,7 +302,7 @@ extern "C" int rovit_eval_selective(const rovit_eval_sel* p, rovit_stream_t stre
     ROVIT_CHECK_ARG(kind >= ROVIT_EVAL_SEL_CONFIDENCE && kind <= ROVIT_EVAL_SEL_SCORE_COLUMN, ROVIT_ERR_SHAPE, "%s: score %d has the unknown kind %d",
                     who, s, kind);
     ROVIT_CHECK_ARG(kind != ROVIT_EVAL_SEL_SCORE_COLUMN || p->score_column[s], ROVIT_ERR_NULL, "%s: score %d is a column with a null pointer", who, s);
-    ROVIT_CHECK_ARG(kind != ROVIT_EVAL_SEL_SCORE_COLUMN || aligned_to(p->score_column[s], 4), ROVIT_ERR_ALIGN,
+    ROVIT_CHECK_ARG(kind != ROVIT_EVAL_SEL_SCORE_COLUMN || rovit_aligned(p->score_column[s], 4), ROVIT_ERR_ALIGN,
                     "%s: the column of score %d is not aligned to its element size", who, s);
     need_sigma |= kind == ROVIT_EVAL_SEL_SIGMA;
   }
@@ -342,7 +311,7 @@ extern "C" int rovit_eval_selective(const rovit_eval_sel* p, rovit_stream_t stre
     ROVIT_CHECK_ARG(kind >= ROVIT_EVAL_SEL_ERROR && kind <= ROVIT_EVAL_SEL_RISK_COLUMN, ROVIT_ERR_SHAPE, "%s: risk %d has the unknown kind %d", who,
                     k, kind);
     ROVIT_CHECK_ARG(kind != ROVIT_EVAL_SEL_RISK_COLUMN || p->risk_column[k], ROVIT_ERR_NULL, "%s: risk %d is a column with a null pointer", who, k);
-    ROVIT_CHECK_ARG(kind != ROVIT_EVAL_SEL_RISK_COLUMN || aligned_to(p->risk_column[k], 4), ROVIT_ERR_ALIGN,
+    ROVIT_CHECK_ARG(kind != ROVIT_EVAL_SEL_RISK_COLUMN || rovit_aligned(p->risk_column[k], 4), ROVIT_ERR_ALIGN,
                     "%s: the column of risk %d is not aligned to its element size", who, k);
     need_class |= kind == ROVIT_EVAL_SEL_ERROR;
     need_sev |= kind == ROVIT_EVAL_SEL_ABS_ERR;
@@ -354,7 +323,7 @@ extern "C" int rovit_eval_selective(const rovit_eval_sel* p, rovit_stream_t stre
   ROVIT_CHECK_ARG(rovit_aligned16(p->probs) && rovit_aligned16(p->pred) && rovit_aligned16(p->label) && rovit_aligned16(p->sev_pred) &&
                       rovit_aligned16(p->sev_true) && rovit_aligned16(p->uncertainty),
                   ROVIT_ERR_ALIGN, "%s: a record array is not 16-byte aligned", who);
-  ROVIT_CHECK_ARG(rovit_aligned16(p->workspace) && aligned_to(p->result, 8) && aligned_to(p->keys_out, 4) && aligned_to(p->risks_out, 4),
+  ROVIT_CHECK_ARG(rovit_aligned16(p->workspace) && rovit_aligned(p->result, 8) && rovit_aligned(p->keys_out, 4) && rovit_aligned(p->risks_out, 4),
                   ROVIT_ERR_ALIGN, "%s: the workspace, the result block or a matrix to leave behind is not aligned", who);
   const Layout l = layout(n, S, K);
   ROVIT_CHECK_ARG(p->workspace_bytes >= l.total, ROVIT_ERR_SHAPE, "%s: the workspace holds %zu bytes, %zu are needed", who, p->workspace_bytes,
@@ -370,7 +339,7 @@ extern "C" int rovit_eval_selective(const rovit_eval_sel* p, rovit_stream_t stre
   a.csum = (double*)(ws + l.csum);
   a.rsum = (double*)(ws + l.rsum);
   a.result = p->result;
-  const int cols = S + K, Q = S * K + K, ntiles = (n + RT - 1) / RT;
+  const int cols = S + K, Q = S * K + K, ntiles = (n + RANK_RT - 1) / RANK_RT;
   const size_t words = ROVIT_EVAL_SEL_WORDS(S, K, P);
   hipStream_t s = (hipStream_t)stream;
   if (hipMemsetAsync(a.cnt, 0, l.local - l.cnt, s) != hipSuccess || hipMemsetAsync(p->result, 0, words * 8, s) != hipSuccess) {

@@ -8,7 +8,7 @@
 // call joint_loss::row and joint_loss::reduce of joint_loss_row.h.  Only the focal term depends on the class label, so
 // lam L(a) + (1 - lam) L(b) is the same single pass with a second label column.  Thread 0 writes the batch's row of the epoch
 // table; the host hands out the row index, so a row has one writer and the table needs neither a counter nor an atomic.
-// train_final_kernel adds the rows in a fixed order (strided per thread, then the fixed tree of block_sum_t) in fp64.
+// train_final_kernel adds the rows in a fixed order (strided per thread, then the fixed tree of common.h's block_sum_t) in fp64.
 #include "common.h"
 #include "joint_loss_row.h"
 
@@ -27,12 +27,6 @@ struct MixedArgs {
   unsigned* table;               // (capacity, RW) 4-byte words or NULL
   int row;
 };
-
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
-  return v;
-}
 
 __global__ __launch_bounds__(NT) void joint_loss_mixed_kernel(const MixedArgs m) {
   __shared__ float s_red[4];
@@ -53,7 +47,7 @@ __global__ __launch_bounds__(NT) void joint_loss_mixed_kernel(const MixedArgs m)
     a.out[4] = r[4];
   }
   if (!m.table) return;                          // uniform: a kernel argument
-  correct = wave_sum_i(correct);
+  correct = wave_sum_t(correct);
   if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = correct;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -63,23 +57,6 @@ __global__ __launch_bounds__(NT) void joint_loss_mixed_kernel(const MixedArgs m)
     w[ROVIT_TRAIN_ROW_BATCH] = (unsigned)a.B;
     w[ROVIT_TRAIN_ROW_NONFINITE] = isfinite(r[4]) ? 0u : 1u;
   }
-}
-
-// all 64 lanes receive the same sum: at every step both partners add the same two values
-template <typename T>
-__device__ __forceinline__ T wave_sum_t(T v) {
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
-  return v;
-}
-// sum over the workgroup's four waves in wave order; s4: 4 values of LDS
-template <typename T>
-__device__ __forceinline__ T block_sum_t(T v, T* s4) {
-  v = wave_sum_t(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((s4[0] + s4[1]) + s4[2]) + s4[3];
 }
 
 __global__ __launch_bounds__(NT) void train_final_kernel(const unsigned* __restrict__ table, int n_rows, long long* __restrict__ result) {
@@ -111,8 +88,6 @@ __global__ __launch_bounds__(NT) void train_final_kernel(const unsigned* __restr
   }
 }
 
-static inline bool aligned_to(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 }  // namespace
 
 extern "C" int rovit_joint_loss_mixed(const rovit_train_loss* p, rovit_stream_t stream) {
@@ -127,12 +102,12 @@ extern "C" int rovit_joint_loss_mixed(const rovit_train_loss* p, rovit_stream_t 
   ROVIT_CHECK_ARG(!p->class_targets_b || (p->lam >= 0.f && p->lam <= 1.f), ROVIT_ERR_SHAPE, "%s: lam %g outside [0, 1]", who, (double)p->lam);
   ROVIT_CHECK_ARG(!p->table || (p->row >= 0 && p->capacity >= 1 && p->capacity <= ROVIT_TRAIN_MAX_ROWS && p->row < p->capacity), ROVIT_ERR_SHAPE,
                   "%s: row %d outside the epoch table (%d rows, at most %d)", who, p->row, p->capacity, ROVIT_TRAIN_MAX_ROWS);
-  ROVIT_CHECK_ARG(aligned_to(p->cls_logits, 4) && aligned_to(p->ordinal_logits, 4) && aligned_to(p->mu, 4) && aligned_to(p->log_var, 4) &&
-                      aligned_to(p->kan_severity, 4) && aligned_to(p->focal_alpha, 4) && aligned_to(p->class_targets_a, 8) &&
-                      aligned_to(p->class_targets_b, 8) && aligned_to(p->severity_targets, p->severity_is_int64 ? 8 : 4),
+  ROVIT_CHECK_ARG(rovit_aligned(p->cls_logits, 4) && rovit_aligned(p->ordinal_logits, 4) && rovit_aligned(p->mu, 4) && rovit_aligned(p->log_var, 4) &&
+                      rovit_aligned(p->kan_severity, 4) && rovit_aligned(p->focal_alpha, 4) && rovit_aligned(p->class_targets_a, 8) &&
+                      rovit_aligned(p->class_targets_b, 8) && rovit_aligned(p->severity_targets, p->severity_is_int64 ? 8 : 4),
                   ROVIT_ERR_ALIGN, "%s: an input pointer is not aligned to its element size", who);
-  ROVIT_CHECK_ARG(aligned_to(p->d_cls, 4) && aligned_to(p->d_ord, 4) && aligned_to(p->d_mu, 4) && aligned_to(p->d_lv, 4) && aligned_to(p->d_kan, 4) &&
-                      aligned_to(p->losses_out, 4) && aligned_to(p->table, 4),
+  ROVIT_CHECK_ARG(rovit_aligned(p->d_cls, 4) && rovit_aligned(p->d_ord, 4) && rovit_aligned(p->d_mu, 4) && rovit_aligned(p->d_lv, 4) && rovit_aligned(p->d_kan, 4) &&
+                      rovit_aligned(p->losses_out, 4) && rovit_aligned(p->table, 4),
                   ROVIT_ERR_ALIGN, "%s: an output pointer is not 4-byte aligned", who);
   MixedArgs m{};
   m.l = LossArgs{p->cls_logits, p->ordinal_logits, p->mu, p->log_var, p->kan_severity, p->class_targets_a, p->severity_targets,
@@ -153,7 +128,7 @@ extern "C" int rovit_train_finalize(const rovit_train_final* p, rovit_stream_t s
   ROVIT_CHECK_ARG(p->table && p->result, ROVIT_ERR_NULL, "%s: the epoch table or the result block is missing (null pointer)", who);
   ROVIT_CHECK_ARG(p->n_rows >= 1 && p->n_rows <= p->capacity && p->capacity <= ROVIT_TRAIN_MAX_ROWS, ROVIT_ERR_SHAPE,
                   "%s: %d rows of a table of %d (1..capacity, at most %d)", who, p->n_rows, p->capacity, ROVIT_TRAIN_MAX_ROWS);
-  ROVIT_CHECK_ARG(aligned_to(p->table, 4) && aligned_to(p->result, 8), ROVIT_ERR_ALIGN, "%s: the table or the result block is not aligned", who);
+  ROVIT_CHECK_ARG(rovit_aligned(p->table, 4) && rovit_aligned(p->result, 8), ROVIT_ERR_ALIGN, "%s: the table or the result block is not aligned", who);
   hipLaunchKernelGGL(train_final_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, (const unsigned*)p->table, p->n_rows, (long long*)p->result);
   ROVIT_CHECK_LAUNCH("train_final_kernel");
   return ROVIT_OK;

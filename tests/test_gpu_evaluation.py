@@ -148,6 +148,24 @@ def test_result_block_is_bit_reproducible_and_independent_of_the_batch_split():
     assert (m['cls_loss'], m['ord_loss'], m['unc_loss'], m['kan_loss'], m['loss']) == (0.25, 0.5, 0.125, 1.0, 1.875)
 
 
+@pytest.mark.parametrize('n', [1023, 1024, 1025])
+def test_rho_with_ties_around_the_rank_tile(n):
+    """The counting rank stages 1024 rows per LDS tile: a last tile one short, exactly full, and a single row in a new tile (there the
+    row range is also split over two workgroups).  Tie-heavy columns, so both the `less` and the `equal` counts matter."""
+    from scipy.stats import spearmanr
+    from rovit_hip.evaluation import EvalAccumulator
+    d = _data(n, 4, seed=n, ties=True)
+    acc = EvalAccumulator(4)
+    _feed(acc, d, (512,))
+    m = acc.compute()
+    want = float(spearmanr(d['sev_true'].numpy(), d['sev_pred'].double().numpy())[0])
+    print(f"n={n}: rho {m['spearman_rho']!r} scipy {want!r} diff {abs(m['spearman_rho'] - want):.3e}")
+    assert m['n'] == n and abs(m['spearman_rho'] - want) <= 1e-12
+    again = EvalAccumulator(4)
+    _feed(again, d, (1, 7, 300))
+    assert again.result_block().tobytes() == acc.result_block().tobytes(), 'the result block depends on the batch split'
+
+
 def test_ties_and_degenerate_inputs():
     from scipy.stats import spearmanr
     from rovit_hip.evaluation import EvalAccumulator

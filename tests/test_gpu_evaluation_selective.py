@@ -30,7 +30,9 @@ ROUNDED = (['conf2', 'ent2', 'sig2'], ['error', 'abs_err'])
 WIDE = (['confidence', 'entropy', 'sigma', 'mu', 'c1', 'c2', 'c3', 'c4'], ['error', 'abs_err', 'mu_abs_err', 'r3'])
 # name: (n, scores and risks, P)
 CASES = {'n1': (1, BUILTIN, 20), 'n2': (2, BUILTIN, 20), 'n5_all_tied': (5, BUILTIN, 20), 'n257': (257, BUILTIN, 20),
-         'n1000_two_decimals': (1000, ROUNDED, 20), 'n1027': (1027, BUILTIN, 20), 'n2051': (2051, BUILTIN, 20), 'n257_wide': (257, WIDE, 256)}
+         'n1000_two_decimals': (1000, ROUNDED, 20), 'n1027': (1027, BUILTIN, 20), 'n2051': (2051, BUILTIN, 20), 'n257_wide': (257, WIDE, 256),
+         # around the 1024-row LDS tile of the counting rank: last tile one short, exactly full, one row in a new tile
+         'n1023': (1023, BUILTIN, 20), 'n1024': (1024, BUILTIN, 20), 'n1025': (1025, BUILTIN, 20)}
 
 
 def dev():
