@@ -1193,6 +1193,90 @@ size_t rovit_knn_workspace_bytes(int batch, int n, int embed, int k);
 int rovit_knn_build(const rovit_knn_index* p, rovit_stream_t stream);
 int rovit_knn_search(const rovit_knn_query* p, rovit_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Last-layer Laplace approximation of the heads (laplace.hip): how well do the training rows determine a head's last linear layer at
+ * this feature row?  Generalised Gauss-Newton Hessian over the last layer (Kristiadi et al., ICML 2020; Daxberger et al., NeurIPS 2021).
+ * A head is fc1 (hid, E) + bias, ReLU, then the last layer; a = [relu(fc1 f + b1); 1] is the augmented hidden row of a feature row f,
+ * D = hid + 1 wide, and P = hid + 32 is D padded to a multiple of 32 with exact zeros.  The Grams and the whitening are exact fp32
+ * (v_mfma_f32_32x32x2_f32); a is the correctly rounded hidden row (fp64 accumulation).  Eval semantics (no dropout).
+ *
+ * rovit_laplace_weights, one pointwise launch.  With cls_logits (n, C) not NULL: cls_weights (n, K), K = C (C + 1) / 2, column k the
+ * pair (c, d), c <= d, row-major over the upper triangle: lambda_cc = p_c (1 - p_c), lambda_cd = -p_c p_d, p = softmax(logits) in fp64
+ * as e_c = exp(l_c - max), p_c (1 - p_c) = e_c (sum_{d != c} e_d) / s^2, rounded to fp32 once.  With log_var (n) not NULL: mu_weights (n)
+ * = exp(-log_var) in fp64, rounded once.  A row with a non-finite logit (a non-finite log_var, or one whose weight is not finite in
+ * fp32) gets weight 0 in every column and is counted: counts[ROVIT_LAPLACE_BAD_LOGITS], counts[ROVIT_LAPLACE_BAD_LOG_VAR] (int64, zeroed
+ * first, integer atomics).  Limits: 1 <= n <= ROVIT_KAN_STATS_MAX_ROWS, 1 <= C <= ROVIT_EVAL_MAX_CLASSES; at least one of the two inputs.
+ *
+ * rovit_laplace_gram: features (n, E), fc1_weight (hid, E), fc1_bias (hid), weights (n, K) fp32.  result, ROVIT_LAPLACE_WORDS(hid, K)
+ * 8-byte words:
+ *   int64  [ROVIT_LAPLACE_N]  [_N_VALID]  [_BAD_ROWS]   (words up to _HEADER are 0)
+ *   double at _HEADER: G_k[a][b] = sum_i w_ik a_ia a_ib, (K, D, D), every matrix exactly symmetric
+ * A row with a non-finite feature or a non-finite weight is left out and counted in BAD_ROWS.  Three kernels: the hidden rows of 64-row
+ * tiles (fc1 accumulated in fp64 on the vector unit, rounded to fp32 once after the bias and the ReLU) into the workspace, padded to P;
+ * per (chunk, k) the upper tile triangle of A^T (w_k A) over 32-row slabs in LDS, rows of the chunk in order along k of the matrix
+ * instruction, one partial per (chunk, k); the fold, per element the chunk partials in fp64 in chunk order, written to [a][b] and [b][a].
+ * A chunk is R = 256 ceil(n / (256 ROVIT_LAPLACE_MAX_CHUNKS)) consecutive rows, a function of n alone.  No floating-point atomic: the
+ * block is bit-identical from run to run, for every way the rows arrived and for every grid (max_workgroups > 0 caps the grid of every
+ * kernel; work items are walked with a stride of the grid).  Every word of the block is written.
+ * workspace: rovit_laplace_workspace_bytes(n, E, hid, K) bytes, 16-byte aligned (0 for sizes outside the limits).
+ * Limits: E a multiple of 32 in 32..256, hid a multiple of 32 in 32..256, 1 <= K <= ROVIT_LAPLACE_MAX_WEIGHTS, 1 <= n <=
+ * ROVIT_KAN_STATS_MAX_ROWS; features and fc1_weight 16-byte aligned.
+ *
+ * rovit_laplace_predict: features (B, E), any B >= 1, fc1 as above, whitening W (C P, C P) fp32 row-major, W = R^-1 of the posterior
+ * precision R R^T in the padded, class-major parameter order (index c P + a).  W is LOWER-TRIANGULAR: of row tile (class block t, tile
+ * at) the kernel reads the columns of the class blocks c < t in full and of block t up to the diagonal tile; nothing right of it is read,
+ * and the entries above the diagonal inside the diagonal tile must be zero.  With z_c = W[:, block c] a (length C P):
+ *   logit_cov (B, C, C) S[c][d] = z_c . z_d, symmetric (computed once, written twice)      logit_var (B, C) S[c][c]
+ *   with cls_logits (B, C) not NULL: probs (B, C) = softmax(l_c / sqrt(1 + (pi / 8) S_cc)) in fp64, rounded once; confidence_score (B)
+ *   = 1 - max probs, as rest / sum; mean_logit_var (B) = the mean of S_cc in fp64, rounded once
+ * C = 1 serves a Gaussian head: logit_var is then the epistemic variance of mu.  One launch; a workgroup owns ROVIT_LAPLACE_TILE rows
+ * (the last tile may be partial), forms their hidden rows in LDS (never in memory) and streams W in 32-row tiles, one query row per
+ * lane of the accumulators; S is one fp32 fma chain per lane in a fixed order, four partial chains added in a fixed order: the same bits
+ * from run to run and for every grid.  A non-finite feature gives non-finite outputs in its own row only.
+ * Limits: E and hid as above, 1 <= C <= ROVIT_EVAL_MAX_CLASSES; features, fc1_weight and whitening 16-byte aligned.
+ * A bad descriptor is refused before any launch, by all three.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define ROVIT_LAPLACE_MAX_WEIGHTS 36
+#define ROVIT_LAPLACE_MAX_CHUNKS 64
+#define ROVIT_LAPLACE_TILE 64
+enum { ROVIT_LAPLACE_BAD_LOGITS = 0, ROVIT_LAPLACE_BAD_LOG_VAR = 1, ROVIT_LAPLACE_COUNT_WORDS = 2 };
+enum { ROVIT_LAPLACE_N = 0, ROVIT_LAPLACE_N_VALID = 1, ROVIT_LAPLACE_BAD_ROWS = 2, ROVIT_LAPLACE_HEADER = 8 };
+#define ROVIT_LAPLACE_WORDS(hid, K) ((size_t)ROVIT_LAPLACE_HEADER + (size_t)(K) * ((hid) + 1) * ((hid) + 1))
+typedef struct rovit_laplace_weight_args {
+  int n, num_classes, max_workgroups, reserved;
+  const float* cls_logits;           /* (n, num_classes) or NULL */
+  const float* log_var;              /* (n) or NULL */
+  float* cls_weights;                /* (n, C (C + 1) / 2); with cls_logits */
+  float* mu_weights;                 /* (n); with log_var */
+  long long* counts;                 /* ROVIT_LAPLACE_COUNT_WORDS */
+} rovit_laplace_weight_args;
+typedef struct rovit_laplace_fit {
+  int n, embed, hid, num_weights, max_workgroups, reserved;
+  const float* features;             /* (n, embed) */
+  const float* fc1_weight;           /* (hid, embed) */
+  const float* fc1_bias;             /* (hid) */
+  const float* weights;              /* (n, num_weights) */
+  void* workspace;
+  size_t workspace_bytes;
+  void* result;                      /* ROVIT_LAPLACE_WORDS(hid, num_weights) 8-byte words */
+} rovit_laplace_fit;
+typedef struct rovit_laplace_query {
+  int batch, embed, hid, num_classes, max_workgroups, reserved;
+  const float* features;             /* (batch, embed) */
+  const float* fc1_weight;           /* (hid, embed) */
+  const float* fc1_bias;             /* (hid) */
+  const float* whitening;            /* (C P, C P), P = hid + 32, lower-triangular */
+  const float* cls_logits;           /* (batch, num_classes) or NULL */
+  float* logit_cov;                  /* (batch, num_classes, num_classes) */
+  float* logit_var;                  /* (batch, num_classes) */
+  float* probs;                      /* (batch, num_classes); with cls_logits */
+  float* confidence_score; float* mean_logit_var;   /* (batch) each; with cls_logits */
+} rovit_laplace_query;
+int rovit_laplace_weights(const rovit_laplace_weight_args* p, rovit_stream_t stream);
+size_t rovit_laplace_workspace_bytes(int n, int embed, int hid, int num_weights);
+int rovit_laplace_gram(const rovit_laplace_fit* p, rovit_stream_t stream);
+int rovit_laplace_predict(const rovit_laplace_query* p, rovit_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

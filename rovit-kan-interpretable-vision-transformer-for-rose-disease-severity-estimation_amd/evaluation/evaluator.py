@@ -19,7 +19,12 @@ records each row's distance to its k-th nearest training feature as the extra co
 card) and adds ``metrics['knn']``: how well the neighbour-weighted vote alone classifies and estimates severity, and how often it agrees
 with the classification head; ``evaluate_ood(..., index=fi)`` adds the ``'knn'`` card.
 ``evaluate_corruptions(store_or_loader)`` is the corruption-robustness score card: the test images corrupted on the device from the uint8
-store (``rovit_hip.corrupt``), one card per (corruption, severity) cell, the corruption errors and, against a baseline, CE and mCE."""
+store (``rovit_hip.corrupt``), one card per (corruption, severity) cell, the corruption errors and, against a baseline, CE and mCE.
+``fit_laplace(train_loader)`` fits the last-layer Laplace approximation of the heads (``rovit_hip.laplace.HeadLaplace``);
+``evaluate(laplace=la)`` records each row's mean logit variance and, from stage 3, the total standard deviation of ``mu`` as the extra
+columns ``laplace_logit_var`` and ``laplace_mu_std`` (two more scores of the selective card) and adds ``metrics['laplace']``: the prior
+precisions, and NLL, ECE, Brier score and accuracy before and after the probit adjustment; ``evaluate_ood(..., laplace=la)`` adds the
+``'laplace'`` card."""
 from pathlib import Path
 from typing import Dict
 
@@ -45,23 +50,34 @@ class Evaluator:
         self.conformal = None
         self.index = None
         self._knn_tally = None
+        self.laplace = None
+        self._laplace_acc = None
 
     MC_COLUMNS = ('predictive_entropy_mc', 'mutual_information', 'epistemic_var', 'uncertainty_std')
 
     DENSITY_COLUMNS = ('mahalanobis', 'relative_mahalanobis')
     KNN_COLUMN = 'knn_distance'
+    LAPLACE_COLUMNS = ('laplace_logit_var', 'laplace_mu_std')
     OOD_LEVEL = 0.95
 
     def collect(self, selective: bool = False, mc_samples: int = 0, mc_seed: int = 0, record_mu: bool = False, density=None, index=None,
-                knn_k: int = 10) -> EvalAccumulator:
+                knn_k: int = 10, laplace=None) -> EvalAccumulator:
         """The collection loop alone: one forward and one record launch per batch, nothing copied to the host.  ``selective`` (or
         ``record_mu``) also records the uncertainty head's ``mu`` as an extra column when the model returns one; ``mc_samples = T > 0``
         adds the MC-dropout columns of ``model.predict_mc(images, num_samples=T, seed=mc_seed, offset=batch index)``, a SECOND backbone
         pass per batch."""
         if mc_samples and not selective:
             raise RovitHipError('Evaluator: mc_samples records columns for the selective score card; pass selective=True with it')
-        acc = self.accumulator = self._collect(self.test_loader, selective, mc_samples, mc_seed, record_mu, density, index, knn_k)
+        acc = self.accumulator = self._collect(self.test_loader, selective, mc_samples, mc_seed, record_mu, density, index, knn_k, laplace)
         return acc
+
+    def fit_laplace(self, loader, prior_precision='marglik'):
+        """Fit the last-layer Laplace approximation of the heads (``RoViTKAN.fit_laplace``) on another split, normally the training
+        loader: one forward pass, the weighted Grams on the GPU, one device-to-host copy, the factorisation on the host.  No labels are
+        read.  The ``HeadLaplace`` is returned and kept on ``self.laplace``; pass it to ``evaluate(laplace=...)`` or
+        ``evaluate_ood(..., laplace=...)``."""
+        self.laplace = self.model.fit_laplace(loader, prior_precision=prior_precision)
+        return self.laplace
 
     def fit_index(self, loader, metric: str = 'cosine'):
         """Record the backbone features of another split, normally the training loader, with their class labels and severities in a
@@ -92,9 +108,10 @@ class Evaluator:
         return self.conformal
 
     def _collect(self, loader, selective: bool, mc_samples: int, mc_seed: int, record_mu: bool, density=None, index=None,
-                 knn_k: int = 10) -> EvalAccumulator:
+                 knn_k: int = 10, laplace=None) -> EvalAccumulator:
         acc = EvalAccumulator(len(self.config.data.class_names))
         self._knn_tally = [] if index is not None else None
+        self._laplace_acc = EvalAccumulator(len(self.config.data.class_names)) if laplace is not None else None
         self.model.eval()
         with torch.no_grad():
             for batch_index, (images, class_labels, severity_labels) in enumerate(loader):
@@ -116,6 +133,14 @@ class Evaluator:
                     nn = index.search(outputs['features'], k=knn_k)
                     extra[self.KNN_COLUMN] = nn['kth_distance']
                     self._knn_tally.append(self._knn_row(nn, outputs, class_labels, severity_labels))
+                if laplace is not None:
+                    la = laplace.predict(outputs['features'], outputs['cls_logits'], outputs.get('mu'), outputs.get('log_var'))
+                    extra[self.LAPLACE_COLUMNS[0]] = la['mean_logit_var']
+                    if 'total_std' in la:                         # from curriculum stage 3
+                        extra[self.LAPLACE_COLUMNS[1]] = la['total_std']
+                    # the same rows with the probit-adjusted probabilities in place of the softmax: softmax(log p') = p'
+                    adjusted = dict(outputs, cls_logits=torch.log(la['probs'].clamp_min(torch.finfo(torch.float32).tiny)))
+                    self._laplace_acc.update(adjusted, class_labels, severity_labels)
                 acc.update(outputs, class_labels, severity_labels, extra=extra or None)
         return acc
 
@@ -147,7 +172,8 @@ class Evaluator:
                 'severity_mae': err / rows if index.has_severity and rows > 0 else None, 'agreement': agree / rows if voted else None}
 
     def evaluate(self, return_arrays: bool = False, bootstrap: int = 0, bootstrap_seed: int = 0, selective: bool = False,
-                 mc_samples: int = 0, mc_seed: int = 0, calibration=None, density=None, conformal=None, index=None, knn_k: int = 10):
+                 mc_samples: int = 0, mc_seed: int = 0, calibration=None, density=None, conformal=None, index=None, knn_k: int = 10,
+                 laplace=None):
         """``selective=True`` adds ``metrics['selective']`` (``EvalAccumulator.selective`` with 20 coverages: the built-in scores, and
         with ``mc_samples = T > 0`` the MC-dropout scores predictive_entropy_mc and mutual_information, from curriculum stage 3 also
         epistemic_var and uncertainty_std) and a "Selective prediction" section in the table and the file.  The MC columns cost a
@@ -172,11 +198,18 @@ class Evaluator:
         to its ``knn_k``-th nearest recorded feature, as an extra column (one more search per batch; with ``selective=True`` one more
         score of the card), and adds ``metrics['knn']`` = ``{'k', 'accuracy', 'severity_mae', 'agreement'}``: accuracy (per cent) and
         severity MAE of the neighbour-weighted vote alone, and the share of rows where the vote and the classification head agree, all
-        three over the rows that have at least one neighbour; a "Nearest neighbours" section goes into the table and the file."""
+        three over the rows that have at least one neighbour; a "Nearest neighbours" section goes into the table and the file.
+
+        ``laplace`` (a fitted ``HeadLaplace``, normally ``fit_laplace(train_loader)``) records ``laplace_logit_var``, the mean over the
+        classes of every row's closed-form logit variance, and from stage 3 ``laplace_mu_std`` = sqrt(sigma^2 + the epistemic variance
+        of mu) as extra columns (one launch per head and batch; with ``selective=True`` two more scores of the card), and adds
+        ``metrics['laplace']`` = ``{'prior_precision', 'status', 'prior_precision_mu', 'status_mu', 'n', 'before', 'after'}``: ``before``
+        and ``after`` hold ``nll``, ``ece``, ``brier_score`` and ``accuracy`` of the softmax and of the probit-adjusted probabilities; a
+        "Laplace approximation" section goes into the table and the file."""
         print(f'\n{RULE}\nRunning Evaluation on Test Set\n{RULE}\n')
         names = list(self.config.data.class_names)
         acc = self.collect(selective, mc_samples, mc_seed, record_mu=calibration is not None or conformal is not None, density=density,
-                           index=index, knn_k=knn_k)
+                           index=index, knn_k=knn_k, laplace=laplace)
         ci = acc.bootstrap(bootstrap, seed=bootstrap_seed) if bootstrap else None          # brings the point block along in its one copy
         m = acc.compute()                                   # the loop's one synchronisation
         metrics = {k: m[k] for k in ('accuracy', 'macro_f1', 'weighted_f1', 'mae', 'spearman_rho', 'spearman', 'brier_score', 'ece')}
@@ -189,7 +222,7 @@ class Evaluator:
             metrics['confidence_intervals'] = ci
         if selective:
             have = acc._extra_names or ()
-            scores = ['confidence', 'entropy'] + (['sigma'] if acc._has_uncertainty else []) + [c for c in self.MC_COLUMNS + self.DENSITY_COLUMNS + (self.KNN_COLUMN,) if c in have]
+            scores = ['confidence', 'entropy'] + (['sigma'] if acc._has_uncertainty else []) + [c for c in self.MC_COLUMNS + self.DENSITY_COLUMNS + (self.KNN_COLUMN,) + self.LAPLACE_COLUMNS if c in have]
             risks = ['error', 'abs_err'] + (['mu_abs_err'] if 'mu' in have else [])
             metrics['selective'] = acc.selective(scores=scores, risks=risks)
         if calibration is not None:
@@ -202,11 +235,20 @@ class Evaluator:
             metrics['conformal'] = conformal.evaluate(acc)
         if index is not None:
             metrics['knn'] = self._knn_card(index, knn_k)
+        if laplace is not None:
+            metrics['laplace'] = self._laplace_card(laplace, acc, m)
         self._print_results(metrics)
         self._save_results(metrics)
         return (metrics, acc.arrays()) if return_arrays else metrics
 
-    def _ood_columns(self, loader, density, index=None, knn_k: int = 10) -> Dict[str, torch.Tensor]:
+    def _laplace_card(self, laplace, acc: EvalAccumulator, m: Dict) -> Dict:
+        """``metrics['laplace']``: the fit's prior precisions, and the record as it is beside the record with the probit-adjusted
+        probabilities (``_collect`` filled it), each by its own ``compute()`` and a ``calibrate()`` whose NLL at T = 1 describes it."""
+        side = lambda a, mm: {'nll': a.calibrate().diagnostics['nll'], 'ece': mm['ece'], 'brier_score': mm['brier_score'], 'accuracy': mm['accuracy']}
+        return {'prior_precision': laplace.prior_precision, 'status': laplace.status, 'prior_precision_mu': laplace.prior_precision_mu,
+                'status_mu': laplace.status_mu, 'n': laplace.n, 'before': side(acc, m), 'after': side(self._laplace_acc, self._laplace_acc.compute())}
+
+    def _ood_columns(self, loader, density, index=None, knn_k: int = 10, laplace=None) -> Dict[str, torch.Tensor]:
         """The anomaly scores of every image of a loader as device columns: nothing is copied to the host."""
         cols: Dict[str, list] = {}
         self.model.eval()
@@ -225,19 +267,22 @@ class Evaluator:
                     row.update({k: d[k] for k in self.DENSITY_COLUMNS})
                 if index is not None:
                     row['knn'] = index.search(out['features'], k=knn_k)['kth_distance']
+                if laplace is not None:
+                    row['laplace'] = laplace.predict(out['features'], out['cls_logits'])['mean_logit_var']
                 for k, v in row.items():
                     cols.setdefault(k, []).append(v)
         return {k: torch.cat(v) for k, v in cols.items()}
 
-    def evaluate_ood(self, ood_loader, density=None, index=None, knn_k: int = 10) -> Dict[str, Dict]:
+    def evaluate_ood(self, ood_loader, density=None, index=None, knn_k: int = 10, laplace=None) -> Dict[str, Dict]:
         """Extension (not in the reference): how well each uncertainty score tells the test set (in-distribution) from ``ood_loader``
         (out-of-distribution; batches of images, or tuples whose first element is the images).  One ``rovit_hip.density.ood_metrics``
         card per score (AUROC, AUPR both ways, FPR at 95 % TPR; one device-to-host copy each): ``max_prob`` = 1 - max p, ``entropy``,
         ``energy`` = -logsumexp, ``sigma`` when the model returns log_var, and with a fitted ``density`` ``mahalanobis`` and
         ``relative_mahalanobis``, and with a built ``index`` (a ``FeatureIndex``) ``knn``, the distance to the ``knn_k``-th nearest
-        recorded feature (Sun et al. 2022).  Printed as a table; higher = more anomalous for every score."""
+        recorded feature (Sun et al. 2022), and with a fitted ``laplace`` (a ``HeadLaplace``) ``laplace``, the mean closed-form logit
+        variance.  Printed as a table; higher = more anomalous for every score."""
         from rovit_hip.density import ood_metrics
-        inside, outside = self._ood_columns(self.test_loader, density, index, knn_k), self._ood_columns(ood_loader, density, index, knn_k)
+        inside, outside = (self._ood_columns(l, density, index, knn_k, laplace) for l in (self.test_loader, ood_loader))
         cards = {k: ood_metrics(inside[k], outside[k], tpr_levels=(self.OOD_LEVEL,)) for k in inside if k in outside}
         lines = ['', 'Out-of-distribution detection:', f"{'Score':<24}{'AUROC':>10}{'AUPR-out':>10}{'AUPR-in':>10}{'FPR@95%TPR':>12}", '-' * 66]
         for k, c in cards.items():
@@ -446,6 +491,20 @@ class Evaluator:
         return [f"Nearest neighbours (k = {card['k']}):", f"{'Vote accuracy:':<22}{num(card['accuracy'], '.2f')}%",
                 f"{'Vote severity MAE:':<22}{num(card['severity_mae'], '.4f')}", f"{'Agreement with head:':<22}{num(card['agreement'], '.4f')}", '']
 
+    @staticmethod
+    def _laplace_lines(metrics: Dict):
+        """The prior precisions with their status, then NLL, ECE, Brier score and accuracy before and after the probit adjustment."""
+        card = metrics.get('laplace')
+        if card is None:
+            return []
+        mu = '' if card['prior_precision_mu'] is None else f", mu head {card['prior_precision_mu']:.4g} ({card['status_mu']})"
+        lines = [f"Laplace approximation (n = {card['n']}, prior precision {card['prior_precision']:.4g} ({card['status']}){mu}):",
+                 f"{'':<10}{'NLL':>10}{'ECE':>10}{'Brier':>10}{'Accuracy':>10}", '-' * 50]
+        for side in ('before', 'after'):
+            c = card[side]
+            lines.append(f"{side:<10}{c['nll']:>10.4f}{c['ece']:>10.4f}{c['brier_score']:>10.4f}{c['accuracy']:>9.2f}%")
+        return lines + ['']
+
     def _print_results(self, metrics: Dict) -> None:
         print('\n'.join(['', RULE, 'Evaluation Results', RULE] + self._summary(metrics, 'Spearman rho:') + [RULE, '']))
         if 'selective' in metrics:
@@ -456,6 +515,8 @@ class Evaluator:
             print('\n'.join(self._conformal_lines(metrics)))
         if 'knn' in metrics:
             print('\n'.join(self._knn_lines(metrics)))
+        if 'laplace' in metrics:
+            print('\n'.join(self._laplace_lines(metrics)))
         print('Per-Class Metrics:')
         print(f"{'Class':<20} {'Precision':<12} {'Recall':<12} {'F1-Score':<12} {'Support':<10}")
         print('-' * 70)
@@ -473,7 +534,7 @@ class Evaluator:
         for name, c in metrics['per_class'].items():
             lines += [f'{name}:', f"  Precision: {c['precision']:.2f}%", f"  Recall:    {c['recall']:.2f}%", f"  F1-Score:  {c['f1']:.2f}%",
                       f"  Support:   {c['support']}", '']
-        lines += self._selective_lines(metrics) + self._calibration_lines(metrics) + self._conformal_lines(metrics) + self._knn_lines(metrics)
+        lines += self._selective_lines(metrics) + self._calibration_lines(metrics) + self._conformal_lines(metrics) + self._knn_lines(metrics) + self._laplace_lines(metrics)
         path = results_dir / 'evaluation_results.txt'
         path.write_text('\n'.join(lines) + '\n', encoding='utf-8')
         print(f'Results saved to {path}')

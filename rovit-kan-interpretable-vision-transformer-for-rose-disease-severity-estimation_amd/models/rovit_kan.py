@@ -277,6 +277,28 @@ class RoViTKAN(nn.Module):
             self.train(was_training)
         return density.score(out['features'], out['cls_logits'])
 
+    def fit_laplace(self, x_or_loader, prior_precision='marglik', chunk: int = 256):
+        """Extension (not in the reference): a fitted ``rovit_hip.laplace.HeadLaplace`` of this model's classification head and, from
+        curriculum stage 3, of the Gaussian head's ``mu`` layer over images (a (B,3,224,224) tensor, or an iterable of batches whose first
+        element is the images): last-layer Laplace approximation with the GGN Hessian, the weighted Grams on the GPU.  No labels."""
+        from rovit_hip import laplace
+        return laplace.fit_model_laplace(self, x_or_loader, prior_precision, chunk)
+
+    def predict_laplace(self, x: torch.Tensor, laplace) -> Dict[str, torch.Tensor]:
+        """Extension (not in the reference): the forward plus ``laplace.predict(features, cls_logits, mu, log_var)``: the closed-form
+        logit covariance, probit-adjusted class probabilities and, from stage 3, the epistemic variance of ``mu`` and ``total_std``;
+        ``class`` is the argmax of the adjusted probabilities."""
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                out = self(x)
+        finally:
+            self.train(was_training)
+        pred = dict(laplace.predict(out['features'], out['cls_logits'], out.get('mu'), out.get('log_var')))
+        pred['class'] = torch.argmax(pred['probs'], dim=1)
+        return pred
+
     def fit_feature_index(self, x_or_loader, labels=None, severity=None, metric: str = 'cosine', chunk: int = 256):
         """Extension (not in the reference): a built ``rovit_hip.neighbors.FeatureIndex`` of this model's backbone features over images
         (a (B,3,224,224) tensor with optional ``labels`` and ``severity``, or an iterable of batches ``(images, class_labels,

@@ -147,6 +147,10 @@ SIGNATURES = {
     'rovit_augment_batch': (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, C.c_ulonglong, C.c_ulonglong, _vp, _i, _i, _vp]),
     'rovit_corrupt_stats': (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp]),
     'rovit_corrupt_batch': (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    'rovit_laplace_weights': (_i, [_vp, _vp]),
+    'rovit_laplace_workspace_bytes': (_sz, [_i, _i, _i, _i]),
+    'rovit_laplace_gram': (_i, [_vp, _vp]),
+    'rovit_laplace_predict': (_i, [_vp, _vp]),
 }
 
 
@@ -399,6 +403,37 @@ class CorruptionC(C.Structure):
 
 
 CORRUPT_MAX_RADIUS = 18          # ROVIT_CORRUPT_MAX_RADIUS: gaussian ceil(3 sigma), defocus r, motion R + 1
+
+
+# rovit_laplace_weights / rovit_laplace_gram / rovit_laplace_predict: limits, tile sizes and the result blocks' layouts (the ROVIT_LAPLACE_*
+# names of include/rovit_hip.h)
+LAPLACE_MAX_WEIGHTS, LAPLACE_MAX_CHUNKS, LAPLACE_TILE = 36, 64, 64
+LAPLACE_BAD_LOGITS, LAPLACE_BAD_LOG_VAR, LAPLACE_COUNT_WORDS = 0, 1, 2
+LAPLACE_N, LAPLACE_N_VALID, LAPLACE_BAD_ROWS, LAPLACE_HEADER = 0, 1, 2, 8
+
+
+class LaplaceWeightArgs(C.Structure):
+    """``rovit_laplace_weight_args`` of include/rovit_hip.h, field for field."""
+    _fields_ = [('n', _i), ('num_classes', _i), ('max_workgroups', _i), ('reserved', _i), ('cls_logits', _vp), ('log_var', _vp),
+                ('cls_weights', _vp), ('mu_weights', _vp), ('counts', _vp)]
+
+
+class LaplaceFit(C.Structure):
+    """``rovit_laplace_fit`` of include/rovit_hip.h, field for field."""
+    _fields_ = [('n', _i), ('embed', _i), ('hid', _i), ('num_weights', _i), ('max_workgroups', _i), ('reserved', _i), ('features', _vp),
+                ('fc1_weight', _vp), ('fc1_bias', _vp), ('weights', _vp), ('workspace', _vp), ('workspace_bytes', _sz), ('result', _vp)]
+
+
+class LaplaceQuery(C.Structure):
+    """``rovit_laplace_query`` of include/rovit_hip.h, field for field."""
+    _fields_ = [('batch', _i), ('embed', _i), ('hid', _i), ('num_classes', _i), ('max_workgroups', _i), ('reserved', _i), ('features', _vp),
+                ('fc1_weight', _vp), ('fc1_bias', _vp), ('whitening', _vp), ('cls_logits', _vp), ('logit_cov', _vp), ('logit_var', _vp),
+                ('probs', _vp), ('confidence_score', _vp), ('mean_logit_var', _vp)]
+
+
+def laplace_words(hid: int, K: int) -> int:
+    """ROVIT_LAPLACE_WORDS(hid, K): matrix k sits at LAPLACE_HEADER + k (hid + 1)^2."""
+    return LAPLACE_HEADER + K * (hid + 1) * (hid + 1)
 
 
 # entry points only the developer library exports (round-2 / round-3 experiments that lost; tools/ A/B them)
