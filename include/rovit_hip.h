@@ -891,6 +891,63 @@ int rovit_kan_curves(const float* xs, const float* spline_w, const float* knots,
                      int n_knots, int num_points, rovit_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * KAN grid extension (kan_grid.hip): move every edge spline of one layer from its stored knots k (nk of them, nb = nk - 4) to a new
+ * uniform knot vector k' (nk', nb' = nk' - 4) by least squares on data.  models/kan.py:8-44 fixes the grid at construction; the
+ * definitions below are this repository's own ("parity unpinned").  b(v), b'(v): the truncated cubic bases of the
+ * two grids as the forward evaluates them (kan_device.h), v = tanh(x).
+ *
+ * rovit_kan_regrid_moments: for every input i over its FINITE rows x_ni (N_i of them; a non-finite x_ni is skipped for input i and
+ * counted) the sums  G_i = sum_n b' b'^T,  M_i = sum_n b' b^T,  O_i = sum_n b b^T  into the moment block,
+ * rovit_kan_regrid_moment_words(in_f, nk, nk') 8-byte words:
+ *   double G [i][a][d], a < nb', d < 4: entry (a, a - d) of G_i (0 for a < d)        at 0
+ *   double M [i][a][b], a < nb', b < nb                                              at 4 in_f nb'
+ *   double O [i][b][d], b < nb, d < 4                                                at 4 in_f nb' + in_f nb' nb
+ *   int64  N_i [i], then non-finite inputs [i]                                       at .. + 4 in_f nb
+ * Each (row, input) takes tanhf and the two bases once; products are summed in fp32 over at most 16 rows and folded into fp64; the rows
+ * are cut into ranges of whole 256-row chunks, a function of n and in_f only, and the ranges are added in order: the block is
+ * bit-identical from run to run.  Integers are added with integer atomics.  No (n, in, nb) tensor exists.
+ * workspace: rovit_kan_regrid_workspace_bytes(n, in_f, nk, nk') bytes, 8-byte aligned (0 for sizes outside the limits).  It holds
+ * R in_f (2 nb' + 2 nb - 1) blocks of 16 doubles with R <= 64 row ranges and R in_f < 1024 + in_f: at most (1024 + in_f) * 30 592 bytes,
+ * whatever n is.
+ *
+ * rovit_kan_regrid_solve: per input, in fp64,  A = G_i / N_i + prior_g,  delta = 2^-40 tr(A) / nb' added to the diagonal entries that
+ * are <= delta (the bases neither the data nor D reach: their row of M is zero and they get coefficient 0; every other entry is left
+ * exact), Cholesky,  T_i = A^-1 (M_i / N_i + prior_m)  and  c'_ij = T_i c_ij  for every output j (N_i = 0: the priors alone).  prior_g (nb', nb')
+ * and prior_m (nb', nb) are the caller's (eps / L) int_D b' b'^T dv and (eps / L) int_D b' b^T dv, row-major fp64 on the device.
+ * It writes spline_w_new (in_f, out_f, nb') and the diagnostics block, rovit_kan_regrid_diag_words(in_f, out_f) 8-byte words, E = in_f out_f:
+ *   double fit_ms [i][j] = c'^T G c' - 2 c'^T M c + c^T O c  (data parts / N_i, c' before its rounding to fp32; may be -0 within rounding)
+ *   double target_ms [i][j] = c^T O c        at E          double pivot ratio [i] (smallest / largest Cholesky pivot)   at 2E
+ *   int64 N_i [i]  at 2E + in_f      int64 non-finite inputs [i]  at 2E + 2 in_f      int64 status  at 2E + 3 in_f
+ * status counts the inputs whose factorisation met a non-positive pivot; their pivot ratio is 0 and their new coefficients are 0.
+ *
+ * Limits of both: in_f, out_f >= 1, 8 <= nk, nk' <= 64, 1 <= n <= ROVIT_KAN_STATS_MAX_ROWS; anything else is ROVIT_ERR_SHAPE before
+ * any launch, a missing pointer ROVIT_ERR_NULL.
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct rovit_kan_regrid {
+  int n, in_f, n_knots_old, n_knots_new;
+  const float* x;                   /* (n, in_f) inputs of the layer */
+  const float* knots_old;           /* (n_knots_old) */
+  const float* knots_new;           /* (n_knots_new) */
+  void* workspace;
+  size_t workspace_bytes;
+  void* moments;                    /* the moment block */
+} rovit_kan_regrid;
+typedef struct rovit_kan_regrid_fit {
+  int in_f, out_f, n_knots_old, n_knots_new;
+  const void* moments;              /* rovit_kan_regrid_moments' block */
+  const double* prior_g;            /* (nb', nb') */
+  const double* prior_m;            /* (nb', nb) */
+  const float* spline_w;            /* (in_f, out_f, nb) */
+  float* spline_w_new;              /* (in_f, out_f, nb') */
+  void* diagnostics;                /* the diagnostics block */
+} rovit_kan_regrid_fit;
+size_t rovit_kan_regrid_moment_words(int in_f, int n_knots_old, int n_knots_new);
+size_t rovit_kan_regrid_diag_words(int in_f, int out_f);
+size_t rovit_kan_regrid_workspace_bytes(int n, int in_f, int n_knots_old, int n_knots_new);
+int rovit_kan_regrid_moments(const rovit_kan_regrid* p, rovit_stream_t stream);
+int rovit_kan_regrid_solve(const rovit_kan_regrid_fit* p, rovit_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Per-sample augmentation of a device-resident uint8 image store (augment_batch.hip).  Serves the batches of
  * training/trainer.py:79-82 (`images, class_labels, severity_labels`, moved with .to(device)) and the loaders scripts/train.py:73-84
  * builds with create_dataloaders(..., augmented_transform=, original_transform=): the data set is decoded ONCE and kept on the device

@@ -551,7 +551,9 @@ def load_model_for_evaluation(checkpoint_path: Path, config, device, use_ema=Non
     if use_ema and 'ema_state_dict' not in checkpoint:
         raise KeyError(f'{checkpoint_path} holds no ema_state_dict (use_ema=True)')
     averaged = use_ema is not False and 'ema_state_dict' in checkpoint
-    model.load_state_dict(checkpoint['ema_state_dict' if averaged else 'model_state_dict'])
+    state = checkpoint['ema_state_dict' if averaged else 'model_state_dict']
+    model.kan_module.resize_grid_like(state, prefix='kan_module.')          # a checkpoint saved after a KAN grid extension
+    model.load_state_dict(state)
     model.to(device)
     model.eval()
     print(f'Model loaded from {checkpoint_path}')

@@ -131,6 +131,59 @@ class KANSeverityModule(nn.Module):
     def invalidate_prepared(self):
         self._prep_key = None
 
+    # ---- grid extension (not in the reference; rovit_hip/kan_grid.py) ----------------------------------------------------------
+
+    def _refresh_grid(self):
+        """After a layer's knots and ``spline_weights`` were replaced: the module's ``num_knots`` when all layers share one value, the
+        batch thresholds by the constructor's rule (the largest grid decides), the prepared weights and the uniformity cache dropped,
+        the regrid counter bumped (``RoViTAdamW`` compares it: an optimizer built earlier holds the old storage) and the owning
+        ``RoViTKAN``'s gradient views cleared."""
+        counts = [l.num_knots for l in self.kan_layers]
+        if len(set(counts)) == 1:
+            self.num_knots = counts[0]
+        self.fused_min_batch = 2048 if max(counts) > 8 else 4096
+        self.mfma_min_batch = 32768 if max(counts) > 8 else 4096
+        self.invalidate_prepared()
+        self.__dict__.pop('_uniform_cache', None)
+        self.__dict__['_regrid_count'] = self.__dict__.get('_regrid_count', 0) + 1
+        owner = self.__dict__.get('_owner')
+        if owner is not None and getattr(owner, '_head_grad_views', None) is not None:
+            owner._head_grad_views = None
+
+    def regrid(self, features: torch.Tensor, **fit_kw):
+        """Extension: refit every edge spline to a new uniform grid by least squares on ``features`` (B, in) and install it:
+        ``KANRegrid(self).update(features)``, ``fit(**fit_kw)``, ``apply()``.  ``layout='cover'`` (the default) removes the dead zone of
+        the truncated basis; ``num_knots=`` / ``knots=`` refine the grid.  Returns the ``RegridResult``."""
+        from rovit_hip.kan_grid import KANRegrid
+        acc = KANRegrid(self, capacity=max(1, features.shape[0]))
+        acc.update(features)
+        res = acc.fit(**fit_kw)
+        res.apply()
+        return res
+
+    @torch.no_grad()
+    def resize_grid_like(self, state_dict, prefix: str = ''):
+        """Re-allocate every layer whose knot count differs from the one in ``state_dict`` (keys ``{prefix}kan_layers.{l}.knots``), so that
+        ``load_state_dict`` of a regridded checkpoint works on a module built from the original config.  The new tensors are zeros until
+        the state dict is loaded."""
+        changed = False
+        for l, layer in enumerate(self.kan_layers):
+            kn = state_dict.get(f'{prefix}kan_layers.{l}.knots')
+            if kn is None or kn.numel() == layer.knots.numel():
+                continue
+            nk = int(kn.numel())
+            if not 2 * layer.degree + 2 <= nk <= 64:
+                raise ValueError(f'kan_layers.{l}: {nk} knots in the state dict (supported: {2 * layer.degree + 2}..64)')
+            layer.num_knots, layer.num_basis = nk - 2 * layer.degree, nk - layer.degree - 1
+            layer.knots = torch.zeros(nk, dtype=layer.knots.dtype, device=layer.knots.device)
+            w = layer.spline_weights
+            layer.spline_weights = nn.Parameter(torch.zeros(layer.in_features, layer.out_features, layer.num_basis, dtype=w.dtype, device=w.device),
+                                                requires_grad=w.requires_grad)
+            changed = True
+        if changed:
+            self._refresh_grid()
+        return self
+
     def _trajectory(self, x: torch.Tensor) -> List[torch.Tensor]:
         last = len(self.kan_layers) - 1
         codes = tuple(ACT_SIGMOID3 if i == last else ACT_RELU for i in range(last + 1))

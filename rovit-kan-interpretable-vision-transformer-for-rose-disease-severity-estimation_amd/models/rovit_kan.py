@@ -35,6 +35,7 @@ class RoViTKAN(nn.Module):
         self.ordinal_head = OrdinalHead(embed_dim, hidden_dim, num_classes, dropout)
         self.uncertainty_head = UncertaintyHead(embed_dim, hidden_dim, dropout)
         self.kan_module = KANSeverityModule(layers=kan_layers, num_knots=kan_num_knots, degree=kan_degree)
+        self.kan_module.__dict__['_owner'] = self          # not a submodule link: a regrid clears this model's _head_grad_views through it
         self._curriculum_stage = 4
 
     @property
@@ -250,6 +251,14 @@ class RoViTKAN(nn.Module):
         of every edge on the GPU (rovit_hip.kan_stats)."""
         from rovit_hip import kan_stats
         return kan_stats.model_edge_stats(self, x_or_loader, chunk)
+
+    def kan_regrid(self, x_or_loader, chunk: int = 256, **fit_kw):
+        """Extension (not in the reference): KAN grid extension over images (a (B,3,224,224) tensor, or an iterable of batches whose first
+        element is the images): every edge spline of the KAN head is refitted to a new uniform grid by least squares on this model's
+        backbone features and installed (rovit_hip.kan_grid; ``num_knots``, ``knots``, ``span``, ``layout``, ``margin``, ``prior_weight``,
+        ``layers`` as ``KANRegrid.fit``).  Returns the ``RegridResult``.  Build a new optimizer afterwards."""
+        from rovit_hip import kan_grid
+        return kan_grid.model_regrid(self, x_or_loader, chunk, **fit_kw)
 
     def kan_attribution(self, x_or_loader, chunk: int = 256):
         """Extension (not in the reference): ``kan_edge_stats`` plus pykan's attribution scores of every edge, node and backbone

@@ -132,6 +132,11 @@ SIGNATURES = {
     'rovit_kan_stats_partials_doubles': (_sz, [_i, _i, _i, _i]),
     'rovit_kan_edge_stats': (_i, [_vp, _vp]),
     'rovit_kan_curves': (_i, [_vp] * 5 + [_i] * 4 + [_vp]),
+    'rovit_kan_regrid_moment_words': (_sz, [_i, _i, _i]),
+    'rovit_kan_regrid_diag_words': (_sz, [_i, _i]),
+    'rovit_kan_regrid_workspace_bytes': (_sz, [_i, _i, _i, _i]),
+    'rovit_kan_regrid_moments': (_i, [_vp, _vp]),
+    'rovit_kan_regrid_solve': (_i, [_vp, _vp]),
     'rovit_density_workspace_bytes': (_sz, [_i, _i, _i]),
     'rovit_density_moments': (_i, [_vp, _vp]),
     'rovit_density_score': (_i, [_vp, _vp]),
@@ -299,6 +304,37 @@ def kan_stats_offsets(in_f: int, out_f: int, n_knots: int) -> dict:
     occ = abs_in + in_f
     bad = occ + in_f * n_knots
     return {'edge': 0, 'pre': pre, 'abs_in': abs_in, 'occupancy': occ, 'nonfinite': bad, 'n': bad + 1, 'words': bad + 2}
+
+
+class KANRegridMoments(C.Structure):
+    """``rovit_kan_regrid`` of include/rovit_hip.h, field for field."""
+    _fields_ = [('n', _i), ('in_f', _i), ('n_knots_old', _i), ('n_knots_new', _i), ('x', _vp), ('knots_old', _vp), ('knots_new', _vp),
+                ('workspace', _vp), ('workspace_bytes', _sz), ('moments', _vp)]
+
+
+class KANRegridFit(C.Structure):
+    """``rovit_kan_regrid_fit`` of include/rovit_hip.h, field for field."""
+    _fields_ = [('in_f', _i), ('out_f', _i), ('n_knots_old', _i), ('n_knots_new', _i), ('moments', _vp), ('prior_g', _vp), ('prior_m', _vp),
+                ('spline_w', _vp), ('spline_w_new', _vp), ('diagnostics', _vp)]
+
+
+KAN_REGRID_MIN_KNOTS, KAN_REGRID_CHUNK_ROWS = 8, 256          # kan_grid.hip: the knot-count floor and the rows of one chunk
+
+
+def kan_regrid_moment_offsets(in_f: int, n_knots_old: int, n_knots_new: int) -> dict:
+    """Word offsets inside rovit_kan_regrid_moments' block; ``words`` equals rovit_kan_regrid_moment_words(in_f, nk, nk')."""
+    nb, nbn = n_knots_old - 4, n_knots_new - 4
+    m = 4 * in_f * nbn
+    o = m + in_f * nbn * nb
+    rows = o + 4 * in_f * nb
+    return {'G': 0, 'M': m, 'O': o, 'rows': rows, 'nonfinite': rows + in_f, 'words': rows + 2 * in_f}
+
+
+def kan_regrid_diag_offsets(in_f: int, out_f: int) -> dict:
+    """Word offsets inside rovit_kan_regrid_solve's diagnostics block; ``words`` equals rovit_kan_regrid_diag_words(in_f, out_f)."""
+    e = in_f * out_f
+    return {'fit_ms': 0, 'target_ms': e, 'pivot_ratio': 2 * e, 'rows': 2 * e + in_f, 'nonfinite': 2 * e + 2 * in_f, 'status': 2 * e + 3 * in_f,
+            'words': 2 * e + 3 * in_f + 1}
 
 
 # rovit_density_moments / rovit_density_score / rovit_ood_metrics: limits, tile sizes and the result blocks' layouts (the ROVIT_DENSITY_* and

@@ -103,6 +103,7 @@ class RoViTAdamW(torch.optim.Optimizer):
         super().__init__([{'params': list(self.bb_params), 'lr': lr / 10.0}, {'params': list(self.other_params), 'lr': lr}],
                          dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.last_grad_norm: Optional[torch.Tensor] = None
+        self._regrid_seen = self._regrid_count()          # the KAN head's spline_weights captured above are those of this grid
         # The reference builds its optimizer BEFORE Trainer.__init__ moves the model to the device (scripts/train.py:104 vs
         # training/trainer.py:32): the flat buffers are therefore created when the parameters are first seen on a
         # CUDA/HIP device -- here if they already are, else at the first step / state_dict call -- and again if the model
@@ -114,7 +115,16 @@ class RoViTAdamW(torch.optim.Optimizer):
         p0 = self.bb_params[0]
         return self.p_flat is None or p0.device != self.p_flat.device or p0.data_ptr() != self.p_flat.data_ptr()
 
+    def _regrid_count(self) -> int:
+        return getattr(getattr(self.model, 'kan_module', None), '_regrid_count', 0)
+
+    def _check_regrid(self):
+        if self._regrid_count() != self._regrid_seen:
+            raise native.RovitHipError('the KAN head was regridded after this optimizer was built: its flat buffers hold the old '
+                                       'spline_weights storage; build a new RoViTAdamW (the Adam moments restart)')
+
     def _build(self):
+        self._check_regrid()
         dev = self.bb_params[0].device
         if dev.type != 'cuda':
             raise native.RovitHipError('RoViTAdamW needs the model on a CUDA/HIP device before the first step '
@@ -221,6 +231,7 @@ class RoViTAdamW(torch.optim.Optimizer):
                 loss = closure()
         if self._swapped:
             raise native.RovitHipError('optimizer.step() inside swap_ema(): the parameters are the average there')
+        self._check_regrid()
         if self._stale():
             if any(p.grad is not None for p in self.bb_params) and self.p_flat is not None:
                 raise native.RovitHipError('the model was moved between backward and optimizer.step(): run the step again')
