@@ -1334,6 +1334,85 @@ size_t rovit_laplace_workspace_bytes(int n, int embed, int hid, int num_weights)
 int rovit_laplace_gram(const rovit_laplace_fit* p, rovit_stream_t stream);
 int rovit_laplace_predict(const rovit_laplace_query* p, rovit_stream_t stream);
 
+/* ---- KernelSHAP over groups of patches (csrc/shap.hip; rovit_hip/shap.py holds the host plan and the numpy fp64 reference) ----------
+ * P players (2 <= P <= ROVIT_SHAP_PATCHES), M samples (even, 2 <= M <= ROVIT_SHAP_MAX_SAMPLES); sample 2k + 1 is the complement of
+ * sample 2k.  A coalition is ROVIT_SHAP_WORDS 32-bit words: player i is bit i % 32 of word i / 32, the bits from P on are zero.
+ *
+ * rovit_shap_coalitions: one workgroup per pair k, from the host's plan tables (device memory, the host never reads anything back):
+ *   pairs (M / 2, 4) int: class s (the coalition's size, 1 <= s < P), enumerated?, rank, reserved     pair_weights (M / 2) double
+ *   enumerated: the coalition is the rank-th s-subset of 0..P-1 in lexicographic order (itertools.combinations), unranked with exact
+ *   64-bit binomials (the host enumerates a class only when all of it fits the budget, so C(P, s) <= ROVIT_SHAP_MAX_SAMPLES)
+ *   sampled: player i has the key (word << 32) | i, word = word i % 4 of Philox4x32-10 with key = seed and counter
+ *   (i / 4, rank, ROVIT_SHAP_STREAM, 0); the coalition is the s players with the smallest keys, ranked by counting in LDS: integer
+ *   compares alone decide membership
+ * It writes bits (M, 7), weights (M) (both samples of a pair carry the pair's) and, with players (196: patch -> player id) not NULL,
+ * the src rows of rovit_vit_forward_tokens for the patches of the ABSENT players perturbed:
+ *   src_replace (M, 197): row 0 the class token, row 1 + p = 1 + p (kept) or -2 - p (the baseline's row)
+ *   src_drop: sample m's sequence -- 0, then 1 + p of the kept patches in patch order -- starts at word drop_offsets[m] of a buffer of
+ *   drop_words ints (the host packs sequences of equal length together); a store outside the buffer is skipped
+ * src_replace / src_drop may be NULL each.
+ *
+ * rovit_shap_gram: gram (P, P) double, A[i][j] = sum_m w_m z_mi z_mj, every element one thread's sum over m ascending; then ONE
+ * workgroup factors A = L L^T in fp64 in place in the factor block, which lives in global memory and is read through L2 (the packed
+ * triangle of 196 rows would fill 154 448 B of the 160 KB LDS; the factorisation is 2.5 MFLOP, once per call):
+ *   factor: ROVIT_SHAP_FACTOR_WORDS(P) doubles: L (P, P) row-major (upper part zero), u = A^-1 1 (P), 1^T u, the smallest pivot
+ *   (before its square root), ok (1.0; 0.0 after a pivot that is not > 0: u is then NaN and L is left half factored), the sum of
+ *   the weights
+ *
+ * rovit_shap_solve: one workgroup per (image b, target t): b_i = sum_m w_m z_mi (values[m][b][t] - v_empty[b][t]) in fp64 over m
+ * ascending (each product rounded, then added), x = A^-1 b by the two triangular solves, lambda = (1^T x - (v_full - v_empty)) / 1^T u,
+ *   phi (B, T, P) double = x - lambda u, phi32 the same in fp32      ok (B, T) int: the factor block's
+ *   fit_rmse (B, T) double = sqrt(sum_m w_m (z_m . phi - y_m)^2 / sum_m w_m)
+ *   patch_map (B, T, 196) fp32 with players not NULL: phi[players[p]] / (patches of that player)
+ * ok = 0 gives NaN phi, fit_rmse and patch_map.
+ * No floating-point atomic anywhere; every sum has a fixed order and no partition depends on the grid: all outputs are bit-identical
+ * from run to run and for every max_workgroups (> 0 caps the grid; work items are walked with a stride of the grid).
+ * A bad descriptor is refused before any launch, by all three.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define ROVIT_SHAP_STREAM 0x53686170u          /* "Shap": counter word 2, apart from the other Philox streams */
+#define ROVIT_SHAP_PATCHES 196
+#define ROVIT_SHAP_WORDS 7
+#define ROVIT_SHAP_MAX_SAMPLES (1 << 20)
+#define ROVIT_SHAP_FACTOR_WORDS(P) ((size_t)(P) * (P) + (P) + 4)
+typedef struct rovit_shap_coalition_args {
+  int num_players, num_samples, max_workgroups, reserved;
+  unsigned long long seed;
+  const int* pairs;                  /* (M / 2, 4) */
+  const double* pair_weights;        /* (M / 2) */
+  const int* players;                /* (196) or NULL */
+  const long long* drop_offsets;     /* (M); with src_drop */
+  long long drop_words;
+  unsigned* bits;                    /* (M, 7) */
+  double* weights;                   /* (M) */
+  int* src_replace;                  /* (M, 197) or NULL */
+  int* src_drop;                     /* drop_words ints or NULL */
+} rovit_shap_coalition_args;
+typedef struct rovit_shap_gram_args {
+  int num_players, num_samples, max_workgroups, reserved;
+  const unsigned* bits;              /* (M, 7) */
+  const double* weights;             /* (M) */
+  double* gram;                      /* (P, P) */
+  double* factor;                    /* ROVIT_SHAP_FACTOR_WORDS(P) */
+} rovit_shap_gram_args;
+typedef struct rovit_shap_solve_args {
+  int num_players, num_samples, batch, num_targets, max_workgroups, reserved;
+  const unsigned* bits;              /* (M, 7) */
+  const double* weights;             /* (M) */
+  const double* factor;              /* rovit_shap_gram's */
+  const float* values;               /* (M, batch, num_targets) */
+  const float* v_empty;              /* (batch, num_targets) */
+  const float* v_full;               /* (batch, num_targets) */
+  const int* players;                /* (196) or NULL */
+  double* phi;                       /* (batch, num_targets, P) */
+  float* phi32;                      /* (batch, num_targets, P) */
+  float* patch_map;                  /* (batch, num_targets, 196); with players */
+  double* fit_rmse;                  /* (batch, num_targets) */
+  int* ok;                           /* (batch, num_targets) */
+} rovit_shap_solve_args;
+int rovit_shap_coalitions(const rovit_shap_coalition_args* p, rovit_stream_t stream);
+int rovit_shap_gram(const rovit_shap_gram_args* p, rovit_stream_t stream);
+int rovit_shap_solve(const rovit_shap_solve_args* p, rovit_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

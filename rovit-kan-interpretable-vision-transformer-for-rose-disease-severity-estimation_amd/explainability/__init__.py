@@ -2,3 +2,4 @@
 from .attention_maps import ViTAttentionRollout  # noqa: F401
 from .gradcam import GradCAMPlusPlus  # noqa: F401
 from .kan_viz import KANVisualizer  # noqa: F401
+from .shap import PatchSHAP  # noqa: F401

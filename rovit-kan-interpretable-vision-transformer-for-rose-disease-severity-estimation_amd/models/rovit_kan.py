@@ -245,6 +245,14 @@ class RoViTKAN(nn.Module):
         from rovit_hip import perturbation as pert
         return pert.perturbation_curves(self, x, saliency, target, class_idx, modes, steps, perturbation, baseline, chunk)
 
+    def patch_shap(self, x: torch.Tensor, target='class', class_idx=None, num_samples: int = 2048, players=14, perturbation: str = 'drop',
+                   baseline=None, seed: int = 0, chunk: int = 256, upsample: bool = True, return_values: bool = False):
+        """Extension (not in the reference): KernelSHAP values of the patches, or of any grouping of them into players, for the
+        probability of a class, ordinal_severity, mu, log_var or kan_severity on the GPU; absent players' patches are dropped from the
+        sequence or replaced by a baseline's, and the values sum to f(image) - f(nothing) (rovit_hip.shap)."""
+        from rovit_hip import shap
+        return shap.patch_shap(self, x, target, class_idx, num_samples, players, perturbation, baseline, seed, chunk, upsample, return_values)
+
     def kan_edge_stats(self, x_or_loader, chunk: int = 256):
         """Extension (not in the reference): per-edge activation statistics of the KAN head over images (a (B,3,224,224) tensor, or an
         iterable of batches whose first element is the images): magnitude, spline share, knot-span occupancy and dead-zone share

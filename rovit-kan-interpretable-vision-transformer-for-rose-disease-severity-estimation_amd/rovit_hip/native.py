@@ -137,6 +137,9 @@ SIGNATURES = {
     'rovit_kan_regrid_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'rovit_kan_regrid_moments': (_i, [_vp, _vp]),
     'rovit_kan_regrid_solve': (_i, [_vp, _vp]),
+    'rovit_shap_coalitions': (_i, [_vp, _vp]),
+    'rovit_shap_gram': (_i, [_vp, _vp]),
+    'rovit_shap_solve': (_i, [_vp, _vp]),
     'rovit_density_workspace_bytes': (_sz, [_i, _i, _i]),
     'rovit_density_moments': (_i, [_vp, _vp]),
     'rovit_density_score': (_i, [_vp, _vp]),
@@ -470,6 +473,38 @@ class LaplaceQuery(C.Structure):
 def laplace_words(hid: int, K: int) -> int:
     """ROVIT_LAPLACE_WORDS(hid, K): matrix k sits at LAPLACE_HEADER + k (hid + 1)^2."""
     return LAPLACE_HEADER + K * (hid + 1) * (hid + 1)
+
+
+# rovit_shap_coalitions / rovit_shap_gram / rovit_shap_solve: the Philox stream word, the limits and the factor block's layout (the
+# ROVIT_SHAP_* names of include/rovit_hip.h)
+SHAP_STREAM, SHAP_PATCHES, SHAP_WORDS, SHAP_MAX_SAMPLES = 0x53686170, 196, 7, 1 << 20
+
+
+class ShapCoalitionArgs(C.Structure):
+    """``rovit_shap_coalition_args`` of include/rovit_hip.h, field for field."""
+    _fields_ = [('num_players', _i), ('num_samples', _i), ('max_workgroups', _i), ('reserved', _i), ('seed', C.c_ulonglong), ('pairs', _vp),
+                ('pair_weights', _vp), ('players', _vp), ('drop_offsets', _vp), ('drop_words', C.c_longlong), ('bits', _vp), ('weights', _vp),
+                ('src_replace', _vp), ('src_drop', _vp)]
+
+
+class ShapGramArgs(C.Structure):
+    """``rovit_shap_gram_args`` of include/rovit_hip.h, field for field."""
+    _fields_ = [('num_players', _i), ('num_samples', _i), ('max_workgroups', _i), ('reserved', _i), ('bits', _vp), ('weights', _vp),
+                ('gram', _vp), ('factor', _vp)]
+
+
+class ShapSolveArgs(C.Structure):
+    """``rovit_shap_solve_args`` of include/rovit_hip.h, field for field."""
+    _fields_ = [('num_players', _i), ('num_samples', _i), ('batch', _i), ('num_targets', _i), ('max_workgroups', _i), ('reserved', _i),
+                ('bits', _vp), ('weights', _vp), ('factor', _vp), ('values', _vp), ('v_empty', _vp), ('v_full', _vp), ('players', _vp),
+                ('phi', _vp), ('phi32', _vp), ('patch_map', _vp), ('fit_rmse', _vp), ('ok', _vp)]
+
+
+def shap_factor_offsets(P: int) -> dict:
+    """Word offsets inside rovit_shap_gram's factor block (ROVIT_SHAP_FACTOR_WORDS(P) doubles): the lower Cholesky factor L (P, P)
+    row-major, u = A^-1 1 (P), 1^T u, the smallest pivot, ok (1.0 / 0.0) and the sum of the weights."""
+    return {'L': 0, 'u': P * P, 'sum_u': P * P + P, 'min_pivot': P * P + P + 1, 'ok': P * P + P + 2, 'sum_w': P * P + P + 3,
+            'words': P * P + P + 4}
 
 
 # entry points only the developer library exports (round-2 / round-3 experiments that lost; tools/ A/B them)
