@@ -1,5 +1,8 @@
 """Round-3 GPU tests: the fused MLP half of a block (mlp_fused.hip) against the two-launch path it replaces and against a plain
 PyTorch fp32 reference of the same op, called through the C ABI; the fused path inside the backbone forward."""
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
@@ -7,6 +10,9 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import ref_cpu  # noqa: E402  (checker only)
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from wgrad_cases import _chunks, _rows  # noqa: E402  (chunk-major [24][M][32] <-> row-major (M,768))
 
 
 def _native():
@@ -33,17 +39,6 @@ def _mlp_problem(M, seed):
     b2 = (r(192) * 0.3).to(dev())
     X0 = (r(M, 192) * 2).to(dev())
     return xhat2, w1, w2, b1, b2, X0
-
-
-def _rows(t, M):
-    """chunk-major [24][M][32] (what the one-launch MLP kernels keep) -> row-major (M,768)"""
-    return t.view(24, M, 32).permute(1, 0, 2).reshape(M, 768).contiguous()
-
-
-def _chunks(t):
-    """row-major (M,768) -> chunk-major [24][M][32], flat"""
-    M = t.shape[0]
-    return t.view(M, 24, 32).permute(1, 0, 2).contiguous().view(M, 768)
 
 
 def _two_launch(native, xhat2, w1, w2, b1, b2, X0, keep=True):
@@ -323,7 +318,8 @@ def test_fused_mlp_backward_equals_the_two_launch_dgrad_chain_and_a_torch_refere
         shapes = [(768, 192), (192, 768)]                              # (N, K): fc1 (dY = dpre, A = xhat2), fc2 (dY = dY, A = "act" := dact)
         outs = []
         for blocked in (0, 1):
-            wsl = [torch.zeros(lib.rovit_wgrad_workspace_bytes(n, k, S), dtype=torch.uint8, device=dev()) for n, k in shapes]
+            # NaN, not zeros: a slab element that a launch never writes must not compare equal
+            wsl = [torch.full((lib.rovit_wgrad_workspace_bytes(n, k, S) // 4,), float('nan'), device=dev()) for n, k in shapes]
             dys = [dpre1_c if blocked else dpre1, dY]
             As = [xh, dact_c if blocked else dact]
             native.call('rovit_wgrad_multi_ex', native.ptr_array(dys), arr([768, 192]), native.ptr_array(As), arr([192, 768]), arr([768, 192]),
