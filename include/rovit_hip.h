@@ -355,6 +355,20 @@ int rovit_vit_embed(const float* images, const float* const* params, const void*
 int rovit_vit_forward_tokens(const float* img_tokens, const float* base_tokens, int n_img, int base_shared, const int* seq_img, const int* src,
                              int tokens, const float* const* params, const void* prep, void* workspace, float* features, int n_seq, int depth,
                              int mlp_path, rovit_stream_t stream);
+/* The same forward of n_seq sequences of DIFFERENT lengths in one call (token-dropped sequences).  The sequences are packed back to
+ * back: sequence s owns rows [off[s], off[s + 1]) of src (one entry per packed row, as above) and row off[s] is its class token;
+ * off: int32, n_seq + 1 entries, off[0] = 0, every length in [1, 197].  The array is passed twice.  seq_offsets_host is checked before
+ * anything is launched (null, first entry, order, lengths) and plans the call; no device-to-host copy is made.  The kernels read
+ * seq_offsets_dev and clamp what they find (length into [1, 197], rows into the buffers), so a device array that disagrees with the
+ * host's computes on wrong rows but stays inside the buffers.  features fp32 (n_seq,192).  A sequence's features do not depend on the
+ * others of the call and equal rovit_vit_forward_tokens' of that sequence alone at the same explicit mlp_path (ROVIT_MLP_AUTO picks by
+ * off[n_seq]).  Batches of 16 sequences and more run as two halves on two streams, cut at the sequence boundary where the first half
+ * first reaches half of the rows.  Workspace: rovit_vit_ragged_workspace_bytes(max_rows, depth) with max_rows >= off[n_seq] (the
+ * inference plan of max_rows rows; it holds any n_seq <= max_rows); the entry is not told its size, the caller answers for it. */
+size_t rovit_vit_ragged_workspace_bytes(int max_rows, int depth);
+int rovit_vit_forward_ragged(const float* img_tokens, const float* base_tokens, int n_img, int base_shared, const int* seq_img, const int* src,
+                             const int* seq_offsets_dev, const int* seq_offsets_host, const float* const* params, const void* prep,
+                             void* workspace, float* features, int n_seq, int depth, int mlp_path, rovit_stream_t stream);
 
 /* ---- the individual backbone kernels (used by rovit_vit_* and exposed for unit tests / profiling) ---------- */
 /* C = A(M,K) W(N,K)^T + bias with a fused epilogue:
@@ -473,6 +487,17 @@ int rovit_attention_cls_fwd(const void* qkv, void* out, float* lse2, int batch, 
                             rovit_stream_t stream);
 int rovit_attention_cls_bwd(const void* qkv, const void* out, const float* lse2, const void* dout, void* dqkv, int batch, int tokens,
                             int heads, int head_dim, float scale, rovit_stream_t stream);
+/* The two attention forwards on a RAGGED batch (rovit_vit_forward_ragged: offsets as there, host copy checked, device copy clamped):
+ * qkv bf16 (total_rows, 3*H*64), total_rows = off[n_seq]; one workgroup (rovit_attention_fwd_ragged) or one wave (_cls_) per
+ * (sequence, head), and a sequence of t tokens costs t tokens: key tiles, P V blocks and staged rows beyond t are skipped, exactly.
+ * Every sequence's result equals rovit_attention_fwd / rovit_attention_cls_fwd on its rows alone at tokens = t.  lse2: fp32
+ * (H, total_rows) -- the class-token form writes column off[s] only -- or NULL.  rovit_attention_fwd_ragged: out bf16 (total_rows,
+ * H*64).  rovit_attention_cls_fwd_ragged: out bf16 (n_seq, H*64), COMPACT, one row per sequence; with x_rows fp32 (total_rows, H*64)
+ * and x_cls fp32 (n_seq, H*64) (both or neither) it also copies row off[s] of x_rows to row s of x_cls. */
+int rovit_attention_fwd_ragged(const void* qkv, void* out, float* lse2, const int* seq_offsets_dev, const int* seq_offsets_host, int n_seq,
+                               int heads, int head_dim, float scale, rovit_stream_t stream);
+int rovit_attention_cls_fwd_ragged(const void* qkv, void* out, float* lse2, const float* x_rows, float* x_cls, const int* seq_offsets_dev,
+                                   const int* seq_offsets_host, int n_seq, int heads, int head_dim, float scale, rovit_stream_t stream);
 int rovit_layernorm_fwd(const float* x, void* xhat, float* rstd, int rows, int dim, float eps, rovit_stream_t stream);
 int rovit_layernorm_bwd(const void* dxhat, const void* xhat, const float* rstd, float* dX, void* dXb, int rows, int dim,
                         rovit_stream_t stream);

@@ -1207,3 +1207,302 @@ int rovit_attention_bwd_rows(const void* qkv, const void* out, const float* lse2
   ROVIT_CHECK_LAUNCH("attn_bwd_kernel");
   return ROVIT_OK;
 }
+
+// ---- ragged batches: sequences of different lengths packed back to back in one row space ----------------------------------------------
+// The token-dropping perturbations (perturbation='drop' of the deletion / insertion curves and of KernelSHAP) evaluate sequences of up
+// to 197 different lengths.  Everything row-wise in the forward takes any row range; the attention needs to know where a sequence
+// starts and ends.  Sequence s of a call owns rows [off[s], off[s + 1]) of the packed (total_rows, .) buffers, off = an int32 DEVICE array
+// of n_seq + 1 entries, 1 <= length <= 197, row off[s] the class token.  The host validates its own copy of the array before anything is
+// launched (rovit_check_ragged_offsets); the kernels clamp what they read from the device copy -- a length into [1, 197], a row base
+// into [0, total_rows) and the length again into the rows that are left -- so a device array that disagrees with the host's computes
+// on wrong rows but reads and writes inside the buffers, the stance perturb.hip takes on its indices.
+namespace {
+
+constexpr int TMAX = 197;           // longest sequence: the class token and 196 patches
+
+struct RaggedAttnArgs {
+  const bf16* qkv;        // (total_rows, 3*H*64): [q | k | v], head-major inside each third
+  bf16* out;              // full kernel: (total_rows, H*64).  Class-token kernel: (n_seq, H*64), row = the sequence's index in the launch
+  float* lse2;            // (H, total_rows), or NULL
+  const int* off;         // device (s0 + n_seq + 1)
+  const float* x_rows;    // class-token kernel only, or NULL: fp32 (total_rows, H*64) whose class-token rows ...
+  float* x_cls;           // ... are copied to (n_seq, H*64), row = the sequence's index in the launch
+  int s0, total_rows, H;
+  float scale;
+};
+
+// row base and length of sequence s, clamped (above); both wave-uniform
+__device__ __forceinline__ void ragged_span(const RaggedAttnArgs& a, int s, int& r0, int& T) {
+  const int lo = a.off[s], hi = a.off[s + 1];
+  r0 = __builtin_amdgcn_readfirstlane(min(max(lo, 0), a.total_rows - 1));
+  const long len = (long)hi - lo;                       // (no int overflow on garbage)
+  T = __builtin_amdgcn_readfirstlane(min((int)min(max(len, 1L), (long)TMAX), a.total_rows - r0));
+}
+
+// attn_fwd_kernel for one (sequence, head) of a ragged batch: the same products, mask, maximum and exp2 in the same order, but a sequence
+// of T tokens pays for T tokens.  Skipped, each behind a wave-uniform guard inside the unrolled loops (the score registers stay
+// statically indexed):
+//   * staged K / V rows from the first multiple of 32 at or above T (nothing reads them: the key tiles stop below ceil16(T), the P V
+//     blocks below ceil32(T); rows T .. ceil32(T) - 1 are zeros as in stage_tile);
+//   * key tiles that start at or beyond T: attn_fwd_kernel masks their scores to -inf, which leaves the maximum alone and adds
+//     exp2(-inf) = +0 to l; here their probabilities are set to that +0 without being computed;
+//   * 32-key P V blocks that start at or beyond T: zero probabilities times zero V rows, an exact + 0 on every accumulator.
+// So `out` and `lse2` of a sequence equal attn_fwd_kernel's on that sequence alone at tokens = T (tests/test_gpu_ragged.py, torch.equal).
+// Same launch bound, register budget and LDS as attn_fwd_kernel: two workgroups per CU.  The grid runs the sequences in their order in
+// the call; the callers pack longest first, so the long items start first and the short ones fill the tail.
+__global__ __launch_bounds__(NW * 64, 4) void attn_fwd_ragged_kernel(const RaggedAttnArgs a) {
+  extern __shared__ __attribute__((aligned(16))) bf16 lds[];
+  bf16* Ks = lds;
+  bf16* Vs = lds + TP * AST;
+  const int item = blockIdx.x, sq = item / a.H, h = item - sq * a.H;
+  int r0, T;
+  ragged_span(a, a.s0 + sq, r0, T);
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l15 = lane & 15, lg = lane >> 4;
+  const int ld = 3 * a.H * HD;
+  const bf16* base = a.qkv + (size_t)r0 * ld + h * HD;
+  const int R = (T + 31) & ~31;                         // rows the key tiles and P V blocks below can read
+#pragma unroll
+  for (int i = 0; i < TP * 8 / (NW * 64); ++i) {
+    if (8 * w + 56 * i < R) {                           // wave-uniform: a wave stages 8 whole rows per step, R is a multiple of 32
+      const int c = tid + i * NW * 64;
+      const int row = c >> 3, kc = c & 7;
+      const int rc = row < T ? row : T - 1;
+      const bf16* src = base + (size_t)rc * ld + kc * 8;
+      *(bf16x8*)(Ks + row * AST + kc * 8) = keep_if(*(const bf16x8*)(src + a.H * HD), row < T);
+      *(bf16x8*)(Vs + row * AST + kc * 8) = keep_if(*(const bf16x8*)(src + 2 * a.H * HD), row < T);
+    }
+  }
+  bf16x8 qf[2];
+  {
+    const int qr = 32 * w + l15, qc = qr < T ? qr : T - 1;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) qf[ks] = *(const bf16x8*)(base + (size_t)qc * ld + ks * 32 + lg * 8);
+  }
+  __syncthreads();
+  const float c2 = a.scale * LOG2E;
+  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+  for (int qt = 0; qt < 2; ++qt) {
+    const int q0 = 32 * w + 16 * qt;
+    if (q0 >= T) break;                                 // wave-uniform: nothing of this tile is stored (a wave beyond T only staged)
+    const int qrow = q0 + l15;
+    f32x4 st[13];
+#pragma unroll
+    for (int kt = 0; kt < 13; ++kt) {
+      if (16 * kt < T) {
+        const bf16x8 k0 = row_frag(Ks, 16 * kt + l15, 0, lg), k1 = row_frag(Ks, 16 * kt + l15, 1, lg);
+        st[kt] = mfma16(k1, qf[1], mfma16(k0, qf[0], zero4));
+      }
+    }
+    if (qt == 0) {
+      const int qr = q0 + 16 + l15, qc = qr < T ? qr : T - 1;
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) qf[ks] = *(const bf16x8*)(base + (size_t)qc * ld + ks * 32 + lg * 8);
+    }
+    float m = -INFINITY;
+#pragma unroll
+    for (int kt = 0; kt < 13; ++kt) {
+      if (16 * kt < T) {
+        if (16 * kt + 16 > T) {                         // the tile straddles T
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            if (16 * kt + 4 * lg + r >= T) st[kt][r] = -INFINITY;
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) m = fmaxf(m, st[kt][r]);
+      }
+    }
+    m = group4_max(m);
+    const float mc = m * c2;
+    float l = 0.f;
+#pragma unroll
+    for (int kt = 0; kt < 13; ++kt) {
+      if (16 * kt < T) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float p = __builtin_amdgcn_exp2f(fmaf(st[kt][r], c2, -mc));
+          st[kt][r] = p;
+          l += p;
+        }
+      } else {
+        st[kt] = zero4;                                 // exp2(-inf): the upper half of a P V block that straddles T
+      }
+    }
+    l = group4_sum(l);
+    const float inv_l = 1.f / l;
+    if (lg == 0 && qrow < T && a.lse2) a.lse2[(size_t)h * a.total_rows + r0 + qrow] = mc + log2f(l);
+    f32x4 o[4] = {zero4, zero4, zero4, zero4};
+#pragma unroll
+    for (int kb = 0; kb < 7; ++kb) {
+      if (32 * kb < T) {
+        const bf16x8 pf = pack8(st[2 * kb], kb < 6 ? st[kb < 6 ? 2 * kb + 1 : 0] : zero4);
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) o[dt] = mfma16(col_frag(Vs, 32 * kb, dt, l15, lg), pf, o[dt]);
+      }
+    }
+    if (qrow < T) {
+      bf16* dst = a.out + (size_t)(r0 + qrow) * (a.H * HD) + h * HD + 4 * lg;
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) {
+        f32x4 v = o[dt];
+        v[0] *= inv_l; v[1] *= inv_l; v[2] *= inv_l; v[3] *= inv_l;
+        *(bf16x4*)(dst + 16 * dt) = pack4(v);
+      }
+    }
+  }
+}
+
+// attn_cls_fwd_kernel for one (sequence, head) of a ragged batch: one wave, the class token's query against keys [0, T).  Steps of 8 keys
+// that start at or beyond T are skipped (their scores are -inf in attn_cls_fwd_kernel: p = +0, + 0 on every sum).  The output row is
+// written COMPACTLY, row sq of (n_seq, H*64), and -- when x_rows is given -- this head's 64 values of the sequence's class-token row of
+// the fp32 residual stream are copied to row sq of x_cls: rovit_cls_tail_fwd then runs on dense (n_seq, 192) rows (tokens = 1).
+__global__ __launch_bounds__(256) void attn_cls_fwd_ragged_kernel(const RaggedAttnArgs a, int n_items) {
+  const int lane = threadIdx.x & 63;
+  const int item = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (item >= n_items) return;                                 // whole wave; no barrier in this kernel
+  const int sq = item / a.H, h = item - sq * a.H;
+  int r0, T;
+  ragged_span(a, a.s0 + sq, r0, T);
+  const int ld = 3 * a.H * HD;
+  const bf16* base = a.qkv + (size_t)r0 * ld + h * HD;
+  const int part = lane & 7, ks = lane >> 3;
+  const float c2 = a.scale * LOG2E;
+  if (a.x_rows) a.x_cls[(size_t)sq * (a.H * HD) + h * HD + lane] = a.x_rows[(size_t)r0 * (a.H * HD) + h * HD + lane];
+  float q[8];
+  {
+    const bf16x8 qv = *(const bf16x8*)(base + part * 8);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) q[e] = (float)qv[e] * c2;
+  }
+  float sc[CLS_STEPS];
+  float m = -INFINITY;
+  bf16x8 kreg[CLS_STEPS], vreg[CLS_STEPS];
+#pragma unroll
+  for (int it = 0; it < CLS_STEPS; ++it) {
+    if (8 * it < T) {
+      const int key = 8 * it + ks, kc = key < T ? key : T - 1;
+      kreg[it] = *(const bf16x8*)(base + a.H * HD + (size_t)kc * ld + part * 8);
+    }
+  }
+#pragma unroll
+  for (int it = 0; it < CLS_STEPS; ++it) {
+    if (8 * it < T) {
+      const int key = 8 * it + ks, kc = key < T ? key : T - 1;       // padded keys carry p = 0
+      vreg[it] = *(const bf16x8*)(base + 2 * a.H * HD + (size_t)kc * ld + part * 8);
+    }
+  }
+#pragma unroll
+  for (int it = 0; it < CLS_STEPS; ++it) {
+    if (8 * it < T) {
+      const int key = 8 * it + ks;
+      const bf16x8 kv = kreg[it];
+      float d = 0.f;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) d = fmaf(q[e], (float)kv[e], d);
+      d += __shfl_xor(d, 1); d += __shfl_xor(d, 2); d += __shfl_xor(d, 4);
+      sc[it] = key < T ? d : -INFINITY;
+      m = fmaxf(m, sc[it]);
+    }
+  }
+  m = fmaxf(m, __shfl_xor(m, 8)); m = fmaxf(m, __shfl_xor(m, 16)); m = fmaxf(m, __shfl_xor(m, 32));
+  float l = 0.f;
+#pragma unroll
+  for (int it = 0; it < CLS_STEPS; ++it) {
+    if (8 * it < T) { sc[it] = __builtin_amdgcn_exp2f(sc[it] - m); l += sc[it]; }
+  }
+  l += __shfl_xor(l, 8); l += __shfl_xor(l, 16); l += __shfl_xor(l, 32);
+  if (lane == 0 && a.lse2) a.lse2[(size_t)h * a.total_rows + r0] = m + log2f(l);
+  float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int it = 0; it < CLS_STEPS; ++it) {
+    if (8 * it < T) {
+      const bf16x8 vv = vreg[it];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = fmaf(sc[it], (float)vv[e], o[e]);
+    }
+  }
+  const float inv_l = 1.f / l;
+  bf16x8 ov;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    float v = o[e];
+    v += __shfl_xor(v, 8); v += __shfl_xor(v, 16); v += __shfl_xor(v, 32);
+    ov[e] = (bf16)(v * inv_l);
+  }
+  if (ks == 0) *(bf16x8*)(a.out + (size_t)sq * (a.H * HD) + h * HD + part * 8) = ov;
+}
+
+}  // namespace
+
+// The host's copy of a ragged batch's offsets, checked before anything is launched (common.h): n_seq + 1 entries from 0, every length
+// in [1, 197].  *total_rows receives off[n_seq].
+int rovit_check_ragged_offsets(const int* off, int n_seq, const char* what, int* total_rows) {
+  ROVIT_CHECK_ARG(off, ROVIT_ERR_NULL, "%s: null seq_offsets_host", what);
+  ROVIT_CHECK_ARG(n_seq > 0, ROVIT_ERR_SHAPE, "%s: n_seq must be >= 1, got %d", what, n_seq);
+  ROVIT_CHECK_ARG(off[0] == 0, ROVIT_ERR_SHAPE, "%s: seq_offsets_host[0] must be 0, got %d", what, off[0]);
+  for (int s = 0; s < n_seq; ++s) {
+    const long len = (long)off[s + 1] - off[s];
+    ROVIT_CHECK_ARG(len >= 1 && len <= TMAX, ROVIT_ERR_SHAPE,
+                    "%s: seq_offsets_host must increase by a length in [1, %d]; sequence %d has %ld rows", what, TMAX, s, len);
+  }
+  *total_rows = off[n_seq];
+  return ROVIT_OK;
+}
+
+// internal (common.h): sequences [s0, s0 + n_seq) of a ragged batch whose offsets the caller has checked
+int rovit_attention_fwd_ragged_range(const void* qkv, void* out, float* lse2, const int* off_dev, int s0, int n_seq, int total_rows, int heads,
+                                     float scale, rovit_stream_t stream) {
+  RaggedAttnArgs a{};
+  a.qkv = (const bf16*)qkv; a.out = (bf16*)out; a.lse2 = lse2; a.off = off_dev; a.s0 = s0; a.total_rows = total_rows; a.H = heads; a.scale = scale;
+  const size_t lds = (size_t)2 * TP * AST * sizeof(bf16);
+  ROVIT_CHECK_ARG(rovit_set_max_lds((const void*)attn_fwd_ragged_kernel, lds), ROVIT_ERR_LAUNCH, "attention_fwd_ragged: cannot raise the LDS limit");
+  hipLaunchKernelGGL(attn_fwd_ragged_kernel, dim3(n_seq * heads), dim3(NW * 64), lds, (hipStream_t)stream, a);
+  ROVIT_CHECK_LAUNCH("attn_fwd_ragged_kernel");
+  return ROVIT_OK;
+}
+int rovit_attention_cls_fwd_ragged_range(const void* qkv, void* out, float* lse2, const float* x_rows, float* x_cls, const int* off_dev, int s0,
+                                         int n_seq, int total_rows, int heads, float scale, rovit_stream_t stream) {
+  RaggedAttnArgs a{};
+  a.qkv = (const bf16*)qkv; a.out = (bf16*)out; a.lse2 = lse2; a.off = off_dev; a.s0 = s0; a.total_rows = total_rows; a.H = heads; a.scale = scale;
+  a.x_rows = x_rows; a.x_cls = x_cls;
+  const int items = n_seq * heads;
+  hipLaunchKernelGGL(attn_cls_fwd_ragged_kernel, dim3((items + 3) / 4), dim3(256), 0, (hipStream_t)stream, a, items);
+  ROVIT_CHECK_LAUNCH("attn_cls_fwd_ragged_kernel");
+  return ROVIT_OK;
+}
+
+namespace {
+int check_ragged_attn(const char* what, const void* qkv, const void* out, const int* off_dev, const int* off_host, int n_seq, int heads,
+                      int head_dim, int* total_rows) {
+  ROVIT_CHECK_ARG(qkv, ROVIT_ERR_NULL, "%s: null qkv", what);
+  ROVIT_CHECK_ARG(out, ROVIT_ERR_NULL, "%s: null out", what);
+  ROVIT_CHECK_ARG(off_dev, ROVIT_ERR_NULL, "%s: null seq_offsets_dev", what);
+  int rc = rovit_check_ragged_offsets(off_host, n_seq, what, total_rows);
+  if (rc) return rc;
+  ROVIT_CHECK_ARG(heads > 0 && head_dim == HD && (long)n_seq * heads < (1L << 31), ROVIT_ERR_SHAPE,
+                  "%s: unsupported heads %d / head_dim %d (head_dim must be %d)", what, heads, head_dim, HD);
+  ROVIT_CHECK_ARG(rovit_aligned16(qkv) && rovit_aligned16(out), ROVIT_ERR_ALIGN, "%s: qkv and out must be 16-byte aligned", what);
+  return ROVIT_OK;
+}
+}  // namespace
+
+// rovit_attention_fwd on a ragged batch (include/rovit_hip.h)
+extern "C" int rovit_attention_fwd_ragged(const void* qkv, void* out, float* lse2, const int* seq_offsets_dev, const int* seq_offsets_host,
+                                          int n_seq, int heads, int head_dim, float scale, rovit_stream_t stream) {
+  int total = 0;
+  int rc = check_ragged_attn("attention_fwd_ragged", qkv, out, seq_offsets_dev, seq_offsets_host, n_seq, heads, head_dim, &total);
+  if (rc) return rc;
+  return rovit_attention_fwd_ragged_range(qkv, out, lse2, seq_offsets_dev, 0, n_seq, total, heads, scale, stream);
+}
+// rovit_attention_cls_fwd on a ragged batch, compact output (include/rovit_hip.h)
+extern "C" int rovit_attention_cls_fwd_ragged(const void* qkv, void* out, float* lse2, const float* x_rows, float* x_cls,
+                                              const int* seq_offsets_dev, const int* seq_offsets_host, int n_seq, int heads, int head_dim,
+                                              float scale, rovit_stream_t stream) {
+  int total = 0;
+  int rc = check_ragged_attn("attention_cls_fwd_ragged", qkv, out, seq_offsets_dev, seq_offsets_host, n_seq, heads, head_dim, &total);
+  if (rc) return rc;
+  ROVIT_CHECK_ARG(!x_rows == !x_cls, ROVIT_ERR_NULL, "attention_cls_fwd_ragged: x_rows and x_cls go together (both or neither)");
+  return rovit_attention_cls_fwd_ragged_range(qkv, out, lse2, x_rows, x_cls, seq_offsets_dev, 0, n_seq, total, heads, scale, stream);
+}

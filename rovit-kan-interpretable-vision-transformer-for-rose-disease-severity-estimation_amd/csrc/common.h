@@ -259,6 +259,17 @@ int rovit_gradcam_cam(const void* dqkv, const void* wt, const void* xhat1, const
 // base_shared) by seq_img (n_seq) and src (n_seq * tokens) -- rovit_vit_forward_tokens' first launch
 int rovit_gather_token_rows(const float* img_tokens, const float* base_tokens, int n_img, int base_shared, const int* seq_img, const int* src,
                             float* X, int n_seq, int tokens, rovit_stream_t stream);
+// Ragged batches (rovit_vit_forward_ragged): n_seq sequences of 1..197 rows packed back to back, off (n_seq + 1) their row offsets.
+// attention.hip: the check of the HOST copy of the offsets (what: the entry's name for the message; *total_rows = off[n_seq]), and the
+// two attention launches on sequences [s0, s0 + n_seq) of a checked batch (the DEVICE copy; lse2 (H, total_rows) or NULL; the
+// class-token form writes its out / x_cls rows compactly, row = sequence - s0).  perturb.hip: the gather in front of block 0.
+int rovit_check_ragged_offsets(const int* off, int n_seq, const char* what, int* total_rows);
+int rovit_attention_fwd_ragged_range(const void* qkv, void* out, float* lse2, const int* off_dev, int s0, int n_seq, int total_rows, int heads,
+                                     float scale, rovit_stream_t stream);
+int rovit_attention_cls_fwd_ragged_range(const void* qkv, void* out, float* lse2, const float* x_rows, float* x_cls, const int* off_dev, int s0,
+                                         int n_seq, int total_rows, int heads, float scale, rovit_stream_t stream);
+int rovit_gather_token_rows_ragged(const float* img_tokens, const float* base_tokens, int n_img, int base_shared, const int* seq_img,
+                                   const int* src, const int* off_dev, float* X, int n_seq, int total_rows, rovit_stream_t stream);
 // explain.hip: the same bf16 transposed qkv-weight copy on its own (rovit_vit_gradcam_seeded has no head seed to launch it beside)
 int rovit_gradcam_wt(const float* wqkv, void* wt, rovit_stream_t stream);
 // cls_tail.hip: the last block's post-attention half + the final norm on the class-token rows in one launch

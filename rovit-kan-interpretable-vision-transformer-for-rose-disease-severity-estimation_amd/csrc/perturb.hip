@@ -1,4 +1,5 @@
-// Token-row gather of the deletion / insertion curves (rovit_vit_forward_tokens, vit.hip).
+// Token-row gather of the deletion / insertion curves (rovit_vit_forward_tokens and, for sequences of different lengths in one call,
+// rovit_vit_forward_ragged; vit.hip).
 //
 // The patch embedding is a 16x16 convolution with stride 16, so each token row depends on its own patch alone: every row of an image
 // perturbed patch by patch is a row of the clean image's token table or of its baseline's (rovit_vit_embed writes both once).  This
@@ -38,7 +39,52 @@ __global__ __launch_bounds__(256) void gather_token_rows_kernel(const GatherArgs
   a.X[i] = t[c];
 }
 
+// The same gather for a ragged batch (rovit_vit_forward_ragged): sequences of different lengths packed back to back, src one entry per
+// packed row, off (n_seq + 1) the device copy of the sequence offsets.  A row finds its sequence by bisection (the last s with
+// off[s] <= row; at most 18 probes of an array that sits in L2; it ends on some s in [0, n_seq) whatever the array holds), then the
+// image and the table row are clamped as above.
+struct RaggedGatherArgs {
+  const float4* img;
+  const float4* base;
+  const int* seq_img;
+  const int* src;
+  const int* off;
+  float4* X;
+  int n_img, base_shared, n_seq;
+  unsigned total;                          // total_rows * GV  (< 2^31, checked on the host)
+};
+
+__global__ __launch_bounds__(256) void gather_token_rows_ragged_kernel(const RaggedGatherArgs a) {
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= a.total) return;
+  const unsigned row = i / GV, c = i - row * GV;
+  int lo = 0, hi = a.n_seq - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (a.off[mid] <= (int)row) lo = mid; else hi = mid - 1;
+  }
+  const int img = min(max(a.seq_img[lo], 0), a.n_img - 1);
+  const int v = a.src[row];
+  const float4* t = v >= 0 ? a.img + ((size_t)img * GT + min(v, GT - 1)) * GV
+                           : a.base + ((size_t)(a.base_shared ? 0 : img) * GT + min(-1 - v, GT - 1)) * GV;
+  a.X[i] = t[c];
+}
+
 }  // namespace
+
+int rovit_gather_token_rows_ragged(const float* img_tokens, const float* base_tokens, int n_img, int base_shared, const int* seq_img,
+                                   const int* src, const int* off_dev, float* X, int n_seq, int total_rows, rovit_stream_t stream) {
+  ROVIT_CHECK_ARG(img_tokens && base_tokens && seq_img && src && off_dev && X, ROVIT_ERR_NULL, "gather_token_rows_ragged: null pointer");
+  ROVIT_CHECK_ARG(n_img > 0 && n_seq > 0 && total_rows >= n_seq && (long)total_rows * GV < (1L << 31), ROVIT_ERR_SHAPE,
+                  "gather_token_rows_ragged: bad n_img %d / n_seq %d / total_rows %d", n_img, n_seq, total_rows);
+  ROVIT_CHECK_ARG(rovit_aligned16(img_tokens) && rovit_aligned16(base_tokens) && rovit_aligned16(X), ROVIT_ERR_ALIGN,
+                  "gather_token_rows_ragged: token tables and X must be 16-byte aligned");
+  RaggedGatherArgs a{(const float4*)img_tokens, (const float4*)base_tokens, seq_img, src, off_dev, (float4*)X, n_img, base_shared ? 1 : 0,
+                     n_seq, (unsigned)((long)total_rows * GV)};
+  hipLaunchKernelGGL(gather_token_rows_ragged_kernel, dim3((a.total + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
+  ROVIT_CHECK_LAUNCH("gather_token_rows_ragged");
+  return ROVIT_OK;
+}
 
 int rovit_gather_token_rows(const float* img_tokens, const float* base_tokens, int n_img, int base_shared, const int* seq_img, const int* src,
                             float* X, int n_seq, int tokens, rovit_stream_t stream) {

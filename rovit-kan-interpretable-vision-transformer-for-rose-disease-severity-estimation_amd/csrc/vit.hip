@@ -310,17 +310,25 @@ struct TokenRows {
   const int* seq_img;
   const int* src;
 };
+// rovit_vit_forward_ragged: the sequences' row offsets (n_seq + 1), device and host copy; the host copy has been checked
+struct RaggedSeqs {
+  const int* dev;
+  const int* host;
+};
 
 // prepare: 0 = the weights in `prep` are current; 1 = prepare them from `params` first; 2 = ... and write the constant tables too.
 // tokens: the sequence length (197 but for rovit_vit_forward_tokens); rows: gather X from token tables instead of embedding `images`.
+// rg: the `batch` sequences have different lengths (rows required, inference only).  The rows of a half then come from the offsets
+// instead of batch * tokens -- every row-wise launch takes its row range as it takes a half-batch's -- and four things change: the gather,
+// the two attention kernels, and the last block's class-token rows, which the class-token attention writes compactly for the tail.
 int vit_forward_impl(const float* images, const float* const* params, const void* prep, void* workspace, float* features,
                      void* const* attn_taps, float* const* prob_taps, int batch, int depth, int training, int mlp_path,
                      rovit_stream_t stream, int prepare = 0, float* rollout = nullptr, int head_fusion = 0, bool gradcam = false,
-                     int tokens = T, const TokenRows* rows = nullptr) {
+                     int tokens = T, const TokenRows* rows = nullptr, const RaggedSeqs* rg = nullptr) {
   ROVIT_CHECK_ARG((images || rows) && features, ROVIT_ERR_NULL, "vit_forward: null images/features");
   RUN(check_common(params, prep, workspace, batch, depth, mlp_path));
   const Prep P(depth);
-  const Plan L(batch, depth, training, tokens);
+  const Plan L(rg ? rg->host[batch] : batch, depth, training, rg ? 1 : tokens);      // ragged: the inference plan of off[n_seq] rows
   const char* pb = (const char*)prep;
   char* ws = (char*)workspace;
   float* X = (float*)(ws + L.X);
@@ -342,7 +350,10 @@ int vit_forward_impl(const float* images, const float* const* params, const void
     RUN(vit_prepare_impl(params, const_cast<void*>(prep), depth, stream, ss_prep ? (rovit_stream_t)ss_prep->stream : stream, prepare == 2));
     if (ss_prep && !(ev_prep = hand_over(ss_prep, ss_prep->stream, nullptr, true))) { rovit_set_error("vit_forward: event record failed"); return ROVIT_ERR_LAUNCH; }
   }
-  if (rows) {
+  if (rg) {
+    RUN(rovit_gather_token_rows_ragged(rows->img, rows->base, rows->n_img, rows->base_shared, rows->seq_img, rows->src, rg->dev, X, batch, M,
+                                       stream));
+  } else if (rows) {
     RUN(rovit_gather_token_rows(rows->img, rows->base, rows->n_img, rows->base_shared, rows->seq_img, rows->src, X, batch, tokens, stream));
   } else {
     RUN(embed_rows(images, params, pb, P, X, batch, stream));
@@ -353,8 +364,15 @@ int vit_forward_impl(const float* images, const float* const* params, const void
   // persistent launch with ~6 us of ramp (dispatch, weight prologue, first tile, tail), which the other half's
   // kernels now cover.  Each half asks for half of the CUs (rovit_set_cu_budget) so the two chains co-reside.
   SideStream* ss = (two_streams_enabled() && !taps && batch >= 16) ? side_stream() : nullptr;
-  struct Half { int b0, nb; rovit_stream_t st; };
-  Half halves[2] = {{0, ss ? (batch + 1) / 2 : batch, stream}, {(batch + 1) / 2, ss ? batch / 2 : 0, ss ? (rovit_stream_t)ss->stream : stream}};
+  struct Half { int b0, nb, r0, nr; rovit_stream_t st; };     // sequences [b0, b0 + nb) = rows [r0, r0 + nr)
+  int cut = (batch + 1) / 2;
+  if (rg && ss) {       // ragged: the sequence boundary where the first half first reaches half of the rows (both halves keep a sequence)
+    cut = 1;
+    while (cut < batch - 1 && 2L * rg->host[cut] < M) ++cut;
+  }
+  const int cut_row = rg ? rg->host[cut] : cut * tokens;
+  Half halves[2] = {{0, ss ? cut : batch, 0, ss ? cut_row : M, stream},
+                    {cut, ss ? batch - cut : 0, cut_row, ss ? M - cut_row : 0, ss ? (rovit_stream_t)ss->stream : stream}};
   const int nh = ss ? 2 : 1;
   if (ss) {
     if (!ss_prep) ss->next = 0;        // (the preparation above has taken events of this call already)
@@ -374,17 +392,16 @@ int vit_forward_impl(const float* images, const float* const* params, const void
     const bool cls_only = (i == depth - 1);
     const int rs = cls_only ? tokens : 1;
     // per-half views: r = first row of the half; activations are row-major with the images contiguous
-#define ROWS(ptr, width, esz) ((ptr) + (size_t)h.b0 * tokens * (width) * (esz))
+#define ROWS(ptr, width, esz) ((ptr) + (size_t)h.r0 * (width) * (esz))
     // LayerNorm1 of block 0 is a kernel of its own; every other LayerNorm of the loop is fused into the epilogue
     // of the GEMM that produces its input (proj -> norm2, fc2 -> next block's norm1).
     if (i == 0) EACH_HALF {
       const Half& h = halves[hh];
-      RUN(rovit_layernorm_fwd(X + (size_t)h.b0 * tokens * D, ROWS(s + L.xhat1, D, 2), (float*)ROWS(s + L.rstd1, 1, 4), h.nb * tokens, D, eps,
-                              h.st));
+      RUN(rovit_layernorm_fwd(X + (size_t)h.r0 * D, ROWS(s + L.xhat1, D, 2), (float*)ROWS(s + L.rstd1, 1, 4), h.nr, D, eps, h.st));
     }
     if (!qkv_done) EACH_HALF {
       const Half& h = halves[hh];
-      RUN(rovit_gemm_nt(ROWS(s + L.xhat1, D, 2), D, q + P.wqkv, D, h.nb * tokens, 3 * D, D, (const float*)(q + P.bqkv), EPI_BF16,
+      RUN(rovit_gemm_nt(ROWS(s + L.xhat1, D, 2), D, q + P.wqkv, D, h.nr, 3 * D, D, (const float*)(q + P.bqkv), EPI_BF16,
                         ROWS(s + L.qkv, 3 * D, 2), 3 * D, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, h.st));
     }
     qkv_done = false;
@@ -398,7 +415,16 @@ int vit_forward_impl(const float* images, const float* const* params, const void
       }
       // the last block: only the class token's attention output is consumed (the half behind it runs on those rows alone), and a query's
       // output needs no other query -- 197 scores per (image, head) instead of 197 x 197 (taps want every token's output: full kernel)
-      if (cls_only && !taps) {
+      if (rg) {
+        // the class-token form also compacts: its output rows and the class-token rows of X, one per sequence, into the half's OWN rows
+        // of the o and act buffers (the other half, on the other stream, may still be reading its rows of them in the block before)
+        if (cls_only) {
+          RUN(rovit_attention_cls_fwd_ragged_range(s + L.qkv, ROWS(s + L.o, D, 2), nullptr, X, (float*)ROWS(s + L.act, MLP, 2), rg->dev, h.b0,
+                                                   h.nb, M, H, 0.125f, h.st));
+        } else {
+          RUN(rovit_attention_fwd_ragged_range(s + L.qkv, s + L.o, nullptr, rg->dev, h.b0, h.nb, M, H, 0.125f, h.st));
+        }
+      } else if (cls_only && !taps) {
         RUN(rovit_attention_cls_fwd(ROWS(s + L.qkv, 3 * D, 2), ROWS(s + L.o, D, 2), (float*)(s + L.lse) + (size_t)h.b0 * H * tokens, h.nb, tokens,
                                     H, D / H, 0.125f, h.st));
       } else {
@@ -424,7 +450,14 @@ int vit_forward_impl(const float* images, const float* const* params, const void
         const Half& h = halves[hh];
         // (training, and the Grad-CAM++ forward: keep what the class-token backward reads)
         const bool keep = training || gradcam;
-        RUN(rovit_cls_tail_fwd(ROWS(s + L.o, D, 2), X + (size_t)h.b0 * tokens * D, q + P.wproj, bp[B_PROJB], q + P.wfc1, (const float*)(q + P.bfc1),
+        if (rg) {      // dense class-token rows (above): tokens = 1
+          RUN(rovit_cls_tail_fwd(ROWS(s + L.o, D, 2), (float*)ROWS(s + L.act, MLP, 2), q + P.wproj, bp[B_PROJB], q + P.wfc1,
+                                 (const float*)(q + P.bfc1), q + P.wfc2, bp[B_FC2B], params[P_NORM_W], params[P_NORM_B], nullptr, nullptr, nullptr,
+                                 nullptr, features + (size_t)h.b0 * D, (float*)(ws + L.xhat_cls) + (size_t)h.b0 * D,
+                                 (float*)(ws + L.rstd_cls) + h.b0, h.nb, 1, eps, h.st));
+          continue;
+        }
+        RUN(rovit_cls_tail_fwd(ROWS(s + L.o, D, 2), X + (size_t)h.r0 * D, q + P.wproj, bp[B_PROJB], q + P.wfc1, (const float*)(q + P.bfc1),
                                q + P.wfc2, bp[B_FC2B], params[P_NORM_W], params[P_NORM_B], keep ? ROWS(s + L.xhat2, D, 2) : nullptr,
                                keep ? (float*)ROWS(s + L.rstd2, 1, 4) : nullptr, keep ? ROWS(s + L.act, MLP, 2) : nullptr,
                                keep ? ROWS(s + L.dact, MLP, 2) : nullptr, features + (size_t)h.b0 * D,
@@ -434,50 +467,50 @@ int vit_forward_impl(const float* images, const float* const* params, const void
     }
     // Everything behind the attention in ONE launch ("block tail", mlp_fused.hip: proj + residual + norm2 + MLP + residual + next
     // norm1 + the NEXT block's qkv projection; the residual stream stays in registers between the halves).
-    if (!cls_only && mlp_one_launch(mlp_path, (long)batch * tokens)) {
+    if (!cls_only && mlp_one_launch(mlp_path, (long)M)) {
       char* sn = ws + L.blk0 + (size_t)(i + 1) * L.blk_stride;            // next block's saved-activation area
       const bool tail_qkv = true;
       qkv_done = tail_qkv;                                                // block i + 1 finds its qkv projection written
       EACH_HALF {
         const Half& h = halves[hh];
-        float* Xh = X + (size_t)h.b0 * tokens * D;
+        float* Xh = X + (size_t)h.r0 * D;
         RUN(rovit_block_tail_fwd(ROWS(s + L.o, D, 2), q + P.wmlp, bp[B_PROJB], (const float*)(q + P.bfc1), bp[B_FC2B], Xh,
                                  training ? ROWS(s + L.xhat2, D, 2) : nullptr, training ? (float*)ROWS(s + L.rstd2, 1, 4) : nullptr,
                                  training ? ROWS(s + L.act, 32, 2) : nullptr, training ? ROWS(s + L.dact, 32, 2) : nullptr,
                                  ROWS(sn + L.xhat1, D, 2), (float*)ROWS(sn + L.rstd1, 1, 4),
                                  tail_qkv ? (const float*)(q + P.blk_stride + P.bqkv) : nullptr, tail_qkv ? ROWS(sn + L.qkv, 3 * D, 2) : nullptr,
-                                 eps, h.nb * tokens, batch * tokens, h.st));
+                                 eps, h.nr, M, h.st));
       }
       continue;
     }
     EACH_HALF {
       const Half& h = halves[hh];
-      float* Xh = X + (size_t)h.b0 * tokens * D;
+      float* Xh = X + (size_t)h.r0 * D;
       if (cls_only) {
         RUN(rovit_gemm_nt(ROWS(s + L.o, D, 2), D * rs, q + P.wproj, D, h.nb, D, D, bp[B_PROJB], EPI_RESID, nullptr, 0, nullptr, Xh, D * rs,
                           nullptr, 0, nullptr, 0, h.st));
         RUN(rovit_layernorm_fwd_rows(Xh, ROWS(s + L.xhat2, D, 2), (float*)ROWS(s + L.rstd2, 1, 4), h.nb, tokens, eps, h.st));
       } else {
-        RUN(rovit_gemm_resid_ln(ROWS(s + L.o, D, 2), D, q + P.wproj, D, h.nb * tokens, D, bp[B_PROJB], Xh, ROWS(s + L.xhat2, D, 2),
+        RUN(rovit_gemm_resid_ln(ROWS(s + L.o, D, 2), D, q + P.wproj, D, h.nr, D, bp[B_PROJB], Xh, ROWS(s + L.xhat2, D, 2),
                                 (float*)ROWS(s + L.rstd2, 1, 4), eps, h.st));
       }
     }
     // two-launch MLP half (small batches, and the CLS rows of the last block): fc1 + GELU, then fc2 + residual + next LayerNorm
     EACH_HALF {
       const Half& h = halves[hh];
-      RUN(rovit_gemm_nt(ROWS(s + L.xhat2, D, 2), D * rs, q + P.wfc1, D, cls_only ? h.nb : h.nb * tokens, MLP, D, (const float*)(q + P.bfc1),
+      RUN(rovit_gemm_nt(ROWS(s + L.xhat2, D, 2), D * rs, q + P.wfc1, D, cls_only ? h.nb : h.nr, MLP, D, (const float*)(q + P.bfc1),
                         EPI_GELU, ROWS(s + L.act, MLP, 2), MLP * rs, training ? ROWS(s + L.dact, MLP, 2) : nullptr, nullptr, 0, nullptr, 0,
                         nullptr, 0, h.st));
     }
     EACH_HALF {
       const Half& h = halves[hh];
-      float* Xh = X + (size_t)h.b0 * tokens * D;
+      float* Xh = X + (size_t)h.r0 * D;
       if (cls_only) {
         RUN(rovit_gemm_nt(ROWS(s + L.act, MLP, 2), MLP * rs, q + P.wfc2, MLP, h.nb, D, MLP, bp[B_FC2B], EPI_RESID, nullptr, 0, nullptr, Xh,
                           D * rs, nullptr, 0, nullptr, 0, h.st));
       } else {
         char* sn = ws + L.blk0 + (size_t)(i + 1) * L.blk_stride;          // next block's saved-activation area
-        RUN(rovit_gemm_resid_ln(ROWS(s + L.act, MLP, 2), MLP, q + P.wfc2, MLP, h.nb * tokens, MLP, bp[B_FC2B], Xh, ROWS(sn + L.xhat1, D, 2),
+        RUN(rovit_gemm_resid_ln(ROWS(s + L.act, MLP, 2), MLP, q + P.wfc2, MLP, h.nr, MLP, bp[B_FC2B], Xh, ROWS(sn + L.xhat1, D, 2),
                                 (float*)ROWS(sn + L.rstd1, 1, 4), eps, h.st));
       }
     }
@@ -518,6 +551,42 @@ extern "C" int rovit_vit_forward_tokens(const float* img_tokens, const float* ba
   const TokenRows rows{img_tokens, base_tokens, n_img, base_shared, seq_img, src};
   return vit_forward_impl(nullptr, params, prep, workspace, features, nullptr, nullptr, n_seq, depth, 0, mlp_path, stream, 0, nullptr, 0,
                           false, tokens, &rows);
+}
+
+// The same forward of n_seq sequences of DIFFERENT lengths in one call (token-dropped sequences: perturbation='drop').  The sequences are
+// packed back to back: sequence s owns rows [off[s], off[s + 1]) of src and of every activation, 1 <= length <= 197.  The offsets come
+// twice: the host copy is checked here, before anything is launched, and plans the call (row count, the two-stream cut); the kernels
+// read the device copy and clamp it (attention.hip).  No device-to-host copy.  Workspace: rovit_vit_ragged_workspace_bytes(max_rows,
+// depth) for any max_rows >= off[n_seq] -- the inference plan of that many rows, which holds any n_seq <= max_rows; the call lays out
+// the plan of off[n_seq] rows inside it, so the caller must have sized it for at least that many (this entry is not told the size).
+extern "C" size_t rovit_vit_ragged_workspace_bytes(int max_rows, int depth) {
+  return max_rows > 0 && depth > 0 && depth <= 64 ? Plan(max_rows, depth, 0, 1).total : 0;
+}
+extern "C" int rovit_vit_forward_ragged(const float* img_tokens, const float* base_tokens, int n_img, int base_shared, const int* seq_img,
+                                        const int* src, const int* seq_offsets_dev, const int* seq_offsets_host, const float* const* params,
+                                        const void* prep, void* workspace, float* features, int n_seq, int depth, int mlp_path,
+                                        rovit_stream_t stream) {
+  ROVIT_CHECK_ARG(img_tokens, ROVIT_ERR_NULL, "vit_forward_ragged: null img_tokens");
+  ROVIT_CHECK_ARG(base_tokens, ROVIT_ERR_NULL, "vit_forward_ragged: null base_tokens");
+  ROVIT_CHECK_ARG(seq_img, ROVIT_ERR_NULL, "vit_forward_ragged: null seq_img");
+  ROVIT_CHECK_ARG(src, ROVIT_ERR_NULL, "vit_forward_ragged: null src");
+  ROVIT_CHECK_ARG(seq_offsets_dev, ROVIT_ERR_NULL, "vit_forward_ragged: null seq_offsets_dev");
+  ROVIT_CHECK_ARG(params, ROVIT_ERR_NULL, "vit_forward_ragged: null params");
+  ROVIT_CHECK_ARG(prep, ROVIT_ERR_NULL, "vit_forward_ragged: null prep");
+  ROVIT_CHECK_ARG(workspace, ROVIT_ERR_NULL, "vit_forward_ragged: null workspace");
+  ROVIT_CHECK_ARG(features, ROVIT_ERR_NULL, "vit_forward_ragged: null features");
+  ROVIT_CHECK_ARG(n_img > 0, ROVIT_ERR_SHAPE, "vit_forward_ragged: n_img must be >= 1, got %d", n_img);
+  ROVIT_CHECK_ARG(depth > 0 && depth <= 64, ROVIT_ERR_SHAPE, "vit_forward_ragged: depth must be in [1, 64], got %d", depth);
+  ROVIT_CHECK_ARG(mlp_path == ROVIT_MLP_AUTO || mlp_path == ROVIT_MLP_TWO_LAUNCH || mlp_path == ROVIT_MLP_ONE_LAUNCH, ROVIT_ERR_SHAPE,
+                  "vit_forward_ragged: mlp_path must be ROVIT_MLP_AUTO, _TWO_LAUNCH or _ONE_LAUNCH (got %d)", mlp_path);
+  ROVIT_CHECK_ARG(rovit_aligned16(prep), ROVIT_ERR_ALIGN, "vit_forward_ragged: prep must be 16-byte aligned");
+  ROVIT_CHECK_ARG(rovit_aligned16(workspace), ROVIT_ERR_ALIGN, "vit_forward_ragged: workspace must be 16-byte aligned");
+  int total_rows = 0;
+  RUN(rovit_check_ragged_offsets(seq_offsets_host, n_seq, "vit_forward_ragged", &total_rows));
+  const TokenRows rows{img_tokens, base_tokens, n_img, base_shared, seq_img, src};
+  const RaggedSeqs rg{seq_offsets_dev, seq_offsets_host};
+  return vit_forward_impl(nullptr, params, prep, workspace, features, nullptr, nullptr, n_seq, depth, 0, mlp_path, stream, 0, nullptr, 0,
+                          false, 1, &rows, &rg);
 }
 
 // rovit_vit_prepare + rovit_vit_forward as ONE call (a training step prepares the weights after every optimizer step): the blocks'

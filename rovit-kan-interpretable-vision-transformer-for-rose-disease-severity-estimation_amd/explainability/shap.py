@@ -17,7 +17,7 @@ class PatchSHAP:
 
     def explain_batch(self, images: torch.Tensor, class_idx=None, target='class', **kwargs):
         """patch_shap's result dict for every image (a dict name -> result for a list of targets), tensors on the device.  ``kwargs``:
-        num_samples, players, perturbation, baseline, seed, chunk, upsample, return_values (rovit_hip.shap.patch_shap)."""
+        num_samples, players, perturbation, baseline, seed, chunk, upsample, return_values, ragged (rovit_hip.shap.patch_shap)."""
         self.model.eval()
         return patch_shap(self.model, images.to(self.device), target, class_idx, **kwargs)
 

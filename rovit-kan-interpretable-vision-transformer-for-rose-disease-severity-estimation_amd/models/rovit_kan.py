@@ -238,20 +238,22 @@ class RoViTKAN(nn.Module):
         return relevance.attention_relevance(self, x, target, class_idx, upsample, chunk, return_values)
 
     def perturbation_curves(self, x: torch.Tensor, saliency, target='class', class_idx=None, modes=('deletion', 'insertion'),
-                            steps: int = 28, perturbation: str = 'replace', baseline=None, chunk: int = 256):
+                            steps: int = 28, perturbation: str = 'replace', baseline=None, chunk: int = 256, ragged: bool = False):
         """Extension (not in the reference): deletion / insertion curves and their areas (Petsiuk et al. 2018) of one or several
         saliency maps for cls_logits' probability, ordinal_severity, mu, log_var or kan_severity on the GPU, patches replaced by a
-        baseline's or dropped from the sequence (rovit_hip.perturbation)."""
+        baseline's or dropped from the sequence (rovit_hip.perturbation; ``ragged``: dropped sequences of all lengths share backbone calls)."""
         from rovit_hip import perturbation as pert
-        return pert.perturbation_curves(self, x, saliency, target, class_idx, modes, steps, perturbation, baseline, chunk)
+        return pert.perturbation_curves(self, x, saliency, target, class_idx, modes, steps, perturbation, baseline, chunk, ragged)
 
     def patch_shap(self, x: torch.Tensor, target='class', class_idx=None, num_samples: int = 2048, players=14, perturbation: str = 'drop',
-                   baseline=None, seed: int = 0, chunk: int = 256, upsample: bool = True, return_values: bool = False):
+                   baseline=None, seed: int = 0, chunk: int = 256, upsample: bool = True, return_values: bool = False,
+                   ragged: bool = False):
         """Extension (not in the reference): KernelSHAP values of the patches, or of any grouping of them into players, for the
         probability of a class, ordinal_severity, mu, log_var or kan_severity on the GPU; absent players' patches are dropped from the
         sequence or replaced by a baseline's, and the values sum to f(image) - f(nothing) (rovit_hip.shap)."""
         from rovit_hip import shap
-        return shap.patch_shap(self, x, target, class_idx, num_samples, players, perturbation, baseline, seed, chunk, upsample, return_values)
+        return shap.patch_shap(self, x, target, class_idx, num_samples, players, perturbation, baseline, seed, chunk, upsample, return_values,
+                               ragged)
 
     def kan_edge_stats(self, x_or_loader, chunk: int = 256):
         """Extension (not in the reference): per-edge activation statistics of the KAN head over images (a (B,3,224,224) tensor, or an

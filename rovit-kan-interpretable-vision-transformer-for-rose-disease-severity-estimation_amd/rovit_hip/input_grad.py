@@ -149,6 +149,12 @@ class _Backbone:
              tokens, self.pa, ptr(self.eng.prep), ptr(ws), ptr(feats), n, self.vit.depth, int(mlp_path), stream_ptr())
         return feats
 
+    def forward_ragged(self, img_tokens, base_tokens, base_shared, seq_img, src, offsets_dev, offsets_host, ws, mlp_path):
+        """The same for n sequences of different lengths packed back to back (rovit_vit_forward_ragged; rovit_hip.ragged): src one
+        entry per packed row, the (n + 1,) row offsets on the device and as a host array; ws from ragged.take_ws."""
+        from .ragged import forward_ragged
+        return forward_ragged(self, img_tokens, base_tokens, base_shared, seq_img, src, offsets_dev, offsets_host, ws, mlp_path)
+
     def relevance(self, ws, seed, out, scratch):
         """The dgrad chain alone with one relevance step per block (rovit_vit_backward_relevance): out (n,197) = row 0 of R_L."""
         n = out.shape[0]

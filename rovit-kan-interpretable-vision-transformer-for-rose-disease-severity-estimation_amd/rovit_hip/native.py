@@ -72,6 +72,8 @@ SIGNATURES = {
     'rovit_attention_relevance_step': (_i, [_vp] * 5 + [_i, _i, _vp]),
     'rovit_vit_embed': (_i, [_vp] * 4 + [_i, _i, _vp]),
     'rovit_vit_forward_tokens': (_i, [_vp, _vp, _i, _i, _vp, _vp, _i] + [_vp] * 4 + [_i, _i, _i, _vp]),
+    'rovit_vit_ragged_workspace_bytes': (_sz, [_i, _i]),
+    'rovit_vit_forward_ragged': (_i, [_vp, _vp, _i, _i] + [_vp] * 8 + [_i, _i, _i, _vp]),
     'rovit_gemm_nt': (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _vp]),
     'rovit_gemm_resid_ln': (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp]),
     'rovit_mlp_stream_bytes': (_sz, []),
@@ -95,6 +97,8 @@ SIGNATURES = {
     'rovit_attention_bwd': (_i, [_vp] * 5 + [_i] * 4 + [_f, _vp]),
     'rovit_attention_cls_fwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
     'rovit_attention_cls_bwd': (_i, [_vp] * 5 + [_i] * 4 + [_f, _vp]),
+    'rovit_attention_fwd_ragged': (_i, [_vp] * 5 + [_i, _i, _i, _f, _vp]),
+    'rovit_attention_cls_fwd_ragged': (_i, [_vp] * 7 + [_i, _i, _i, _f, _vp]),
     'rovit_layernorm_fwd': (_i, [_vp, _vp, _vp, _i, _i, _f, _vp]),
     'rovit_layernorm_bwd': (_i, [_vp] * 5 + [_i, _i, _vp]),
     'rovit_im2col': (_i, [_vp, _vp, _i, _vp]),

@@ -10,6 +10,7 @@ baseline's.  Each image and its baseline are embedded once (rovit_vit_embed) and
 front of block 0 (rovit_vit_forward_tokens; csrc/perturb.hip): bit-identical to running the forward on the perturbed pixels, with no
 pixel tensor per step.  ``perturbation='drop'`` removes the perturbed tokens from the sequence instead: no baseline square enters the
 model and every kept token keeps its own position embedding."""
+import numpy as np
 import torch
 
 from .input_grad import _Backbone, _check_args, _head_outputs, _target_value
@@ -78,8 +79,10 @@ def trapezoid_auc(curve: torch.Tensor, fractions: torch.Tensor) -> torch.Tensor:
     return torch.trapezoid(curve, fractions, dim=1)
 
 
-def _check(model, x, saliency, target, class_idx, modes, steps, perturbation, baseline, chunk):
+def _check(model, x, saliency, target, class_idx, modes, steps, perturbation, baseline, chunk, ragged=False):
     what = 'perturbation_curves'
+    if not isinstance(ragged, bool):
+        raise RovitHipError(f'{what}: ragged must be a bool, got {ragged!r}')
     if isinstance(steps, bool) or not isinstance(steps, int) or not 1 <= steps <= NP:
         raise RovitHipError(f'{what}: steps must be an int in [1, {NP}], got {steps!r}')
     ms = [modes] if isinstance(modes, str) else list(modes) if isinstance(modes, (list, tuple)) else None
@@ -109,7 +112,7 @@ def _check(model, x, saliency, target, class_idx, modes, steps, perturbation, ba
 
 
 def perturbation_curves(model, x: torch.Tensor, saliency, target='class', class_idx=None, modes=('deletion', 'insertion'),
-                        steps: int = 28, perturbation: str = 'replace', baseline=None, chunk: int = 256):
+                        steps: int = 28, perturbation: str = 'replace', baseline=None, chunk: int = 256, ragged: bool = False):
     """Deletion / insertion curves of saliency maps for one RoViTKAN output, every image of the batch.
 
     ``saliency``: (B,14,14), (B,196), (B,224,224) or (B,3,224,224); a patch's score is the sum of the map over its pixels and channels
@@ -125,10 +128,15 @@ def perturbation_curves(model, x: torch.Tensor, saliency, target='class', class_
     The unperturbed and the fully perturbed sequence of each image are computed once for every map and mode, so all curves of an image
     start and end on identical values.  Sequences of equal length are packed into backbone calls of ``chunk``; the MLP path is the
     engine's override or is chosen from ``chunk`` x tokens, never from a call's size, so an image's values do not depend on the others.
+    ``ragged=True`` with ``'drop'``: the sequences of ALL lengths are packed, longest first, into calls of ``chunk`` x 197 rows
+    (rovit_hip.ragged, rovit_vit_forward_ragged) -- a handful of backbone calls instead of one and more per length; the MLP path is then
+    the engine's override or chosen from ``chunk`` x 197 alone.  A short sequence may so take the other MLP path than with
+    ``ragged=False`` (the two paths agree to bf16 rounding, not bit for bit), which is why the default stays False.  With
+    ``'replace'`` every sequence has 197 tokens and the flag changes nothing.
     Eval semantics, as input_gradients: the bf16 engine whatever ``precision`` says, no dropout, no ``.grad`` written, flags untouched,
     workspaces from the engine's pool.  Every bad argument is refused (RovitHipError) before anything is launched."""
     from .functions import VitEngine
-    ms, maps, targets = _check(model, x, saliency, target, class_idx, modes, steps, perturbation, baseline, chunk)
+    ms, maps, targets = _check(model, x, saliency, target, class_idx, modes, steps, perturbation, baseline, chunk, ragged)
     dev = x.device
     B = x.shape[0]
     ks = step_counts(steps)
@@ -162,25 +170,47 @@ def perturbation_curves(model, x: torch.Tensor, saliency, target='class', class_
         override = bb.eng.mlp_path if bb.eng.mlp_path is not None else VitEngine.default_mlp_path
         C_ = model.classification_head.fc2.out_features
         raw = torch.empty(len(combos), B, C_ if target == 'class' else 1, device=dev, dtype=torch.float32)
-        cap = min(chunk, max(len(g) for g in groups.values()) * B)
-        ws = bb.eng.take_ws(cap, False, dev)
-        for tokens, cis in groups.items():
-            mlp = override if override != MLP_AUTO else (MLP_ONE_LAUNCH if chunk * tokens >= MLP_FUSED_MIN_ROWS else MLP_TWO_LAUNCH)
-            c_map = torch.tensor([combos[c][0] for c in cis], device=dev)
-            c_del = torch.tensor([combos[c][1] for c in cis], device=dev)
-            c_k = torch.tensor([combos[c][2] for c in cis], device=dev)
-            c_row = torch.tensor(cis, device=dev)
-            total = len(cis) * B
-            for j0 in range(0, total, chunk):
-                j = torch.arange(j0, min(total, j0 + chunk), device=dev)
-                ci, b = j // B, j % B                                  # sequences combo-major, images inside
+        if ragged and perturbation == 'drop':
+            from . import ragged as rg
+            max_rows = chunk * 197
+            mlp = override if override != MLP_AUTO else (MLP_ONE_LAUNCH if max_rows >= MLP_FUSED_MIN_ROWS else MLP_TWO_LAUNCH)
+            lengths = np.repeat(np.array([tokens_of(c) for c in combos], dtype=np.int64), B)      # sequences combo-major, images inside
+            calls, _ = rg.ragged_layout(lengths, max_rows)
+            c_map = torch.tensor([c[0] for c in combos], device=dev)
+            c_del = torch.tensor([c[1] for c in combos], device=dev)
+            c_k = torch.tensor([c[2] for c in combos], device=dev)
+            ws = rg.take_ws(bb.eng, max_rows, dev)
+            for seq, off in calls:
+                j = torch.from_numpy(seq).to(dev)
+                ci, b = j // B, j % B
                 pert = perturbed_mask(ranks[c_map[ci], b], c_del[ci], c_k[ci])
-                src = source_rows(pert, perturbation, tokens)
-                feats = bb.forward_tokens(img_t, base_t, base_shared, b.int(), src, ws, mlp)
+                full = source_rows(pert, 'drop', 197)                      # a sequence's rows are the first `length` of its 197
+                off_d, seq_of_row, pos = rg.packed_rows(off, dev)
+                feats = bb.forward_ragged(img_t, base_t, 0, b.int(), full[seq_of_row, pos].contiguous(), off_d, off, ws, mlp)
                 outs = _head_outputs(model, feats)
                 v = outs[0] if target == 'class' else _target_value(target, outs, None).unsqueeze(1)
-                raw[c_row[ci], b] = v.float()
-        bb.eng.give_ws(cap, False, ws)
+                raw[ci, b] = v.float()
+            bb.eng.give_ws(max_rows, 'ragged', ws)
+        else:
+            cap = min(chunk, max(len(g) for g in groups.values()) * B)
+            ws = bb.eng.take_ws(cap, False, dev)
+            for tokens, cis in groups.items():
+                mlp = override if override != MLP_AUTO else (MLP_ONE_LAUNCH if chunk * tokens >= MLP_FUSED_MIN_ROWS else MLP_TWO_LAUNCH)
+                c_map = torch.tensor([combos[c][0] for c in cis], device=dev)
+                c_del = torch.tensor([combos[c][1] for c in cis], device=dev)
+                c_k = torch.tensor([combos[c][2] for c in cis], device=dev)
+                c_row = torch.tensor(cis, device=dev)
+                total = len(cis) * B
+                for j0 in range(0, total, chunk):
+                    j = torch.arange(j0, min(total, j0 + chunk), device=dev)
+                    ci, b = j // B, j % B                                  # sequences combo-major, images inside
+                    pert = perturbed_mask(ranks[c_map[ci], b], c_del[ci], c_k[ci])
+                    src = source_rows(pert, perturbation, tokens)
+                    feats = bb.forward_tokens(img_t, base_t, base_shared, b.int(), src, ws, mlp)
+                    outs = _head_outputs(model, feats)
+                    v = outs[0] if target == 'class' else _target_value(target, outs, None).unsqueeze(1)
+                    raw[c_row[ci], b] = v.float()
+            bb.eng.give_ws(cap, False, ws)
         if target == 'class':
             cls = targets.long() if targets is not None else raw[0].argmax(dim=1)
             vals = torch.softmax(raw, dim=2).gather(2, cls.view(1, B, 1).expand(len(combos), B, 1)).squeeze(2)

@@ -476,7 +476,7 @@ class KernelShap:
 
 # ---- the model call ------------------------------------------------------------------------------------------------------------------
 
-def _check(model, x, target, class_idx, num_samples, players, perturbation, baseline, seed, chunk, upsample, return_values):
+def _check(model, x, target, class_idx, num_samples, players, perturbation, baseline, seed, chunk, upsample, return_values, ragged=False):
     from .gradcam import _target_names
     from .input_grad import _check_args
     from .perturbation import PERTURBATIONS
@@ -494,7 +494,7 @@ def _check(model, x, target, class_idx, num_samples, players, perturbation, base
         ks = KernelShap(pmap, num_samples, seed)
     except RovitHipError as e:
         raise RovitHipError(f'{what}: {e}') from None
-    for name, flag in (('upsample', upsample), ('return_values', return_values)):
+    for name, flag in (('upsample', upsample), ('return_values', return_values), ('ragged', ragged)):
         if not isinstance(flag, bool):
             raise RovitHipError(f'{what}: {name} must be a bool, got {flag!r}')
     stage = getattr(model, 'curriculum_stage', None)
@@ -509,7 +509,7 @@ def _check(model, x, target, class_idx, num_samples, players, perturbation, base
 
 
 def patch_shap(model, x: torch.Tensor, target='class', class_idx=None, num_samples: int = 2048, players=14, perturbation: str = 'drop',
-               baseline=None, seed: int = 0, chunk: int = 256, upsample: bool = True, return_values: bool = False):
+               baseline=None, seed: int = 0, chunk: int = 256, upsample: bool = True, return_values: bool = False, ragged: bool = False):
     """KernelSHAP values of the players of every image for one RoViTKAN output (or several: a list / tuple of targets is explained from
     the same forwards and returns a dict name -> result).
 
@@ -530,13 +530,17 @@ def patch_shap(model, x: torch.Tensor, target='class', class_idx=None, num_sampl
 
     Eval semantics, as input_gradients: the bf16 engine whatever ``precision`` says, no dropout, no ``.grad`` written, flags untouched.
     Sequences of equal length are packed into backbone calls of ``chunk``; the MLP path is the engine's override or is chosen from
-    ``chunk`` x tokens, never from a call's size, so an image's values do not depend on the others of the batch.  Every bad argument is
-    refused (RovitHipError) before anything is launched."""
+    ``chunk`` x tokens, never from a call's size, so an image's values do not depend on the others of the batch.  ``ragged=True`` with
+    ``'drop'``: the sequences of ALL lengths are packed, longest first, into calls of ``chunk`` x 197 rows (rovit_hip.ragged,
+    rovit_vit_forward_ragged) -- sampled coalitions of 196 players come in about 197 lengths, and this makes a handful of backbone calls
+    of them; the MLP path is then the engine's override or chosen from ``chunk`` x 197 alone, so a short sequence may take the other
+    path than with ``ragged=False`` (the two agree to bf16 rounding, not bit for bit: the default stays False).  With ``'replace'`` the
+    flag changes nothing.  Every bad argument is refused (RovitHipError) before anything is launched."""
     from .functions import VitEngine
     from .input_grad import _Backbone, _head_outputs, _target_value
     from .perturbation import source_rows
     names, several, targets, ks = _check(model, x, target, class_idx, num_samples, players, perturbation, baseline, seed, chunk, upsample,
-                                         return_values)
+                                         return_values, ragged)
     dev = x.device
     B, M, P = x.shape[0], ks.M, ks.P
     with torch.no_grad():
@@ -570,23 +574,49 @@ def patch_shap(model, x: torch.Tensor, target='class', class_idx=None, num_sampl
         others = [n for n in names if n != 'class']
         raw_cls = torch.empty(M + 2, B, C_, device=dev, dtype=torch.float32) if 'class' in names else None
         raw_oth = torch.empty(M + 2, B, len(others), device=dev, dtype=torch.float32) if others else None
-        cap = min(chunk, max(sum(len(r) for r, _ in g) for g in groups.values()) * B)
-        ws = bb.eng.take_ws(cap, False, dev)
-        for tokens, parts in groups.items():
-            mlp = override if override != MLP_AUTO else (MLP_ONE_LAUNCH if chunk * tokens >= MLP_FUSED_MIN_ROWS else MLP_TWO_LAUNCH)
-            rows = torch.cat([r for r, _ in parts])
-            src_g = torch.cat([s for _, s in parts]) if len(parts) > 1 else parts[0][1]
-            total = rows.shape[0] * B
-            for j0 in range(0, total, chunk):
-                j = torch.arange(j0, min(total, j0 + chunk), device=dev)
-                ci, b = j // B, j % B                                  # sequences coalition-major, images inside
-                feats = bb.forward_tokens(img_t, base_t, base_shared, b.int(), src_g[ci].contiguous(), ws, mlp)
+        if ragged and perturbation == 'drop':
+            from . import ragged as rg
+            max_rows = chunk * 197
+            mlp = override if override != MLP_AUTO else (MLP_ONE_LAUNCH if max_rows >= MLP_FUSED_MIN_ROWS else MLP_TWO_LAUNCH)
+            # every coalition's rows in one flat buffer: the groups in ascending length (_drop_layout's offsets), the full image, nothing
+            kept = ks.kept_patches()
+            woff, words, _ = _drop_layout(kept)
+            flat = torch.cat([s_.reshape(-1) for _, _, s_ in co['src_drop']]
+                             + [source_rows(ends[:1], 'drop', 197).reshape(-1), source_rows(ends[1:], 'drop', 1).reshape(-1)])
+            woff_d = torch.from_numpy(np.concatenate([woff, [words, words + 197]])).to(dev)
+            lengths = np.repeat(np.concatenate([kept + 1, [197, 1]]), B)                    # sequences coalition-major, images inside
+            calls, _ = rg.ragged_layout(lengths, max_rows)
+            ws = rg.take_ws(bb.eng, max_rows, dev)
+            for seq, off in calls:
+                j = torch.from_numpy(seq).to(dev)
+                ci, b = j // B, j % B
+                off_d, seq_of_row, pos = rg.packed_rows(off, dev)
+                src = flat[woff_d[ci][seq_of_row] + pos].contiguous()
+                feats = bb.forward_ragged(img_t, base_t, 0, b.int(), src, off_d, off, ws, mlp)
                 outs = _head_outputs(model, feats)
                 if raw_cls is not None:
-                    raw_cls[rows[ci], b] = outs[0].float()
+                    raw_cls[ci, b] = outs[0].float()
                 for k, n in enumerate(others):
-                    raw_oth[rows[ci], b, k] = _target_value(n, outs, None).float()
-        bb.eng.give_ws(cap, False, ws)
+                    raw_oth[ci, b, k] = _target_value(n, outs, None).float()
+            bb.eng.give_ws(max_rows, 'ragged', ws)
+        else:
+            cap = min(chunk, max(sum(len(r) for r, _ in g) for g in groups.values()) * B)
+            ws = bb.eng.take_ws(cap, False, dev)
+            for tokens, parts in groups.items():
+                mlp = override if override != MLP_AUTO else (MLP_ONE_LAUNCH if chunk * tokens >= MLP_FUSED_MIN_ROWS else MLP_TWO_LAUNCH)
+                rows = torch.cat([r for r, _ in parts])
+                src_g = torch.cat([s for _, s in parts]) if len(parts) > 1 else parts[0][1]
+                total = rows.shape[0] * B
+                for j0 in range(0, total, chunk):
+                    j = torch.arange(j0, min(total, j0 + chunk), device=dev)
+                    ci, b = j // B, j % B                                  # sequences coalition-major, images inside
+                    feats = bb.forward_tokens(img_t, base_t, base_shared, b.int(), src_g[ci].contiguous(), ws, mlp)
+                    outs = _head_outputs(model, feats)
+                    if raw_cls is not None:
+                        raw_cls[rows[ci], b] = outs[0].float()
+                    for k, n in enumerate(others):
+                        raw_oth[rows[ci], b, k] = _target_value(n, outs, None).float()
+            bb.eng.give_ws(cap, False, ws)
         cols = []
         cls = None
         for n in names:
