@@ -1359,6 +1359,85 @@ size_t rovit_laplace_workspace_bytes(int n, int embed, int hid, int num_weights)
 int rovit_laplace_gram(const rovit_laplace_fit* p, rovit_stream_t stream);
 int rovit_laplace_predict(const rovit_laplace_query* p, rovit_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Training-data influence through the last layer (influence.hip): which recorded rows made this output, which argue against it, and
+ * which recorded labels are suspect (Koh & Liang, ICML 2017; Pruthi et al., NeurIPS 2020; Barshan et al., AISTATS 2020).  Notation of
+ * the Laplace section: a (padded to P = hid + 32), the whitening table W = R^-1 of H + tau I = R R^T taken as given, parameters
+ * class-major (index c P + a), N = C P.  With the last-layer gradient g[c P + a] = r_c a_a of a row:
+ *   whitened gradient u = W g (N; the padding's entries exactly 0)      score s(t, j) = u_t . u_j = g_t^T (H + tau I)^-1 g_j
+ *   self-influence |u_j|^2                                              relative score s(t, j) / |u_j|
+ * Sign and scale: to first order, removing recorded row j changes the query's target by + s(t, j) (H is a sum over rows, not a mean).
+ * Residual r, fp64 rounded to fp32 once:
+ *   head ROVIT_INFLUENCE_CLS, target _LOSS    r = softmax(l) - e_y, y = labels[i], or the first argmax of l with labels NULL
+ *   head ROVIT_INFLUENCE_CLS, target _OUTPUT  r = e_c, c = labels[i] or the first argmax
+ *   head ROVIT_INFLUENCE_MU (C = 1), _LOSS    r = (mu - severity) exp(-log_var)          _OUTPUT  r = 1
+ *
+ * rovit_influence_embed, one launch: a workgroup owns ROVIT_LAPLACE_TILE rows, forms r in the prologue, the hidden rows in LDS as
+ * rovit_laplace_predict does, streams W tile by tile (lower-triangular: nothing right of the diagonal tile is read) and stores per output
+ * tile of class block cb  u = sum_{c <= cb} r_c z_c, z_c = W[:, block c] a on the exact-fp32 matrix instruction, one fma chain in
+ * ascending c.  Outputs, all at the pointers given (the host offsets them to the batch's first row):
+ *   rows (n, N)   residual (n, C) (NaN for a row whose inputs are bad)   norm2 (n) = |u|^2, accumulated in fp64 and rounded once
+ *   valid (n) int: 0 for a row with a non-finite feature, logit, mu, log_var or severity, a residual that is not finite in fp32 or a
+ *   non-finite entry of u (BAD_ROWS), a label outside [0, C) (BAD_LABELS; a row that is both counts as BAD_ROWS), or u = 0 throughout;
+ *   such a row is stored as zeros with norm2 = 0
+ *   counts: int64 [ROVIT_INFLUENCE_N] [_N_VALID] [_BAD_ROWS] [_BAD_LABELS], ADDED to with integer atomics (the host zeroes them)
+ * Limits as rovit_laplace_predict; features, fc1_weight, whitening and rows 16-byte aligned.
+ *
+ * rovit_influence_search: queries (B, dim) against rows (n, dim) with their norm2 and valid columns.  A row is a candidate when it is
+ * valid, is not exclude[b], has norm2 > 0 under relative, and its score is finite.  Score: q . r on the exact-fp32 matrix instruction, one
+ * accumulator chain per (query, row) over the dim in ascending slabs of 64; relative divides by sqrtf(norm2[j]) in fp32; -0 becomes +0.
+ *   pro_scores / pro_indices (B, k): by (score descending, index ascending)      opp_scores / opp_indices: (score ascending, index ascending)
+ *   the two lists are independent (they overlap when fewer than 2 k candidates exist); empty slots hold -1 / NaN; a query whose
+ *   query_valid is 0 has every slot empty.  With ref_labels / ref_severity: pro_labels, opp_labels (-1), pro_severities, opp_severities (NaN).
+ * Only integer compares on the key (orderable score bits << 32) | index decide membership.  No (B, n) matrix exists: a work item is (64
+ * queries, a split of the rows); per-lane ascending key lists for both ends, the splits' lists in the workspace, a merge kernel ranks them.
+ * No floating-point atomic; every output is bit-identical from run to run, for every max_workgroups and for every max_splits (> 0 caps
+ * the grid / the number of reference splits; 0: the defaults).
+ * workspace: rovit_influence_workspace_bytes(batch, n, dim, k) bytes, 16-byte aligned (0 for sizes outside the limits).
+ * Limits: dim a multiple of 32 in 32..ROVIT_INFLUENCE_MAX_DIM, 1 <= k <= ROVIT_INFLUENCE_MAX_K, 1 <= n <= ROVIT_KAN_STATS_MAX_ROWS,
+ * batch >= 1; queries, rows and the workspace 16-byte aligned.  A bad descriptor is refused before any launch, by both.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define ROVIT_INFLUENCE_MAX_K 32
+#define ROVIT_INFLUENCE_MAX_DIM 2304           /* 8 classes x (256 + 32) */
+enum { ROVIT_INFLUENCE_CLS = 0, ROVIT_INFLUENCE_MU = 1 };
+enum { ROVIT_INFLUENCE_LOSS = 0, ROVIT_INFLUENCE_OUTPUT = 1 };
+enum { ROVIT_INFLUENCE_N = 0, ROVIT_INFLUENCE_N_VALID = 1, ROVIT_INFLUENCE_BAD_ROWS = 2, ROVIT_INFLUENCE_BAD_LABELS = 3,
+       ROVIT_INFLUENCE_COUNT_WORDS = 4 };
+typedef struct rovit_influence_rows {
+  int n, embed, hid, num_classes, head, target, max_workgroups, reserved;
+  const float* features;             /* (n, embed) */
+  const float* fc1_weight;           /* (hid, embed) */
+  const float* fc1_bias;             /* (hid) */
+  const float* whitening;            /* (C P, C P), P = hid + 32, lower-triangular */
+  const float* cls_logits;           /* (n, num_classes); head CLS */
+  const int* labels;                 /* (n) or NULL; head CLS */
+  const float* mu; const float* log_var; const float* severity;   /* (n) each; head MU with target LOSS */
+  float* rows;                       /* (n, C P) */
+  float* residual;                   /* (n, num_classes) */
+  float* norm2;                      /* (n) */
+  int* valid;                        /* (n) */
+  long long* counts;                 /* ROVIT_INFLUENCE_COUNT_WORDS, added to */
+} rovit_influence_rows;
+typedef struct rovit_influence_query {
+  int batch, n, dim, k, relative, max_workgroups, max_splits, reserved;
+  const float* queries;              /* (batch, dim) */
+  const int* query_valid;            /* (batch) or NULL: every query is good */
+  const float* rows;                 /* (n, dim) */
+  const float* norm2;                /* (n) */
+  const int* valid;                  /* (n) */
+  const int* exclude;                /* (batch) or NULL */
+  const int* ref_labels;             /* (n) or NULL */
+  const float* ref_severity;         /* (n) or NULL */
+  void* workspace;
+  size_t workspace_bytes;
+  float* pro_scores; int* pro_indices; float* opp_scores; int* opp_indices;   /* (batch, k) each */
+  int* pro_labels; int* opp_labels;                  /* (batch, k); with ref_labels */
+  float* pro_severities; float* opp_severities;      /* (batch, k); with ref_severity */
+} rovit_influence_query;
+int rovit_influence_embed(const rovit_influence_rows* p, rovit_stream_t stream);
+size_t rovit_influence_workspace_bytes(int batch, int n, int dim, int k);
+int rovit_influence_search(const rovit_influence_query* p, rovit_stream_t stream);
+
 /* ---- KernelSHAP over groups of patches (csrc/shap.hip; rovit_hip/shap.py holds the host plan and the numpy fp64 reference) ----------
  * P players (2 <= P <= ROVIT_SHAP_PATCHES), M samples (even, 2 <= M <= ROVIT_SHAP_MAX_SAMPLES); sample 2k + 1 is the complement of
  * sample 2k.  A coalition is ROVIT_SHAP_WORDS 32-bit words: player i is bit i % 32 of word i / 32, the bits from P on are zero.

@@ -24,21 +24,21 @@
 //                      smallest unpacked; then the vote in fp64 in slot order by one lane.
 // Work items are walked with a stride of the grid; no floating-point atomic; no result depends on which workgroup computes it.
 #include "common.h"
+#include "topk_device.h"
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 namespace {
 
-typedef unsigned long long u64;
+using namespace topk;                            // u64, EMPTY, keys_below, list_insert, store_unit: shared with influence.hip
 
-constexpr int NT = 256;                          // threads per workgroup
+constexpr int NT = 256;                        // threads per workgroup
 constexpr int QT = ROVIT_KNN_QUERY_TILE;         // query rows of a work item
 constexpr int RT = 64;                           // reference rows of an LDS tile
 constexpr int MAXK = ROVIT_KNN_MAX_K;
 constexpr int MAX_SPLITS = 64;
 constexpr int TARGET_ITEMS = 512;                // two work items per CU: the splits are chosen to reach it
 constexpr int MAX_T = 8;                         // embed / 32
-constexpr u64 EMPTY = ~0ull;                     // above every real key: its distance bits would be a NaN's
 static_assert(QT == 64 && RT == 64, "2 x 2 sub-tiles of 32 per workgroup, one per wave");
 
 inline int bucket_of(int k) { return k <= 8 ? 8 : (k <= 16 ? 16 : 32); }
@@ -140,34 +140,6 @@ struct SearchArgs {
 inline size_t search_lds_bytes(int E, int kb) {
   const size_t stage = ((size_t)(QT + RT) * (E + 4) + 2 * RT) * 4, merge = (size_t)QT * 4 * kb * 8;
   return stage > merge ? stage : merge;
-}
-
-// the number of keys below c in an ascending list of KB keys (KB a power of two)
-__device__ __forceinline__ int keys_below(const u64* list, int KB, u64 c) {
-  int lo = 0;
-  for (int s = KB >> 1; s > 0; s >>= 1)
-    if (list[lo + s - 1] < c) lo += s;
-  return lo + (list[lo] < c ? 1 : 0);
-}
-
-template <int KB>
-__device__ __forceinline__ void list_insert(u64 (&lst)[KB], u64 key) {
-  if (key < lst[KB - 1]) {
-    lst[KB - 1] = key;
-#pragma unroll
-    for (int i = KB - 1; i > 0; --i) {
-      const u64 lo = lst[i - 1], hi = lst[i];
-      const bool swap = hi < lo;
-      lst[i - 1] = swap ? hi : lo;
-      lst[i] = swap ? lo : hi;
-    }
-  }
-}
-
-// one unit = 8 consecutive features of one row: two float4 in, two float4 out as (f0 f2 f4 f6 | f1 f3 f5 f7)
-__device__ __forceinline__ void store_unit(float* dst, const float4 u, const float4 v) {
-  *reinterpret_cast<float4*>(dst) = make_float4(u.x, u.z, v.x, v.z);
-  *reinterpret_cast<float4*>(dst + 4) = make_float4(u.y, u.w, v.y, v.w);
 }
 
 template <int KB>

@@ -24,7 +24,10 @@ store (``rovit_hip.corrupt``), one card per (corruption, severity) cell, the cor
 ``evaluate(laplace=la)`` records each row's mean logit variance and, from stage 3, the total standard deviation of ``mu`` as the extra
 columns ``laplace_logit_var`` and ``laplace_mu_std`` (two more scores of the selective card) and adds ``metrics['laplace']``: the prior
 precisions, and NLL, ECE, Brier score and accuracy before and after the probit adjustment; ``evaluate_ood(..., laplace=la)`` adds the
-``'laplace'`` card."""
+``'laplace'`` card.
+``fit_influence(train_loader)`` embeds the training rows' whitened last-layer gradients (``rovit_hip.influence.HeadInfluence``);
+``audit_labels(top)`` prints and saves the "Label audit" table: the training rows with the largest self-influence, the ones whose labels
+deserve a second look.  Neither changes what ``evaluate`` returns, prints or saves."""
 from pathlib import Path
 from typing import Dict
 
@@ -52,6 +55,7 @@ class Evaluator:
         self._knn_tally = None
         self.laplace = None
         self._laplace_acc = None
+        self.influence = None
 
     MC_COLUMNS = ('predictive_entropy_mc', 'mutual_information', 'epistemic_var', 'uncertainty_std')
 
@@ -78,6 +82,39 @@ class Evaluator:
         ``evaluate_ood(..., laplace=...)``."""
         self.laplace = self.model.fit_laplace(loader, prior_precision=prior_precision)
         return self.laplace
+
+    def fit_influence(self, train_loader):
+        """Embed the whitened last-layer gradients of the training rows (``RoViTKAN.fit_influence``): one forward pass that also fits the
+        Laplace approximation unless ``fit_laplace`` has been called, one embed launch per head and batch.  The ``HeadInfluence`` is
+        returned and kept on ``self.influence``; ``audit_labels`` reads it."""
+        self.influence = self.model.fit_influence(train_loader, laplace=self.laplace)
+        return self.influence
+
+    def audit_labels(self, top: int = 50, results_dir=None) -> Dict:
+        """The ``top`` training rows by self-influence (``HeadInfluence.label_audit``), the standard audit score for label noise: prints
+        a "Label audit" table and saves ``label_audit.txt`` / ``label_audit.json`` to ``results_dir`` (default: the config's).  Returns
+        ``{'counts', 'rows': [{'index', 'label', 'predicted', 'label_prob', 'self_influence'}, ...]}``."""
+        import json
+        if self.influence is None:
+            raise RovitHipError('Evaluator.audit_labels: fit_influence(train_loader) first')
+        audit = {k: v.cpu().tolist() for k, v in self.influence.label_audit(top).items()}
+        names = list(self.config.data.class_names)
+        name = lambda c: names[c] if 0 <= c < len(names) else str(c)
+        rows = [{'index': i, 'label': y, 'predicted': p, 'label_prob': q, 'self_influence': s}
+                for i, y, p, q, s in zip(audit['indices'], audit['labels'], audit['predicted'], audit['label_prob'], audit['scores']) if i >= 0]
+        result = {'counts': self.influence.counts(), 'rows': rows}
+        lines = [f"Label audit (top {len(rows)} of {result['counts']['n_valid']} valid training rows by self-influence):",
+                 f"{'Index':>8}  {'Given label':<20}{'Predicted':<20}{'P(label)':>10}{'Self-influence':>16}", '-' * 76]
+        lines += [f"{r['index']:>8}  {name(r['label']):<20}{name(r['predicted']):<20}{r['label_prob']:>10.4f}{r['self_influence']:>16.6g}" for r in rows]
+        print('\n'.join(lines + ['']))
+        if results_dir is None:
+            results_dir = getattr(getattr(self.config, 'paths', None), 'results_dir', None)
+        if results_dir is not None:
+            results_dir = Path(results_dir)
+            results_dir.mkdir(parents=True, exist_ok=True)
+            (results_dir / 'label_audit.txt').write_text('\n'.join(lines) + '\n', encoding='utf-8')
+            (results_dir / 'label_audit.json').write_text(json.dumps(result, indent=2) + '\n', encoding='utf-8')
+        return result
 
     def fit_index(self, loader, metric: str = 'cosine'):
         """Record the backbone features of another split, normally the training loader, with their class labels and severities in a

@@ -3,3 +3,4 @@ from .attention_maps import ViTAttentionRollout  # noqa: F401
 from .gradcam import GradCAMPlusPlus  # noqa: F401
 from .kan_viz import KANVisualizer  # noqa: F401
 from .shap import PatchSHAP  # noqa: F401
+from .influence import TrainingInfluence  # noqa: F401

@@ -336,6 +336,28 @@ class RoViTKAN(nn.Module):
             out['head_ordinal_severity'] = pred['ordinal_severity']
         return out
 
+    def fit_influence(self, train_loader, laplace=None, chunk: int = 256):
+        """Extension (not in the reference): a ``rovit_hip.influence.HeadInfluence`` over an iterable of batches ``(images, class_labels,
+        severity_labels, ...)``: the whitened last-layer gradients of every training row, embedded on the GPU in one pass.  Without a
+        fitted ``laplace`` (a ``HeadLaplace``) the same pass fits one."""
+        from rovit_hip import influence
+        return influence.fit_model_influence(self, train_loader, laplace, chunk)
+
+    def influential_examples(self, x: torch.Tensor, influence, k: int = 5, labels=None, relative: bool = True) -> Dict[str, torch.Tensor]:
+        """Extension (not in the reference): explanation by training example.  One forward, then ``influence.search(features, cls_logits,
+        labels, k=k, relative=relative)``: the ``k`` proponents and opponents of the loss of every image's label (without ``labels``: of
+        the prediction made) with their scores, indices and labels, and beside them the head's own ``class`` under ``head_class``."""
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                fwd = self(x)
+        finally:
+            self.train(was_training)
+        out = dict(influence.search(fwd['features'], fwd['cls_logits'], labels, k=k, relative=relative))
+        out['head_class'] = torch.argmax(fwd['cls_logits'], dim=1)
+        return out
+
     def count_parameters(self) -> Dict[str, int]:
         def n(m):
             return sum(p.numel() for p in m.parameters() if p.requires_grad)

@@ -163,6 +163,9 @@ SIGNATURES = {
     'rovit_laplace_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'rovit_laplace_gram': (_i, [_vp, _vp]),
     'rovit_laplace_predict': (_i, [_vp, _vp]),
+    'rovit_influence_embed': (_i, [_vp, _vp]),
+    'rovit_influence_workspace_bytes': (_sz, [_i, _i, _i, _i]),
+    'rovit_influence_search': (_i, [_vp, _vp]),
 }
 
 
@@ -477,6 +480,30 @@ class LaplaceQuery(C.Structure):
 def laplace_words(hid: int, K: int) -> int:
     """ROVIT_LAPLACE_WORDS(hid, K): matrix k sits at LAPLACE_HEADER + k (hid + 1)^2."""
     return LAPLACE_HEADER + K * (hid + 1) * (hid + 1)
+
+
+# rovit_influence_embed / rovit_influence_search: limits, heads, targets and the counts (the ROVIT_INFLUENCE_* names of include/rovit_hip.h)
+INFLUENCE_MAX_K, INFLUENCE_MAX_DIM = 32, 2304
+INFLUENCE_CLS, INFLUENCE_MU = 0, 1
+INFLUENCE_LOSS, INFLUENCE_OUTPUT = 0, 1
+INFLUENCE_N, INFLUENCE_N_VALID, INFLUENCE_BAD_ROWS, INFLUENCE_BAD_LABELS, INFLUENCE_COUNT_WORDS = 0, 1, 2, 3, 4
+
+
+class InfluenceRows(C.Structure):
+    """``rovit_influence_rows`` of include/rovit_hip.h, field for field."""
+    _fields_ = [('n', _i), ('embed', _i), ('hid', _i), ('num_classes', _i), ('head', _i), ('target', _i), ('max_workgroups', _i),
+                ('reserved', _i), ('features', _vp), ('fc1_weight', _vp), ('fc1_bias', _vp), ('whitening', _vp), ('cls_logits', _vp),
+                ('labels', _vp), ('mu', _vp), ('log_var', _vp), ('severity', _vp), ('rows', _vp), ('residual', _vp), ('norm2', _vp),
+                ('valid', _vp), ('counts', _vp)]
+
+
+class InfluenceQuery(C.Structure):
+    """``rovit_influence_query`` of include/rovit_hip.h, field for field."""
+    _fields_ = [('batch', _i), ('n', _i), ('dim', _i), ('k', _i), ('relative', _i), ('max_workgroups', _i), ('max_splits', _i),
+                ('reserved', _i), ('queries', _vp), ('query_valid', _vp), ('rows', _vp), ('norm2', _vp), ('valid', _vp), ('exclude', _vp),
+                ('ref_labels', _vp), ('ref_severity', _vp), ('workspace', _vp), ('workspace_bytes', _sz),
+                ('pro_scores', _vp), ('pro_indices', _vp), ('opp_scores', _vp), ('opp_indices', _vp), ('pro_labels', _vp),
+                ('opp_labels', _vp), ('pro_severities', _vp), ('opp_severities', _vp)]
 
 
 # rovit_shap_coalitions / rovit_shap_gram / rovit_shap_solve: the Philox stream word, the limits and the factor block's layout (the
