@@ -33,10 +33,30 @@ __device__ __forceinline__ float block_sum(float v, float* s_red) {
   return s_red[0] + s_red[1] + s_red[2] + s_red[3];
 }
 
+// log-softmax of one logit as (z - shift) - rest, with the row's (shift, rest) from softmax_shift().  One statement, used for log p_t of
+// both label columns and for every p_j.
+__device__ __forceinline__ float log_softmax(float z, float shift, float rest) { return (z - shift) - rest; }
+
+// (shift, rest) of a row whose largest logit is zmax and whose log(sum_j exp(z_j - zmax)) is lgse.
+//   |zmax| >= DIRECT_BELOW: (zmax, lgse), log p_j = (z_j - zmax) - lgse.  The common shift of the logits leaves with the first subtraction,
+//     which is exact to an ulp of the difference.  zmax + lgse would be rounded at the size of zmax, and z_j minus it would carry
+//     ulp(zmax) / 2 into every log-probability of the row: 3e-5 for logits around 1000, three times the gradient bound of the tests.
+//   |zmax| <  DIRECT_BELOW: (zmax + lgse, 0), log p_j = z_j - lse.  There |lse| < 4 + log(16) < 8, so the sum is rounded by at most
+//     2^-22 = 2.4e-7: no more than the subtraction z_j - zmax of the other form loses at a gap of 8, and a fortieth of the bound.  These
+//     are the floating-point operations this row has always had, and keeping them for such logits keeps a training run reproducible bit
+//     for bit across the change: the bf16 backward re-rounds even a one-ulp change of the loss gradients to bf16 noise (5e-4 rms of the
+//     parameter gradients after one step), and AdamW carries that on.
+constexpr float DIRECT_BELOW = 4.f;
+__device__ __forceinline__ void softmax_shift(float zmax, float lgse, float& shift, float& rest) {
+  const bool direct = fabsf(zmax) < DIRECT_BELOW;
+  shift = direct ? zmax + lgse : zmax;
+  rest = direct ? 0.f : lgse;
+}
+
 // Focal term of one row for one label (losses.py:15-38): val = alpha (1 - p_t)^gamma (-log p_t) and the factor `coef` of
-// d/dz_j = alpha [gamma p_t (1-p_t)^(gamma-1) log p_t - (1-p_t)^gamma] (delta_jt - p_j) / B
-__device__ __forceinline__ void focal_term(const LossArgs& a, const float* z, float lse, int t, float invB, float& val, float& coef) {
-  const float logpt = z[t] - lse;
+// d/dz_j = alpha [gamma p_t (1-p_t)^(gamma-1) log p_t - (1-p_t)^gamma] (delta_jt - p_j) / B.  log p_t is log_softmax(z[t], shift, rest).
+__device__ __forceinline__ void focal_term(const LossArgs& a, const float* z, float shift, float rest, int t, float invB, float& val, float& coef) {
+  const float logpt = log_softmax(z[t], shift, rest);
   const float pt = __expf(logpt);
   const float al = a.alpha ? a.alpha[t] : 1.f;
   const float om = 1.f - pt;
@@ -47,7 +67,7 @@ __device__ __forceinline__ void focal_term(const LossArgs& a, const float* z, fl
 }
 
 // One batch row: adds the row's four loss terms to the thread's accumulators and writes the row's gradients of the TOTAL loss.
-// MIXED: the focal term and its gradient are lam f(t_a) + (1 - lam) f(t_b) (CutMix / MixUp, trainer.py:104-111); softmax and lse are
+// MIXED: the focal term and its gradient are lam f(t_a) + (1 - lam) f(t_b) (CutMix / MixUp, trainer.py:104-111); the log-softmax is
 // computed once, and the three label-free terms once.  WANT_CORRECT: returns 1 when the row's first-maximum argmax of the logits (a NaN
 // counts as the maximum, as in torch.max) equals class label a (trainer.py:151-153), else 0.
 template <bool MIXED, bool WANT_CORRECT>
@@ -74,22 +94,23 @@ __device__ __forceinline__ int row(const LossArgs& a, const long long* cls_t_b, 
   for (int j = 0; j < a.C; ++j) { z[j] = a.cls[(size_t)b * a.C + j]; zmax = fmaxf(zmax, z[j]); }
   float se = 0.f;
   for (int j = 0; j < a.C; ++j) se += __expf(z[j] - zmax);
-  const float lse = zmax + __logf(se);
+  float shift, rest;
+  softmax_shift(zmax, __logf(se), shift, rest);
   float val, coef;
-  focal_term(a, z, lse, t, invB, val, coef);
+  focal_term(a, z, shift, rest, t, invB, val, coef);
   if (MIXED) {
     float val_b, coef_b;
-    focal_term(a, z, lse, tb, invB, val_b, coef_b);
+    focal_term(a, z, shift, rest, tb, invB, val_b, coef_b);
     const float oml = 1.f - lam;
     l_cls += lam * val + oml * val_b;
     for (int j = 0; j < a.C; ++j) {
-      const float pj = __expf(z[j] - lse);
+      const float pj = __expf(log_softmax(z[j], shift, rest));
       a.d_cls[(size_t)b * a.C + j] = lam * (coef * ((j == t ? 1.f : 0.f) - pj)) + oml * (coef_b * ((j == tb ? 1.f : 0.f) - pj));
     }
   } else {
     l_cls += val;
     for (int j = 0; j < a.C; ++j) {
-      const float pj = __expf(z[j] - lse);
+      const float pj = __expf(log_softmax(z[j], shift, rest));
       a.d_cls[(size_t)b * a.C + j] = coef * ((j == t ? 1.f : 0.f) - pj);
     }
   }
