@@ -370,6 +370,39 @@ int rovit_vit_forward_ragged(const float* img_tokens, const float* base_tokens, 
                              const int* seq_offsets_dev, const int* seq_offsets_host, const float* const* params, const void* prep,
                              void* workspace, float* features, int n_seq, int depth, int mlp_path, rovit_stream_t stream);
 
+/* ---- PatchDropout training (Liu et al., WACV 2023): forward and backward on a kept subset of the 196 patches (patch_dropout.hip) ----
+ * rovit_patch_dropout_draw: for each of `batch` samples a uniformly random subset of k (1..196) patches, one launch, no host read.
+ * Patch p of sample b gets the key word (p % 4) of Philox4x32-10(key = seed, counter = (b, ROVIT_PATCH_DROPOUT_STREAM + p / 4,
+ * step lo, step hi)); the patches are ranked by the integer pair (key, p) and those of rank < k are kept.  Outputs, int32:
+ *   keep (batch, k)     the kept patches in ascending order
+ *   src  (batch, 1 + k) the rows rovit_gather_token_rows reads: 0 (the class token), then 1 + keep
+ *   inv  (batch, 197)   a token's row in the short sequence (0 for the class token), -1 for a dropped patch
+ * Integer compares only, no atomics: the same (seed, step, b, k) gives the same bits on every run and grid. */
+#define ROVIT_PATCH_DROPOUT_STREAM 0x50447200u      /* "PDr\0": counter word 1, + patch / 4 (0..48) */
+int rovit_patch_dropout_draw(unsigned long long seed, unsigned long long step, int* keep, int* src, int* inv, int batch, int k,
+                             rovit_stream_t stream);
+/* The inverse of the token gather for gradients: dense bf16 (batch*197,192) row (b, t) = rows bf16 (batch*tokens,192) row
+ * (b, inv[b*197 + t]) when that is in [0, tokens), else zeros.  Every dense row is written exactly once with 16-byte stores; no
+ * memset, no atomics.  rows, dense: 16-byte aligned. */
+int rovit_scatter_token_rows(const void* rows, const int* inv, void* dense, int batch, int tokens, rovit_stream_t stream);
+/* The training forward on kept tokens.  All 197 rows of every image are embedded (rovit_vit_embed's two launches, position embedding
+ * included) into token_table, fp32 (batch,197,192); rows src[b * tokens + r] (r < tokens, as rovit_vit_forward_tokens reads them; row 0
+ * the class token) of image seq_img[b] are gathered; from block 0's LayerNorm on the launches are those of rovit_vit_forward with
+ * training = 1 at batch * tokens rows, and the activations the backward reads are kept.  tokens in [2, 197].  workspace:
+ * rovit_vit_workspace_bytes(batch, depth, 1) -- the plan of `tokens` rows is no larger.  prepare: 0 = prep is current, 1 = prepare the
+ * weight images inside the call (rovit_vit_forward_prepare), 2 = ... and write the constant tables.  With tokens = 197 and
+ * src[b * 197 + r] = r the features and saved activations are rovit_vit_forward's bits. */
+int rovit_vit_forward_train_tokens(const float* images, const int* seq_img, const int* src, int tokens, const float* const* params, void* prep,
+                                   void* workspace, float* token_table, float* features, int batch, int depth, int mlp_path, int prepare,
+                                   rovit_stream_t stream);
+/* The backward of rovit_vit_forward_train_tokens (same batch, depth, tokens, mlp_path and workspace), every block in one call: the
+ * launches of rovit_vit_backward at batch * tokens rows down to block 0's input gradient, rovit_scatter_token_rows through inv
+ * (batch,197) into dense_grad (bf16, batch*197*192 elements), then the patch-embedding, position and class-token gradients at 197
+ * tokens as in rovit_vit_backward: a dropped patch contributes exact zeros.  grads as there; every entry is overwritten. */
+int rovit_vit_backward_tokens(const float* images, const float* d_features, const int* inv, int tokens, const float* const* params,
+                              const void* prep, void* workspace, void* dense_grad, float* const* grads, int batch, int depth, int mlp_path,
+                              rovit_stream_t stream);
+
 /* ---- the individual backbone kernels (used by rovit_vit_* and exposed for unit tests / profiling) ---------- */
 /* C = A(M,K) W(N,K)^T + bias with a fused epilogue:
  *   BF16  out bf16 (M,N)                      GELU  out = gelu(c), out2 = gelu'(c)  (both bf16, ld = ldo)

@@ -48,6 +48,8 @@ void rovit_set_error(const char* fmt, ...) {
 // (rovit_corrupt_stats and rovit_corrupt_batch were added at 440 the same way: image corruptions of the uint8 store, corrupt.hip.)
 // (rovit_vit_ragged_workspace_bytes, rovit_vit_forward_ragged, rovit_attention_fwd_ragged and rovit_attention_cls_fwd_ragged were added
 // at 440 the same way: sequences of different lengths in one inference forward, attention.hip / perturb.hip / vit.hip.)
+// (rovit_patch_dropout_draw, rovit_scatter_token_rows, rovit_vit_forward_train_tokens and rovit_vit_backward_tokens were added at 440 the
+// same way: PatchDropout training on kept tokens, patch_dropout.hip / vit.hip.)
 extern "C" int rovit_version(void) { return 440; }
 extern "C" const char* rovit_last_error_string(void) { return g_err; }
 

@@ -31,3 +31,16 @@ __device__ __forceinline__ void rank_count_tile(const float* sX, float xi, unsig
     }
   }
 }
+
+// The same counting rank of a short list of 32-bit words held whole in LDS (patch_dropout.hip: 196 Philox words per sample), by the
+// integer pair (word, index): rank_i = #{j : w_j < w_i or (w_j == w_i and j < i)}.  Ties are broken by the index, so the ranks are a
+// permutation of 0..n-1 whatever the words are.  Integer compares only; every lane reads the same address (a broadcast).
+__device__ __forceinline__ unsigned rank_count_pairs_u32(const unsigned* sW, int n, unsigned wi, int i) {
+  unsigned rank = 0;
+#pragma unroll 4
+  for (int j = 0; j < n; ++j) {
+    const unsigned wj = sW[j];
+    rank += (wj < wi) | ((wj == wi) & (j < i));
+  }
+  return rank;
+}

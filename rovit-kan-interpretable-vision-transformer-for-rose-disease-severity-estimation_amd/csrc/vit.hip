@@ -317,7 +317,8 @@ struct RaggedSeqs {
 };
 
 // prepare: 0 = the weights in `prep` are current; 1 = prepare them from `params` first; 2 = ... and write the constant tables too.
-// tokens: the sequence length (197 but for rovit_vit_forward_tokens); rows: gather X from token tables instead of embedding `images`.
+// tokens: the sequence length (197 but for rovit_vit_forward_tokens / _train_tokens); rows: gather X from token tables instead of
+// embedding `images` (both given: embed `images` into rows->img first, then gather -- the training forward on kept tokens).
 // rg: the `batch` sequences have different lengths (rows required, inference only).  The rows of a half then come from the offsets
 // instead of batch * tokens -- every row-wise launch takes its row range as it takes a half-batch's -- and four things change: the gather,
 // the two attention kernels, and the last block's class-token rows, which the class-token attention writes compactly for the tail.
@@ -354,6 +355,8 @@ int vit_forward_impl(const float* images, const float* const* params, const void
     RUN(rovit_gather_token_rows_ragged(rows->img, rows->base, rows->n_img, rows->base_shared, rows->seq_img, rows->src, rg->dev, X, batch, M,
                                        stream));
   } else if (rows) {
+    // rovit_vit_forward_train_tokens: the table is this call's own -- all 197 rows of every image, position embedding included
+    if (images) RUN(embed_rows(images, params, pb, P, const_cast<float*>(rows->img), rows->n_img, stream));
     RUN(rovit_gather_token_rows(rows->img, rows->base, rows->n_img, rows->base_shared, rows->seq_img, rows->src, X, batch, tokens, stream));
   } else {
     RUN(embed_rows(images, params, pb, P, X, batch, stream));
@@ -589,6 +592,22 @@ extern "C" int rovit_vit_forward_ragged(const float* img_tokens, const float* ba
                           false, 1, &rows, &rg);
 }
 
+// The TRAINING forward on kept tokens (PatchDropout): all 197 rows of every image are embedded into token_table (fp32 (batch,197,192),
+// position embedding added there), rows src[b * tokens + r] of image seq_img[b] are gathered into X, and from block 0's LayerNorm on
+// the launches are rovit_vit_forward's training ones at batch * tokens rows.  The plan of `tokens` rows fits the dense training
+// workspace.  prepare: 0 the weight images are current, 1 prepare them inside the call, 2 ... and write the constant tables too.
+extern "C" int rovit_vit_forward_train_tokens(const float* images, const int* seq_img, const int* src, int tokens, const float* const* params,
+                                              void* prep, void* workspace, float* token_table, float* features, int batch, int depth,
+                                              int mlp_path, int prepare, rovit_stream_t stream) {
+  ROVIT_CHECK_ARG(images && seq_img && src && token_table, ROVIT_ERR_NULL, "vit_forward_train_tokens: null images / seq_img / src / token_table");
+  ROVIT_CHECK_ARG(tokens >= 2 && tokens <= T, ROVIT_ERR_SHAPE, "vit_forward_train_tokens: tokens must be in [2, %d], got %d", T, tokens);
+  ROVIT_CHECK_ARG(prepare >= 0 && prepare <= 2, ROVIT_ERR_SHAPE, "vit_forward_train_tokens: prepare must be 0, 1 or 2, got %d", prepare);
+  ROVIT_CHECK_ARG(rovit_aligned16(token_table), ROVIT_ERR_ALIGN, "vit_forward_train_tokens: token_table must be 16-byte aligned");
+  const TokenRows rows{token_table, token_table, batch, 0, seq_img, src};
+  return vit_forward_impl(images, params, prep, workspace, features, nullptr, nullptr, batch, depth, 1, mlp_path, stream, prepare, nullptr, 0,
+                          false, tokens, &rows);
+}
+
 // rovit_vit_prepare + rovit_vit_forward as ONE call (a training step prepares the weights after every optimizer step): the blocks'
 // weight images are written beside the patch embedding instead of in front of the forward.  write_tables != 0: also (re)write the
 // constant look-up tables of `prep` (needed once per buffer; rovit_vit_prepare always writes them).
@@ -709,9 +728,17 @@ struct Relevance {
   float* u;          // (B,197) fp32: row 0 of R_L once block 0 is done
   float* scratch;    // (B,3,197) fp32: the step kernel's per-head partials
 };
+// rovit_vit_backward_tokens: the forward ran on `tokens` < 197 gathered rows per image.  Everything down to block 0's input gradient
+// runs on batch * tokens rows; in front of the patch-embedding end those bf16 rows are scattered through inv (B,197: a token's row in
+// the short sequence, or -1) into the dense (B*197,192) buffer, dropped tokens as zeros, and that end runs unchanged at 197 tokens.
+struct TokenScatter {
+  const int* inv;
+  void* dense;
+};
 int vit_backward_impl(const float* images, const float* d_features, const float* const* params, const void* prep, void* workspace,
                       float* const* grads, int batch, int depth, int first_block, int last_block, int mlp_path, rovit_stream_t stream,
-                      bool defer_join, hipStream_t notify, const InputGrad* ig = nullptr, const Relevance* rel = nullptr) {
+                      bool defer_join, hipStream_t notify, const InputGrad* ig = nullptr, const Relevance* rel = nullptr, int tokens = T,
+                      const TokenScatter* scatter = nullptr) {
   RUN(check_common(params, prep, workspace, batch, depth, mlp_path));
   ROVIT_CHECK_ARG(grads || ig || rel, ROVIT_ERR_NULL, "vit_backward: null grads");
   ROVIT_CHECK_ARG(first_block < depth && last_block >= 0 && first_block >= last_block, ROVIT_ERR_SHAPE,
@@ -727,7 +754,7 @@ int vit_backward_impl(const float* images, const float* d_features, const float*
     ROVIT_CHECK_ARG(rovit_aligned16(d_images), ROVIT_ERR_ALIGN, "vit_backward_input: d_images must be 16-byte aligned");
   }
   const Prep P(depth);
-  const Plan L(batch, depth, 1);
+  const Plan L(batch, depth, 1, tokens);
   const char* pb = (const char*)prep;
   char* ws = (char*)workspace;
   const int M = (int)L.M;
@@ -859,13 +886,13 @@ int vit_backward_impl(const float* images, const float* d_features, const float*
       // each: 18 us apiece as separate launches, plus their reduce) run as ONE merged launch on the weight-gradient stream: for that the
       // norm2 backward writes the bf16 gradient to the mid-block buffer instead of updating xin in place (fc2's weight gradient reads
       // xin as it came in, proj's the updated rows).
-      const int Mr = batch, rs = T;
+      const int Mr = batch, rs = tokens;
       char* dp = ws + L.dpre[i & 1];
       char* dq = ws + L.dqkv[i & 1];
       char* xmc = ws + L.x1[i & 1];
       // final-norm backward -> fc2 dgrad x gelu' -> fc1 dgrad -> norm2 backward -> proj dgrad on the class-token rows: ONE launch (five before)
       RUN(rovit_cls_tail_bwd(d_features, (const float*)(ws + L.xhat_cls), (const float*)(ws + L.rstd_cls), params[P_NORM_W], q + P.wfc2, q + P.wfc1,
-                             q + P.wproj, s + L.dact, s + L.xhat2, (const float*)(s + L.rstd2), xin, dp, xmc, ws + L.dO, batch, T, stream));
+                             q + P.wproj, s + L.dact, s + L.xhat2, (const float*)(s + L.rstd2), xin, dp, xmc, ws + L.dO, batch, tokens, stream));
       // relevance: dO and lse2 of this block hold the class-token rows only (first = 1 reads nothing else)
       if (rel) {
         RUN(rovit_attention_relevance_step(s + L.qkv, (const float*)(s + L.lse), ws + L.dO, rel->u, rel->scratch, batch, 1, stream));
@@ -877,7 +904,7 @@ int vit_backward_impl(const float* images, const float* d_features, const float*
       // only the class token's row of dO carries gradient: a rank-one backward (attention.hip), which also zeroes the other queries' dQ rows.
       // Enqueued in front of the side stream's launches (which it neither feeds nor reads): see "Round 6" above.
       const bool a4_first = ss && a4_early;
-      if (a4_first) RUN(rovit_attention_cls_bwd(s + L.qkv, s + L.o, (const float*)(s + L.lse), ws + L.dO, dq, batch, T, H, D / H, 0.125f, stream));
+      if (a4_first) RUN(rovit_attention_cls_bwd(s + L.qkv, s + L.o, (const float*)(s + L.lse), ws + L.dO, dq, batch, tokens, H, D / H, 0.125f, stream));
       // the final norm's dgamma / dbeta: sample sums off the dgrad chain -> the weight-gradient stream
       if (wgrad) RUN(rovit_cls_norm_affine_grad(d_features, (const float*)(ws + L.xhat_cls), grads[P_NORM_W], grads[P_NORM_B], batch, sB));
       if (wgrad) {
@@ -895,12 +922,12 @@ int vit_backward_impl(const float* images, const float* d_features, const float*
             {(const float*)(ws + L.slab_proj), sc, D, D, nullptr, nullptr, nullptr, bg[B_PROJW], bg[B_PROJB], nullptr, nullptr, nullptr}};
         RUN(rovit_wgrad_reduce_batch(rd, 3, sB));
       }
-      if (!a4_first) RUN(rovit_attention_cls_bwd(s + L.qkv, s + L.o, (const float*)(s + L.lse), ws + L.dO, dq, batch, T, H, D / H, 0.125f, stream));
+      if (!a4_first) RUN(rovit_attention_cls_bwd(s + L.qkv, s + L.o, (const float*)(s + L.lse), ws + L.dO, dq, batch, tokens, H, D / H, 0.125f, stream));
       if (one_launch && cls_fuse && i > last_block) {
         a5_pending = i;                         // A5 rides in front of block depth - 2's MLP dgrad (rovit_block_bwd_fused_cls)
       } else {
         RUN(release_early(i));
-        RUN(rovit_gemm_ln_bwd_cls(dq, 3 * D, q + P.wqkvT, 3 * D, M, 3 * D, s + L.xhat1, (const float*)(s + L.rstd1), xmc, T, xout, stream));
+        RUN(rovit_gemm_ln_bwd_cls(dq, 3 * D, q + P.wqkvT, 3 * D, M, 3 * D, s + L.xhat1, (const float*)(s + L.rstd1), xmc, tokens, xout, stream));
       }
       // the (full-size) qkv weight gradient of this block goes the way of every other block's: as `pending`, into the next block's
       // merged launch on the weight-gradient stream (or the flush behind the loop) instead of 50 us of serial work here
@@ -928,7 +955,7 @@ int vit_backward_impl(const float* images, const float* d_features, const float*
     if (one_launch && a5_pending == i + 1) {      // [A5 of block i + 1] + [A1 + A2]: xin is written by this launch
       char* su = ws + L.blk0 + (size_t)(i + 1) * L.blk_stride;
       RUN(rovit_block_bwd_fused_cls(ws + L.dqkv[(i + 1) & 1], su + L.xhat1, (const float*)(su + L.rstd1), ws + L.x1[(i + 1) & 1],
-                                    i + 1 == depth - 1 ? T : 0, xin, q + P.wmlpb, s + L.dact, dp, s + L.xhat2, (const float*)(s + L.rstd2),
+                                    i + 1 == depth - 1 ? tokens : 0, xin, q + P.wmlpb, s + L.dact, dp, s + L.xhat2, (const float*)(s + L.rstd2),
                                     xmid, M, sA));
       a5_pending = -1;
     } else if (one_launch) {
@@ -953,7 +980,7 @@ int vit_backward_impl(const float* images, const float* d_features, const float*
       if (i == 0) break;
     }
     if (wait_b && !wait_early && hipStreamWaitEvent(sA, ev_bdone[i + 2], 0) != hipSuccess) EVFAIL("event wait");
-    RUN(rovit_attention_bwd(s + L.qkv, s + L.o, (const float*)(s + L.lse), ws + L.dO, dq, batch, T, H, D / H, 0.125f, sA));       // A4
+    RUN(rovit_attention_bwd(s + L.qkv, s + L.o, (const float*)(s + L.lse), ws + L.dO, dq, batch, tokens, H, D / H, 0.125f, sA));       // A4
     // qkv dgrad fused with the backward of norm1
     RUN(release_early(i));
     if (one_launch && i > last_block) {
@@ -976,10 +1003,16 @@ int vit_backward_impl(const float* images, const float* d_features, const float*
   }
   auto patch_grads = [&]() -> int {          // the patch embedding's and the position embedding's gradients (block range ending at 0)
     ROVIT_CHECK_ARG(images, ROVIT_ERR_NULL, "vit_backward: the range ending at block 0 needs the images of the forward call");
-    RUN(rovit_patch_embed_wgrad(x0v(-1), D, images, batch, T, D, L.s_pe, (float*)(ws + L.slab_pe), stream));
+    // kept tokens: every dense row is written once, a kept token's from its short-sequence row, a dropped token's as zeros
+    const char* dx0 = x0v(-1);
+    if (scatter) {
+      RUN(rovit_scatter_token_rows(dx0, scatter->inv, scatter->dense, batch, tokens, stream));
+      dx0 = (const char*)scatter->dense;
+    }
+    RUN(rovit_patch_embed_wgrad(dx0, D, images, batch, T, D, L.s_pe, (float*)(ws + L.slab_pe), stream));
     RUN(rovit_wgrad_reduce((const float*)(ws + L.slab_pe), L.s_pe, D, PD, nullptr, nullptr, nullptr, grads[P_PATCH_W], grads[P_PATCH_B],
                            nullptr, nullptr, nullptr, stream));
-    RUN(rovit_pos_grad(nullptr, x0v(-1), grads[P_POS], grads[P_CLS], batch, T, stream));
+    RUN(rovit_pos_grad(nullptr, dx0, grads[P_POS], grads[P_CLS], batch, T, stream));
     return ROVIT_OK;
   };
   auto pixel_grads = [&]() -> int {          // d_images: the patch embedding's data gradient, from the same bf16 rows (input_grad.hip)
@@ -1028,6 +1061,19 @@ extern "C" int rovit_vit_backward_notify(const float* images, const float* d_fea
                                          int last_block, int mlp_path, rovit_stream_t stream, rovit_stream_t notify_stream) {
   return vit_backward_impl(images, d_features, params, prep, workspace, grads, batch, depth, first_block, last_block, mlp_path, stream, true,
                            (hipStream_t)notify_stream);
+}
+
+// The backward of rovit_vit_forward_train_tokens, the whole depth in one call: vit_backward_impl with `tokens` in place of 197, then
+// the scatter through inv into dense_grad (bf16 (batch*197,192)) and the patch-embedding, position and class-token gradients at 197.
+extern "C" int rovit_vit_backward_tokens(const float* images, const float* d_features, const int* inv, int tokens, const float* const* params,
+                                         const void* prep, void* workspace, void* dense_grad, float* const* grads, int batch, int depth,
+                                         int mlp_path, rovit_stream_t stream) {
+  ROVIT_CHECK_ARG(images && inv && dense_grad && grads, ROVIT_ERR_NULL, "vit_backward_tokens: null images / inv / dense_grad / grads");
+  ROVIT_CHECK_ARG(tokens >= 2 && tokens <= T, ROVIT_ERR_SHAPE, "vit_backward_tokens: tokens must be in [2, %d], got %d", T, tokens);
+  ROVIT_CHECK_ARG(rovit_aligned16(dense_grad), ROVIT_ERR_ALIGN, "vit_backward_tokens: dense_grad must be 16-byte aligned");
+  const TokenScatter scatter{inv, dense_grad};
+  return vit_backward_impl(images, d_features, params, prep, workspace, grads, batch, depth, depth - 1, 0, mlp_path, stream, false, nullptr,
+                           nullptr, nullptr, tokens, &scatter);
 }
 
 // rovit_vit_backward plus the image gradient (d_images != NULL) and/or without the weight gradients (grads == NULL): include/rovit_hip.h

@@ -110,6 +110,13 @@ class DeiTTiny(nn.Module):
         # 'bf16' (default): bf16 MFMA operands, fp32 accumulation -- the training / fast path.  'fp32': inference-only
         # reference-precision mode (rovit_vit_forward_f32: every product and sum in fp32) for end-to-end parity at 1e-3.
         self.precision = 'bf16'
+        # PatchDropout (rovit_hip.patch_dropout; DeiTTinyBackbone.set_patch_dropout): in train() mode with patch_keep < 1 every forward
+        # keeps a new random subset of the patches, drawn from (seed, step).  Plain attributes, not buffers: the state_dict keeps the
+        # reference's key set; set patch_dropout_step to resume or to repeat a step.
+        self.patch_keep = 1.0
+        self.patch_dropout_seed = 0
+        self.patch_dropout_step = 0
+        self.last_patch_keep = None      # (B, k) int32 kept patches of the most recent token-path forward
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -163,6 +170,9 @@ class DeiTTiny(nn.Module):
         attn_hooked = [i for i, b in enumerate(self.blocks) if b.attn._forward_hooks]
         norm_fwd = [i for i, b in enumerate(self.blocks) if b.norm1._forward_hooks]
         norm_bwd = [i for i, b in enumerate(self.blocks) if b.norm1._backward_hooks]
+        if self.training and self.patch_keep < 1.0:
+            from rovit_hip import patch_dropout
+            return patch_dropout.forward_dropped(self, x, bool(attn_hooked or norm_fwd or norm_bwd))
         if not (attn_hooked or norm_fwd or norm_bwd):
             return VitFn.apply(x, self.engine, training, *self.ordered_parameters())
         return self._forward_with_taps(x, training, attn_hooked, norm_fwd, norm_bwd)
@@ -229,6 +239,31 @@ class DeiTTinyBackbone(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return self.model(x)
+
+    def set_patch_dropout(self, keep: float = 1.0, seed: int = 0):
+        """Extension (not in the reference): PatchDropout (Liu et al., WACV 2023).  In ``train()`` mode with ``keep`` < 1 every forward
+        keeps k = max(1, round(keep * 196)) random patches per image plus the class token, and forward and backward run on those token
+        rows (rovit_hip.patch_dropout); ``eval()`` mode and ``keep`` = 1.0 take the dense path.  The subset of a call is a function of
+        (``seed``, ``patch_dropout_step``, sample); the step counter restarts at 0 here, advances by one per dropped forward, and can
+        be read and set (``patch_dropout_step``) to resume or repeat a run.  ``last_patch_keep`` holds the most recent (B, k) subset."""
+        from rovit_hip import patch_dropout
+        self.model.patch_keep, self.model.patch_dropout_seed = patch_dropout.check_keep_seed(keep, seed)
+        self.model.patch_dropout_step = 0
+        return self
+
+    @property
+    def patch_dropout_step(self) -> int:
+        return self.model.patch_dropout_step
+
+    @patch_dropout_step.setter
+    def patch_dropout_step(self, step: int):
+        if isinstance(step, bool) or not isinstance(step, int) or not (0 <= step < 1 << 64):
+            raise ValueError(f'patch_dropout_step must be an integer in [0, 2^64), got {step!r}')
+        self.model.patch_dropout_step = step
+
+    @property
+    def last_patch_keep(self):
+        return self.model.last_patch_keep
 
     def freeze(self):
         for p in self.model.parameters():

@@ -202,6 +202,11 @@ class RoViTKAN(nn.Module):
         for d in self._head_dropouts():
             d.eval()
 
+    def set_patch_dropout(self, keep: float = 1.0, seed: int = 0):
+        """Extension (not in the reference): DeiTTinyBackbone.set_patch_dropout of the backbone (PatchDropout in train() mode)."""
+        self.backbone.set_patch_dropout(keep, seed)
+        return self
+
     def freeze_backbone(self):
         self.backbone.freeze()
 

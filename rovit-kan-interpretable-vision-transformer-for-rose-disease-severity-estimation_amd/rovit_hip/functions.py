@@ -461,6 +461,7 @@ class VitEngine:
         # forward and backward calls -- the forward's choice is saved with the graph, so a later change cannot split a step
         self.mlp_path: Optional[int] = None          # None: VitEngine.default_mlp_path
         self.last_ws = None              # (workspace, batch) of the most recent training-mode forward (read by rovit_hip.taps)
+        self.seq_img: Optional[torch.Tensor] = None  # arange int32: sequence b reads image b (cached by rovit_hip.patch_dropout)
 
     # -- prepared weights ---------------------------------------------------------------------
     def prepare(self, params: Sequence[torch.Tensor], defer: bool = False) -> int:

@@ -74,6 +74,10 @@ SIGNATURES = {
     'rovit_vit_forward_tokens': (_i, [_vp, _vp, _i, _i, _vp, _vp, _i] + [_vp] * 4 + [_i, _i, _i, _vp]),
     'rovit_vit_ragged_workspace_bytes': (_sz, [_i, _i]),
     'rovit_vit_forward_ragged': (_i, [_vp, _vp, _i, _i] + [_vp] * 8 + [_i, _i, _i, _vp]),
+    'rovit_patch_dropout_draw': (_i, [C.c_ulonglong, C.c_ulonglong, _vp, _vp, _vp, _i, _i, _vp]),
+    'rovit_scatter_token_rows': (_i, [_vp, _vp, _vp, _i, _i, _vp]),
+    'rovit_vit_forward_train_tokens': (_i, [_vp, _vp, _vp, _i] + [_vp] * 5 + [_i] * 4 + [_vp]),
+    'rovit_vit_backward_tokens': (_i, [_vp, _vp, _vp, _i] + [_vp] * 5 + [_i] * 3 + [_vp]),
     'rovit_gemm_nt': (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _vp]),
     'rovit_gemm_resid_ln': (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp]),
     'rovit_mlp_stream_bytes': (_sz, []),

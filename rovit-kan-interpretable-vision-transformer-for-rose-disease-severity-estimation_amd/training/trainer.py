@@ -19,6 +19,9 @@ gradient_clip, freeze_backbone_epochs, curriculum), ``config.train`` (epochs, ea
 * With an optimizer that keeps a weight average (``RoViTAdamW(ema_decay=...)``; the reference has none) ``val_epoch`` validates the
   averaged weights (``optimizer.swap_ema()``), so early stopping and ``best_model.pth`` follow them; the checkpoint gains
   ``'ema_state_dict'`` while ``'model_state_dict'`` stays the raw weights training resumes from.  Without one nothing changes.
+* ``config.train.patch_keep`` < 1 (read with ``getattr``; the reference's ``Config`` has no such field) switches PatchDropout on
+  (``model.set_patch_dropout``; ``config.train.patch_seed``, default 0): training steps run on the kept tokens, validation on all.  The
+  checkpoint then gains ``'patch_dropout_step'``.  Without the field nothing changes.
 """
 from pathlib import Path
 from typing import Dict, List, Optional
@@ -40,6 +43,10 @@ class Trainer:
         self.config, self.device, self.logger = config, device, logger
         self.scaler = None                                  # kept as an attribute; never a GradScaler (module docstring)
         self.mix_loss = bool(config.flags.mixed_precision)
+        # PatchDropout (not in the reference, whose Config has no such field): config.train.patch_keep < 1 trains on kept tokens
+        self.patch_keep = float(getattr(config.train, 'patch_keep', 1.0))
+        if self.patch_keep != 1.0:
+            self.model.set_patch_dropout(keep=self.patch_keep, seed=int(getattr(config.train, 'patch_seed', 0)))
         self.last_train_record: Optional[TrainRecord] = None
         self.best_val_loss = float('inf')
         self.patience_counter = 0
@@ -123,6 +130,8 @@ class Trainer:
               'config': self.config}
         if self._has_ema():
             ck['ema_state_dict'] = self.optimizer.ema_state_dict()
+        if self.patch_keep != 1.0:
+            ck['patch_dropout_step'] = self.model.backbone.patch_dropout_step
         torch.save(ck, path)
 
     def load_checkpoint(self, path) -> None:
@@ -133,6 +142,8 @@ class Trainer:
         self.optimizer.load_state_dict(checkpoint['optimizer_state_dict'])
         if self._has_ema() and 'ema_state_dict' in checkpoint:
             self.optimizer.load_ema_state_dict(checkpoint['ema_state_dict'])
+        if self.patch_keep != 1.0 and 'patch_dropout_step' in checkpoint:
+            self.model.backbone.patch_dropout_step = checkpoint['patch_dropout_step']
         self.scheduler.load_state_dict(checkpoint['scheduler_state_dict'])
         self.best_val_loss = checkpoint['best_val_loss']
         print(f"Checkpoint loaded from {path}\nEpoch: {checkpoint['epoch']}\nVal Loss: {checkpoint['best_val_loss']:.4f}")
