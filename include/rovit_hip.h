@@ -1171,6 +1171,70 @@ size_t rovit_ood_metrics_workspace_bytes(int n_in, int n_out);
 int rovit_ood_metrics(const rovit_ood* p, rovit_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Device radix sort of fp32 columns and the ranks that follow from it (sort_rank.hip; device functions in sort_device.h).  The
+ * counting rank of the three score cards above is O(n^2); this is the O(n) path behind the same words, and the library's only sort.
+ * Key of a value v: the order-preserving uint32 of v + 0.0f (sign bit flipped for v >= 0, all bits for v < 0), so -0 and +0 share a key;
+ *   every NaN, of either sign and any payload, has the key 0xFFFFFFFF, which no number has: NaNs sort behind +inf.
+ * Sorted element: the pair (key, row).  Its 64-bit form (key << 32) | row has no duplicates, so the ascending order is unique: any
+ *   correct algorithm, grid and run gives the same bytes.  rovit_sort_f32 writes, per column c of n[c] rows,
+ *   keys_sorted[c][n[c]] uint32 ascending and perm[c][n[c]] uint32, the row in each sorted slot: the STABLE argsort, NaN rows last.
+ * Algorithm: LSD radix sort, four passes of 8 bits, each three launches on the caller's stream: a digit histogram per tile of
+ *   ROVIT_SORT_TILE rows (LDS counters; the column's digit totals by integer atomics: only the sum matters), an exclusive scan of the
+ *   (digit, tile) table, and a scatter that is stable inside the tile: a row's place among the tile's rows of its digit comes from wave
+ *   ballots and a fixed walk over the tile's 32 (wave, round) groups, never from an atomic.  No kernel waits for another workgroup;
+ *   every loop is bounded by n or a constant; every destination is checked against n before the store; integer compares only.
+ *   Up to ROVIT_SORT_MAX_COLUMNS columns of individual lengths share the twelve launches.
+ * Ranks: for row i with key k in slot s, less = lower_bound(k), eq = upper_bound(k) - less, before = s - less over the sorted keys;
+ *   a NaN row gets less = eq = before = 0 and is counted for no other row.  These are the values the counting kernels produce
+ *   (less = #{x_j < x_i}, eq = #{x_j == x_i}, before = #{j < i : x_j == x_i}, a NaN comparing false).  rovit_rank_f32 returns them with
+ *   perm per column.  method: ROVIT_RANK_COUNT counts on rank_count.h's tile (perm[less + before] = row; NaN rows behind the numbers in
+ *   row order, so perm equals the sort's), ROVIT_RANK_SORT sorts, ROVIT_RANK_AUTO sorts columns of at least ROVIT_RANK_SORT_ROWS rows
+ *   (decided by the longest column of the call).  Both methods give the same words for every input.
+ * rovit_eval_finalize_ex / rovit_eval_selective_ex / rovit_ood_metrics_ex: the three score cards with the rank step by `method`; every
+ *   other launch and every result word is that of the plain entry point, which is the _ex call with ROVIT_RANK_COUNT and no workspace.
+ *   rank_workspace (16-byte aligned, *_rank_workspace_bytes bytes; 0 outside the limits) is read only when the method resolves to
+ *   ROVIT_RANK_SORT.  AUTO goes by n, and by n_in + n_out for the OOD card.  The blocks are byte-identical between the methods wherever
+ *   the counting path is defined (rovit_eval_selective: every key a number; there only the counters agree otherwise).
+ * workspace of rovit_sort_f32 / rovit_rank_f32: rovit_sort_workspace_bytes / rovit_rank_workspace_bytes bytes, 16-byte aligned.
+ * Limits: 1 <= num_columns <= ROVIT_SORT_MAX_COLUMNS, 1 <= n[c] <= ROVIT_EVAL_MAX_ROWS; x 4-byte aligned, outputs 4-byte aligned.
+ * max_workgroups > 0 caps every grid and changes no output.  A bad descriptor is refused before any launch.
+ * ------------------------------------------------------------------------------------------------------------ */
+enum { ROVIT_RANK_AUTO = 0, ROVIT_RANK_COUNT = 1, ROVIT_RANK_SORT = 2 };
+#define ROVIT_RANK_SORT_ROWS 32768                /* AUTO's threshold, measured: tools/time_rank.py, profiles/rank_time.jsonl, DESIGN.md section 2 */
+#define ROVIT_SORT_MAX_COLUMNS 16
+#define ROVIT_SORT_TILE 2048
+typedef struct rovit_sort {
+  int num_columns, max_workgroups;
+  int n[ROVIT_SORT_MAX_COLUMNS];
+  const float* x[ROVIT_SORT_MAX_COLUMNS];                /* (n[c]) each */
+  unsigned int* keys_sorted[ROVIT_SORT_MAX_COLUMNS];     /* (n[c]) each */
+  unsigned int* perm[ROVIT_SORT_MAX_COLUMNS];            /* (n[c]) each */
+  void* workspace;
+  size_t workspace_bytes;
+} rovit_sort;
+typedef struct rovit_rank {
+  int num_columns, method, max_workgroups, reserved;
+  int n[ROVIT_SORT_MAX_COLUMNS];
+  const float* x[ROVIT_SORT_MAX_COLUMNS];                /* (n[c]) each */
+  unsigned int* less[ROVIT_SORT_MAX_COLUMNS];            /* (n[c]) each, as eq, before and perm */
+  unsigned int* eq[ROVIT_SORT_MAX_COLUMNS];
+  unsigned int* before[ROVIT_SORT_MAX_COLUMNS];
+  unsigned int* perm[ROVIT_SORT_MAX_COLUMNS];
+  void* workspace;                                       /* read for ROVIT_RANK_SORT only */
+  size_t workspace_bytes;
+} rovit_rank;
+size_t rovit_sort_workspace_bytes(const int* n, int num_columns);
+int rovit_sort_f32(const rovit_sort* p, rovit_stream_t stream);
+size_t rovit_rank_workspace_bytes(const int* n, int num_columns, int method);
+int rovit_rank_f32(const rovit_rank* p, rovit_stream_t stream);
+size_t rovit_eval_finalize_rank_workspace_bytes(int n);
+int rovit_eval_finalize_ex(const rovit_eval_final* p, int method, void* rank_workspace, size_t rank_workspace_bytes, rovit_stream_t stream);
+size_t rovit_eval_selective_rank_workspace_bytes(int n, int num_scores, int num_risks);
+int rovit_eval_selective_ex(const rovit_eval_sel* p, int method, void* rank_workspace, size_t rank_workspace_bytes, rovit_stream_t stream);
+size_t rovit_ood_metrics_rank_workspace_bytes(int n_in, int n_out);
+int rovit_ood_metrics_ex(const rovit_ood* p, int method, void* rank_workspace, size_t rank_workspace_bytes, rovit_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Split conformal prediction on the evaluation record (conformal.hip; the score functions live in conformal_device.h and are shared
  * by the fit and the application).  rovit_eval_conformal fits the thresholds of M nonconformity scores at A levels for G groups
  * (G = 1: all rows with a label in [0, C); class_conditional: G = 1 + C, group 1 + c the rows of true class c).

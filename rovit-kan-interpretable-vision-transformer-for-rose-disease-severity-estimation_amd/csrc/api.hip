@@ -50,6 +50,9 @@ void rovit_set_error(const char* fmt, ...) {
 // at 440 the same way: sequences of different lengths in one inference forward, attention.hip / perturb.hip / vit.hip.)
 // (rovit_patch_dropout_draw, rovit_scatter_token_rows, rovit_vit_forward_train_tokens and rovit_vit_backward_tokens were added at 440 the
 // same way: PatchDropout training on kept tokens, patch_dropout.hip / vit.hip.)
+// (rovit_sort_workspace_bytes, rovit_sort_f32, rovit_rank_workspace_bytes, rovit_rank_f32 and the three score cards' _ex forms with their
+// *_rank_workspace_bytes were added at 440 the same way: the device radix sort and the ranks behind it, sort_rank.hip.  rovit_eval_finalize,
+// rovit_eval_selective and rovit_ood_metrics keep their argument lists and their launches.)
 extern "C" int rovit_version(void) { return 440; }
 extern "C" const char* rovit_last_error_string(void) { return g_err; }
 

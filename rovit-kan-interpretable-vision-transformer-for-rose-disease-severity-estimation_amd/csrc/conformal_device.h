@@ -4,6 +4,7 @@
 #pragma once
 #include "common.h"
 #include "philox.h"
+#include "sort_device.h"
 
 namespace conformal {
 
@@ -93,11 +94,8 @@ __device__ __forceinline__ float row_score(const rovit_eval_conf& a, int m, int 
   return v + 0.0f;
 }
 
-// the order-preserving key of an fp32 value (numbers only), and back
-__device__ __forceinline__ unsigned order_key(float v) {
-  const unsigned b = __float_as_uint(v);
-  return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ __forceinline__ unsigned key_bits(unsigned k) { return (k >> 31) ? k ^ 0x80000000u : ~k; }
+// the order-preserving key of an fp32 value (numbers only), and back: shared with the radix sort (sort_device.h)
+using ::order_key;
+using ::key_bits;
 
 }  // namespace conformal

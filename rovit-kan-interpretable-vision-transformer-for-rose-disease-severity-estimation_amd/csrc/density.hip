@@ -19,10 +19,12 @@
 //   to the diagonal (the zero upper triangle is never multiplied: exact zeros either way), waves 0-1 form z = W f of row tiles 0-1, waves
 //   2-3 z0 = W0 f; the accumulators hold one feature row per lane, so ||z - M_c||^2 is an in-lane sum plus one cross-half add.
 // rovit_ood_metrics, three kernels: counted ranks on the tile of rank_count.h (uint32, integer atomics over the split j range), the per-row
-//   terms with fixed-tree chunk sums, one fold.
+//   terms with fixed-tree chunk sums, one fold.  rovit_ood_metrics_ex with ROVIT_RANK_SORT replaces ood_rank_kernel only: both populations
+//   are sorted (sort_rank.hip) and the four counts of every row come from binary searches in the two sorted key arrays.
 // Work items are walked with a stride of the grid, and no item's result depends on which workgroup computes it.  No floating-point atomics.
 #include "common.h"
 #include "rank_count.h"
+#include "sort_device.h"
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 
@@ -532,7 +534,31 @@ extern "C" int rovit_density_score(const rovit_density_scores* p, rovit_stream_t
 
 extern "C" size_t rovit_ood_metrics_workspace_bytes(int n_in, int n_out) { return ood_limits_ok(n_in, n_out) ? ood_layout(n_in, n_out).total : 0; }
 
+namespace {
+// the rank workspace of the sorted OOD card: the sorted keys and the permutations of the two populations, then the sort's own
+struct OodRankLayout { size_t keys_in, keys_out, perm_in, perm_out, sort, total; };
+inline OodRankLayout ood_rank_layout(int n_in, int n_out) {
+  const int nn[2] = {n_in, n_out};
+  OodRankLayout l;
+  l.keys_in = 0;
+  l.keys_out = l.keys_in + rovit_up16((size_t)n_in * 4);
+  l.perm_in = l.keys_out + rovit_up16((size_t)n_out * 4);
+  l.perm_out = l.perm_in + rovit_up16((size_t)n_in * 4);
+  l.sort = l.perm_out + rovit_up16((size_t)n_out * 4);
+  l.total = l.sort + rovit_sort_batch_workspace_bytes(nn, 2);
+  return l;
+}
+}  // namespace
+
+extern "C" size_t rovit_ood_metrics_rank_workspace_bytes(int n_in, int n_out) {
+  return ood_limits_ok(n_in, n_out) ? ood_rank_layout(n_in, n_out).total : 0;
+}
+
 extern "C" int rovit_ood_metrics(const rovit_ood* p, rovit_stream_t stream) {
+  return rovit_ood_metrics_ex(p, ROVIT_RANK_COUNT, nullptr, 0, stream);
+}
+
+extern "C" int rovit_ood_metrics_ex(const rovit_ood* p, int method, void* rank_workspace, size_t rank_workspace_bytes, rovit_stream_t stream) {
   const char* who = "ood_metrics";
   ROVIT_CHECK_ARG(p, ROVIT_ERR_NULL, "%s: null descriptor", who);
   ROVIT_CHECK_ARG(ood_limits_ok(p->n_in, p->n_out), ROVIT_ERR_SHAPE, "%s: %d + %d scores (each >= 1, together at most %d)", who, p->n_in, p->n_out,
@@ -549,6 +575,15 @@ extern "C" int rovit_ood_metrics(const rovit_ood* p, rovit_stream_t stream) {
   const OodLayout l = ood_layout(p->n_in, p->n_out);
   ROVIT_CHECK_ARG(p->workspace_bytes >= l.total, ROVIT_ERR_SHAPE, "%s: the workspace holds %zu bytes, %zu are needed", who, p->workspace_bytes,
                   l.total);
+  ROVIT_CHECK_ARG(method >= ROVIT_RANK_AUTO && method <= ROVIT_RANK_SORT, ROVIT_ERR_SHAPE, "%s: unknown rank method %d", who, method);
+  const bool sorted = rovit_rank_method(method, (long long)p->n_in + p->n_out) == ROVIT_RANK_SORT;
+  const OodRankLayout rl = ood_rank_layout(p->n_in, p->n_out);
+  if (sorted) {
+    ROVIT_CHECK_ARG(rank_workspace, ROVIT_ERR_NULL, "%s: the rank workspace is missing (null pointer)", who);
+    ROVIT_CHECK_ARG(rovit_aligned16(rank_workspace), ROVIT_ERR_ALIGN, "%s: the rank workspace is not 16-byte aligned", who);
+    ROVIT_CHECK_ARG(rank_workspace_bytes >= rl.total, ROVIT_ERR_SHAPE, "%s: the rank workspace holds %zu bytes, %zu are needed", who,
+                    rank_workspace_bytes, rl.total);
+  }
   char* ws = (char*)p->workspace;
   OodArgs a;
   a.n_in = p->n_in; a.n_out = p->n_out; a.N = p->n_in + p->n_out; a.chunks = (a.N + NT - 1) / NT; a.L = p->num_levels;
@@ -573,8 +608,25 @@ extern "C" int rovit_ood_metrics(const rovit_ood* p, rovit_stream_t stream) {
   splits = splits < 1 ? 1 : (splits > ntiles ? ntiles : splits);
   const int tps = (ntiles + splits - 1) / splits;
   splits = (ntiles + tps - 1) / tps;
-  hipLaunchKernelGGL(ood_rank_kernel, grid((long long)a.chunks * splits), dim3(NT), 0, s, a, splits, tps);
-  ROVIT_CHECK_LAUNCH("ood_rank_kernel");
+  if (sorted) {
+    // both populations sorted once; less and eq of every row among the in rows and among the out rows by searches in the two key arrays
+    char* rws = (char*)rank_workspace;
+    unsigned* k_in = (unsigned*)(rws + rl.keys_in);
+    unsigned* k_out = (unsigned*)(rws + rl.keys_out);
+    const RovitSortCol c[2] = {{a.s_in, k_in, (unsigned*)(rws + rl.perm_in), a.n_in}, {a.s_out, k_out, (unsigned*)(rws + rl.perm_out), a.n_out}};
+    int rc = rovit_sort_batch(c, 2, rws + rl.sort, rank_workspace_bytes - rl.sort, p->max_workgroups, s, who);
+    if (rc != ROVIT_OK) return rc;
+    const size_t N = (size_t)a.N;
+    const RovitRankQuery q[4] = {{a.s_in, a.n_in, k_in, a.n_in, a.cnt, a.cnt + N},
+                                 {a.s_out, a.n_out, k_in, a.n_in, a.cnt + a.n_in, a.cnt + N + a.n_in},
+                                 {a.s_in, a.n_in, k_out, a.n_out, a.cnt + 2 * N, a.cnt + 3 * N},
+                                 {a.s_out, a.n_out, k_out, a.n_out, a.cnt + 2 * N + a.n_in, a.cnt + 3 * N + a.n_in}};
+    rc = rovit_rank_search(q, 4, p->max_workgroups, s, who);
+    if (rc != ROVIT_OK) return rc;
+  } else {
+    hipLaunchKernelGGL(ood_rank_kernel, grid((long long)a.chunks * splits), dim3(NT), 0, s, a, splits, tps);
+    ROVIT_CHECK_LAUNCH("ood_rank_kernel");
+  }
   hipLaunchKernelGGL(ood_terms_kernel, grid(a.chunks), dim3(NT), 0, s, a);
   ROVIT_CHECK_LAUNCH("ood_terms_kernel");
   hipLaunchKernelGGL(ood_final_kernel, dim3(1), dim3(NT), 0, s, a);

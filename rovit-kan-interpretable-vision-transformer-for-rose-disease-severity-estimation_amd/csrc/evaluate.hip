@@ -16,8 +16,11 @@
 //                           atomics, the exact int64 rank sums, and the chunk's fp64 sums in a fixed order.
 //   eval_final_kernel       one workgroup adds the chunk partials (and the loss table's columns) in a fixed order.
 // O(n^2) counting by choice: exact, order-free, no sort.  n = 2^20 is the bound that keeps sum (R - n - 1)^2 <= n^3 inside int64.
+// rovit_eval_finalize_ex with ROVIT_RANK_SORT replaces eval_rank_count_kernel only: both severity columns are sorted (sort_rank.hip) and
+//   every row's less and eq come from two binary searches in its column's sorted keys: the same four count rows, word for word.
 #include "common.h"
 #include "rank_count.h"
+#include "sort_device.h"
 
 namespace {
 
@@ -209,7 +212,30 @@ extern "C" int rovit_eval_accumulate(const rovit_eval_batch* p, rovit_stream_t s
   return ROVIT_OK;
 }
 
+namespace {
+// the rank workspace of the sorted finalise: the sorted keys and the permutations of sev_true and sev_pred, then the sort's own
+struct FinalRankLayout { size_t keys, perm, sort, total; };
+inline FinalRankLayout final_rank_layout(int n) {
+  const int nn[2] = {n, n};
+  FinalRankLayout l;
+  l.keys = 0;
+  l.perm = l.keys + 2 * rovit_up16((size_t)n * 4);
+  l.sort = l.perm + 2 * rovit_up16((size_t)n * 4);
+  l.total = l.sort + rovit_sort_batch_workspace_bytes(nn, 2);
+  return l;
+}
+}  // namespace
+
+extern "C" size_t rovit_eval_finalize_rank_workspace_bytes(int n) {
+  return n >= 1 && n <= ROVIT_EVAL_MAX_ROWS ? final_rank_layout(n).total : 0;
+}
+
 extern "C" int rovit_eval_finalize(const rovit_eval_final* p, rovit_stream_t stream) {
+  return rovit_eval_finalize_ex(p, ROVIT_RANK_COUNT, nullptr, 0, stream);
+}
+
+extern "C" int rovit_eval_finalize_ex(const rovit_eval_final* p, int method, void* rank_workspace, size_t rank_workspace_bytes,
+                                      rovit_stream_t stream) {
   const char* who = "eval_finalize";
   ROVIT_CHECK_ARG(p, ROVIT_ERR_NULL, "%s: null descriptor", who);
   ROVIT_CHECK_ARG(p->num_classes >= 2 && p->num_classes <= EC, ROVIT_ERR_SHAPE, "%s: %d classes (2..%d)", who, p->num_classes, EC);
@@ -227,20 +253,44 @@ extern "C" int rovit_eval_finalize(const rovit_eval_final* p, rovit_stream_t str
                   ROVIT_ERR_ALIGN, "%s: a record array is not 16-byte aligned", who);
   ROVIT_CHECK_ARG(rovit_aligned(p->bin_edges, 8) && rovit_aligned16(p->rank_counts) && rovit_aligned(p->partials, 8) && rovit_aligned(p->result, 8),
                   ROVIT_ERR_ALIGN, "%s: bin edges, a workspace or the result block is not aligned", who);
+  ROVIT_CHECK_ARG(method >= ROVIT_RANK_AUTO && method <= ROVIT_RANK_SORT, ROVIT_ERR_SHAPE, "%s: unknown rank method %d", who, method);
   const int n = p->n, chunks = (n + NT - 1) / NT, ntiles = (n + RANK_RT - 1) / RANK_RT;
+  const bool sorted = rovit_rank_method(method, n) == ROVIT_RANK_SORT;
+  const FinalRankLayout rl = final_rank_layout(n);
+  if (sorted) {
+    ROVIT_CHECK_ARG(rank_workspace, ROVIT_ERR_NULL, "%s: the rank workspace is missing (null pointer)", who);
+    ROVIT_CHECK_ARG(rovit_aligned16(rank_workspace), ROVIT_ERR_ALIGN, "%s: the rank workspace is not 16-byte aligned", who);
+    ROVIT_CHECK_ARG(rank_workspace_bytes >= rl.total, ROVIT_ERR_SHAPE, "%s: the rank workspace holds %zu bytes, %zu are needed", who,
+                    rank_workspace_bytes, rl.total);
+  }
   hipStream_t s = (hipStream_t)stream;
   if (hipMemsetAsync(p->rank_counts, 0, 4 * (size_t)n * sizeof(unsigned), s) != hipSuccess ||
       hipMemsetAsync(p->result, 0, ROVIT_EVAL_RESULT_WORDS * 8, s) != hipSuccess) {
     rovit_set_error("%s: hipMemsetAsync failed", who);
     return ROVIT_ERR_LAUNCH;
   }
-  // split the j range until about 1024 workgroups exist (four per CU); the counts are integers, so the split changes nothing
-  int splits = (1024 + chunks - 1) / chunks;
-  splits = splits < 1 ? 1 : (splits > ntiles ? ntiles : splits);
-  const int tps = (ntiles + splits - 1) / splits;
-  splits = (ntiles + tps - 1) / tps;
-  hipLaunchKernelGGL(eval_rank_count_kernel, dim3(chunks, splits), dim3(NT), 0, s, p->sev_true, p->sev_pred, n, tps, p->rank_counts);
-  ROVIT_CHECK_LAUNCH("eval_rank_count_kernel");
+  if (sorted) {
+    // the same four count rows from two sorted columns: less and eq of every row by two binary searches in its own column's keys
+    char* ws = (char*)rank_workspace;
+    const size_t col = rovit_up16((size_t)n * 4);
+    unsigned* keys[2] = {(unsigned*)(ws + rl.keys), (unsigned*)(ws + rl.keys + col)};
+    unsigned* perm[2] = {(unsigned*)(ws + rl.perm), (unsigned*)(ws + rl.perm + col)};
+    const RovitSortCol c[2] = {{p->sev_true, keys[0], perm[0], n}, {p->sev_pred, keys[1], perm[1], n}};
+    int rc = rovit_sort_batch(c, 2, ws + rl.sort, rank_workspace_bytes - rl.sort, 0, s, who);
+    if (rc != ROVIT_OK) return rc;
+    const RovitRankQuery q[2] = {{p->sev_true, n, keys[0], n, p->rank_counts, p->rank_counts + (size_t)n},
+                                 {p->sev_pred, n, keys[1], n, p->rank_counts + 2 * (size_t)n, p->rank_counts + 3 * (size_t)n}};
+    rc = rovit_rank_search(q, 2, 0, s, who);
+    if (rc != ROVIT_OK) return rc;
+  } else {
+    // split the j range until about 1024 workgroups exist (four per CU); the counts are integers, so the split changes nothing
+    int splits = (1024 + chunks - 1) / chunks;
+    splits = splits < 1 ? 1 : (splits > ntiles ? ntiles : splits);
+    const int tps = (ntiles + splits - 1) / splits;
+    splits = (ntiles + tps - 1) / tps;
+    hipLaunchKernelGGL(eval_rank_count_kernel, dim3(chunks, splits), dim3(NT), 0, s, p->sev_true, p->sev_pred, n, tps, p->rank_counts);
+    ROVIT_CHECK_LAUNCH("eval_rank_count_kernel");
+  }
   hipLaunchKernelGGL(eval_partial_kernel, dim3(chunks), dim3(NT), 0, s, *p);
   ROVIT_CHECK_LAUNCH("eval_partial_kernel");
   hipLaunchKernelGGL(eval_final_kernel, dim3(1), dim3(NT), 0, s, *p, chunks);

@@ -20,8 +20,11 @@
 //                        the same bits), mean = r_n and the thresholds.
 // A pair is (score s, risk k), q = s K + k, or (risk k, risk k), q = S K + k: the oracle.  Work items are walked with a stride of the
 // grid, and no item's result depends on which workgroup computes it: the grid cap changes nothing.  No floating-point atomics.
+// rovit_eval_selective_ex with ROVIT_RANK_SORT replaces sel_rank_kernel and sel_perm_kernel only: the S + K columns are sorted in one
+// batched call (sort_rank.hip), whose perm IS the stable order, and less, eq and before follow from two searches per sorted slot.
 #include "common.h"
 #include "rank_count.h"
+#include "sort_device.h"
 
 namespace {
 
@@ -285,7 +288,31 @@ static inline bool limits_ok(int n, int S, int K) {
 
 extern "C" size_t rovit_eval_selective_workspace_bytes(int n, int S, int K) { return limits_ok(n, S, K) ? layout(n, S, K).total : 0; }
 
+namespace {
+// the rank workspace of the sorted score card: the sorted keys of the S + K columns, then the sort's own
+struct SelRankLayout { size_t keys, sort, total; };
+inline SelRankLayout sel_rank_layout(int n, int cols) {
+  int nn[ROVIT_SORT_MAX_COLUMNS];
+  for (int c = 0; c < cols; ++c) nn[c] = n;
+  SelRankLayout l;
+  l.keys = 0;
+  l.sort = l.keys + (size_t)cols * rovit_up16((size_t)n * 4);
+  l.total = l.sort + rovit_sort_batch_workspace_bytes(nn, cols);
+  return l;
+}
+static_assert(MS + MK <= ROVIT_SORT_MAX_COLUMNS, "every column of a score card fits one batched sort");
+}  // namespace
+
+extern "C" size_t rovit_eval_selective_rank_workspace_bytes(int n, int S, int K) {
+  return limits_ok(n, S, K) ? sel_rank_layout(n, S + K).total : 0;
+}
+
 extern "C" int rovit_eval_selective(const rovit_eval_sel* p, rovit_stream_t stream) {
+  return rovit_eval_selective_ex(p, ROVIT_RANK_COUNT, nullptr, 0, stream);
+}
+
+extern "C" int rovit_eval_selective_ex(const rovit_eval_sel* p, int method, void* rank_workspace, size_t rank_workspace_bytes,
+                                       rovit_stream_t stream) {
   const char* who = "eval_selective";
   ROVIT_CHECK_ARG(p, ROVIT_ERR_NULL, "%s: null descriptor", who);
   ROVIT_CHECK_ARG(p->n >= 1 && p->n <= ROVIT_EVAL_MAX_ROWS, ROVIT_ERR_SHAPE, "%s: %d recorded rows (1..%d)", who, p->n, ROVIT_EVAL_MAX_ROWS);
@@ -329,6 +356,15 @@ extern "C" int rovit_eval_selective(const rovit_eval_sel* p, rovit_stream_t stre
   ROVIT_CHECK_ARG(p->workspace_bytes >= l.total, ROVIT_ERR_SHAPE, "%s: the workspace holds %zu bytes, %zu are needed", who, p->workspace_bytes,
                   l.total);
 
+  ROVIT_CHECK_ARG(method >= ROVIT_RANK_AUTO && method <= ROVIT_RANK_SORT, ROVIT_ERR_SHAPE, "%s: unknown rank method %d", who, method);
+  const bool sorted = rovit_rank_method(method, n) == ROVIT_RANK_SORT;
+  const SelRankLayout rl = sel_rank_layout(n, S + K);
+  if (sorted) {
+    ROVIT_CHECK_ARG(rank_workspace, ROVIT_ERR_NULL, "%s: the rank workspace is missing (null pointer)", who);
+    ROVIT_CHECK_ARG(rovit_aligned16(rank_workspace), ROVIT_ERR_ALIGN, "%s: the rank workspace is not 16-byte aligned", who);
+    ROVIT_CHECK_ARG(rank_workspace_bytes >= rl.total, ROVIT_ERR_SHAPE, "%s: the rank workspace holds %zu bytes, %zu are needed", who,
+                    rank_workspace_bytes, rl.total);
+  }
   char* ws = (char*)p->workspace;
   Args a;
   a.n = n; a.S = S; a.K = K; a.P = P; a.chunks = (n + NT - 1) / NT;
@@ -355,10 +391,28 @@ extern "C" int rovit_eval_selective(const rovit_eval_sel* p, rovit_stream_t stre
   splits = (ntiles + tps - 1) / tps;
   hipLaunchKernelGGL(sel_prepare_kernel, grid(a.chunks), dim3(NT), 0, s, *p, (float*)(ws + l.x), a.chunks);
   ROVIT_CHECK_LAUNCH("sel_prepare_kernel");
-  hipLaunchKernelGGL(sel_rank_kernel, grid((long long)a.chunks * splits * cols), dim3(NT), 0, s, a, splits, tps);
-  ROVIT_CHECK_LAUNCH("sel_rank_kernel");
-  hipLaunchKernelGGL(sel_perm_kernel, grid((long long)a.chunks * cols), dim3(NT), 0, s, a);
-  ROVIT_CHECK_LAUNCH("sel_perm_kernel");
+  if (sorted) {
+    // the sort's perm IS the stable order; less, eq and before of the row in every sorted slot by two searches in the sorted keys
+    char* rws = (char*)rank_workspace;
+    RovitSortCol c[ROVIT_SORT_MAX_COLUMNS];
+    RovitRankSlots r[ROVIT_SORT_MAX_COLUMNS];
+    for (int k = 0; k < cols; ++k) {
+      unsigned* keys = (unsigned*)(rws + rl.keys + (size_t)k * rovit_up16((size_t)n * 4));
+      unsigned* perm = a.perm + (size_t)k * n;
+      unsigned* cnt = a.cnt + (size_t)k * 3 * n;
+      c[k] = RovitSortCol{a.x + (size_t)k * n, keys, perm, n};
+      r[k] = RovitRankSlots{keys, perm, n, cnt, cnt + (size_t)n, cnt + 2 * (size_t)n};
+    }
+    int rc = rovit_sort_batch(c, cols, rws + rl.sort, rank_workspace_bytes - rl.sort, p->max_workgroups, s, who);
+    if (rc != ROVIT_OK) return rc;
+    rc = rovit_rank_slots(r, cols, p->max_workgroups, s, who);
+    if (rc != ROVIT_OK) return rc;
+  } else {
+    hipLaunchKernelGGL(sel_rank_kernel, grid((long long)a.chunks * splits * cols), dim3(NT), 0, s, a, splits, tps);
+    ROVIT_CHECK_LAUNCH("sel_rank_kernel");
+    hipLaunchKernelGGL(sel_perm_kernel, grid((long long)a.chunks * cols), dim3(NT), 0, s, a);
+    ROVIT_CHECK_LAUNCH("sel_perm_kernel");
+  }
   hipLaunchKernelGGL(sel_scan_kernel, grid((long long)a.chunks * Q), dim3(NT), 0, s, a);
   ROVIT_CHECK_LAUNCH("sel_scan_kernel");
   hipLaunchKernelGGL(sel_offsets_kernel, grid(Q), dim3(NT), 0, s, a);

@@ -235,9 +235,13 @@ def ood_metrics_reference(scores_in, scores_out, tpr_levels: Sequence[float] = (
 
 # ---- device entry points -------------------------------------------------------------------------------------------------------------
 
-def ood_block(scores_in: torch.Tensor, scores_out: torch.Tensor, tpr_levels: Sequence[float] = (0.95,), max_workgroups: int = 0) -> np.ndarray:
+def ood_block(scores_in: torch.Tensor, scores_out: torch.Tensor, tpr_levels: Sequence[float] = (0.95,), max_workgroups: int = 0,
+              rank: str = 'auto') -> np.ndarray:
     """``rovit_ood_metrics``' result block as int64 words on the host (one launch sequence, one device-to-host copy); CPU tensors run
-    ``ood_block_reference``."""
+    ``ood_block_reference``.  ``rank``: ``'count'``, ``'sort'`` or ``'auto'`` (by n_in + n_out), how the ranks are found; the block
+    does not depend on it."""
+    if rank not in native.RANK_METHODS:
+        raise RovitHipError(f"ood_metrics: rank must be one of {sorted(native.RANK_METHODS)}, got {rank!r}")
     if not scores_in.is_cuda:
         return ood_block_reference(scores_in, scores_out, tpr_levels)
     a, b = scores_in.detach().float().reshape(-1).contiguous(), scores_out.detach().float().reshape(-1).contiguous()
@@ -256,17 +260,20 @@ def ood_block(scores_in: torch.Tensor, scores_out: torch.Tensor, tpr_levels: Seq
     for l, v in enumerate(levels):
         d.tpr_levels[l] = v
     d.scores_in, d.scores_out, d.workspace, d.workspace_bytes, d.result = native.ptr(a), native.ptr(b), native.ptr(ws), nbytes, native.ptr(result)
-    native.call('rovit_ood_metrics', ctypes.byref(d), native.stream_ptr())
+    method = native.rank_method(rank, n_in + n_out, 'ood_metrics')
+    rank_bytes = lib.rovit_ood_metrics_rank_workspace_bytes(n_in, n_out) if method == native.RANK_SORT else 0
+    rank_ws = torch.empty(rank_bytes, dtype=torch.uint8, device=a.device) if rank_bytes else None
+    native.call('rovit_ood_metrics_ex', ctypes.byref(d), method, native.ptr(rank_ws), rank_bytes, native.stream_ptr())
     return result.cpu().numpy()                                   # the single device-to-host copy
 
 
-def ood_metrics(scores_in: torch.Tensor, scores_out: torch.Tensor, tpr_levels: Sequence[float] = (0.95,)) -> Dict:
+def ood_metrics(scores_in: torch.Tensor, scores_out: torch.Tensor, tpr_levels: Sequence[float] = (0.95,), rank: str = 'auto') -> Dict:
     """How well a score separates out-of-distribution rows (higher = more anomalous, the positives) from in-distribution rows:
     ``auroc`` = P(out > in) + P(out == in) / 2 exactly (a ratio of integers); ``aupr_out`` / ``aupr_in``: average precision with the
     out / the in rows as the positives, tied scores entering a threshold together; ``fpr_at_tpr[level]``: the share of out rows at or
     below ``thresholds[level]``, the ceil(level n_in)-th smallest in-distribution score (the detector that flags scores ABOVE it keeps
-    that share of the in rows); ``n_in``, ``n_out``.  Non-finite scores raise, after the copy."""
-    return ood_from_block(ood_block(scores_in, scores_out, tpr_levels), tpr_levels)
+    that share of the in rows); ``n_in``, ``n_out``.  Non-finite scores raise, after the copy.  ``rank``: see ``ood_block``."""
+    return ood_from_block(ood_block(scores_in, scores_out, tpr_levels, rank=rank), tpr_levels)
 
 
 class FeatureDensity:

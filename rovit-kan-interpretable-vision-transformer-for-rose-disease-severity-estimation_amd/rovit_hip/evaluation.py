@@ -27,6 +27,10 @@ statistic found by an O(n) radix select, one copy for the whole call; ``Conforma
 (``rovit_eval_conformal_apply``), ``Conformal.predict`` gives label sets and severity intervals for deployment;
 ``conformal_reference`` is the numpy statement.
 
+``EvalAccumulator.rank_method`` (``'auto'``, ``'count'`` or ``'sort'``) chooses how the finalise and ``selective`` rank their columns: the
+O(n^2) counting rank, or the device radix sort of ``rovit_hip.rank`` from ``native.RANK_SORT_ROWS`` rows on; the result blocks are
+byte-identical either way.
+
 On CPU tensors the same class runs the plain torch / numpy fp64 restatement below (``result_block_from_arrays``), as
 ``JointLoss._forward_tensor_ops`` does: the host logic is testable without a GPU, and ``evaluation.metrics`` is built on it.
 """
@@ -202,6 +206,7 @@ class EvalAccumulator:
         if not (isinstance(capacity, int) and 1 <= capacity <= native.EVAL_MAX_ROWS):
             raise RovitHipError(f'EvalAccumulator: capacity must be in 1..{native.EVAL_MAX_ROWS}, got {capacity!r}')
         self.num_classes, self.n_bins, self._capacity0 = num_classes, n_bins, capacity
+        self.rank_method = 'auto'                                  # 'count' | 'sort' | 'auto': how _finalize and selective rank; no result depends on it
         self.reset()
 
     def reset(self) -> None:
@@ -384,7 +389,10 @@ class EvalAccumulator:
             setattr(d, k, native.ptr(self._rec[k]))
         d.loss_table = native.ptr(self._loss_table)
         d.bin_edges, d.rank_counts, d.partials, d.result = (native.ptr(t) for t in (self._edges, counts, partials, result))
-        native.call('rovit_eval_finalize', ctypes.byref(d), native.stream_ptr())
+        method = native.rank_method(self.rank_method, self.n, 'EvalAccumulator.rank_method')
+        rank_bytes = native.load().rovit_eval_finalize_rank_workspace_bytes(self.n) if method == native.RANK_SORT else 0
+        rank_ws = torch.empty(rank_bytes, dtype=torch.uint8, device=dev) if rank_bytes else None
+        native.call('rovit_eval_finalize_ex', ctypes.byref(d), method, native.ptr(rank_ws), rank_bytes, native.stream_ptr())
         self._block_dev, self._rank_counts = result, counts
         return result
 
@@ -476,7 +484,10 @@ class EvalAccumulator:
             if return_keys:
                 f = out[W:].view(torch.float32)
                 d.keys_out, d.risks_out = native.ptr(f), native.ptr(f[S * n:])
-            native.call('rovit_eval_selective', ctypes.byref(d), native.stream_ptr())
+            method = native.rank_method(self.rank_method, n, 'EvalAccumulator.rank_method')
+            rank_bytes = native.load().rovit_eval_selective_rank_workspace_bytes(n, S, K) if method == native.RANK_SORT else 0
+            rank_ws = torch.empty(rank_bytes, dtype=torch.uint8, device=self.device) if rank_bytes else None
+            native.call('rovit_eval_selective_ex', ctypes.byref(d), method, native.ptr(rank_ws), rank_bytes, native.stream_ptr())
             host = out.cpu().numpy()                             # the call's single device-to-host copy
             block = host[:W]
             if return_keys:
@@ -854,6 +865,7 @@ class Calibration:
         if not isinstance(acc, EvalAccumulator) or acc.n < 1:
             raise RovitHipError('Calibration.apply: an EvalAccumulator with recorded rows is needed')
         new = EvalAccumulator(acc.num_classes, acc.n_bins, acc._capacity0)
+        new.rank_method = acc.rank_method
         new.n, new.n_loss_rows, new.device, new._has_uncertainty, new._extra_names = acc.n, acc.n_loss_rows, acc.device, acc._has_uncertainty, acc._extra_names
         shift = None if self.sigma_scale is None else 2.0 * math.log(self.sigma_scale)
         if acc.device.type != 'cuda':

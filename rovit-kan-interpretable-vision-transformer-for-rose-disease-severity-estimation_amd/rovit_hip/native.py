@@ -153,6 +153,16 @@ SIGNATURES = {
     'rovit_density_score': (_i, [_vp, _vp]),
     'rovit_ood_metrics_workspace_bytes': (_sz, [_i, _i]),
     'rovit_ood_metrics': (_i, [_vp, _vp]),
+    'rovit_sort_workspace_bytes': (_sz, [_vp, _i]),
+    'rovit_sort_f32': (_i, [_vp, _vp]),
+    'rovit_rank_workspace_bytes': (_sz, [_vp, _i, _i]),
+    'rovit_rank_f32': (_i, [_vp, _vp]),
+    'rovit_eval_finalize_rank_workspace_bytes': (_sz, [_i]),
+    'rovit_eval_finalize_ex': (_i, [_vp, _i, _vp, _sz, _vp]),
+    'rovit_eval_selective_rank_workspace_bytes': (_sz, [_i, _i, _i]),
+    'rovit_eval_selective_ex': (_i, [_vp, _i, _vp, _sz, _vp]),
+    'rovit_ood_metrics_rank_workspace_bytes': (_sz, [_i, _i]),
+    'rovit_ood_metrics_ex': (_i, [_vp, _i, _vp, _sz, _vp]),
     'rovit_knn_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'rovit_knn_build': (_i, [_vp, _vp]),
     'rovit_knn_search': (_i, [_vp, _vp]),
@@ -377,6 +387,34 @@ class Ood(C.Structure):
     """``rovit_ood`` of include/rovit_hip.h, field for field."""
     _fields_ = [('n_in', _i), ('n_out', _i), ('num_levels', _i), ('max_workgroups', _i), ('tpr_levels', C.c_double * OOD_MAX_LEVELS),
                 ('scores_in', _vp), ('scores_out', _vp), ('workspace', _vp), ('workspace_bytes', _sz), ('result', _vp)]
+
+
+# rovit_sort_f32 / rovit_rank_f32 and the rank method of the three score cards (the ROVIT_RANK_* and ROVIT_SORT_* names of
+# include/rovit_hip.h).  RANK_SORT_ROWS: 'auto' sorts from this many rows on (measured, profiles/rank_time.jsonl).
+RANK_AUTO, RANK_COUNT, RANK_SORT = 0, 1, 2
+RANK_METHODS = {'auto': RANK_AUTO, 'count': RANK_COUNT, 'sort': RANK_SORT}
+RANK_SORT_ROWS, SORT_MAX_COLUMNS, SORT_TILE, SORT_NAN_KEY = 32768, 16, 2048, 0xFFFFFFFF
+
+
+class Sort(C.Structure):
+    """``rovit_sort`` of include/rovit_hip.h, field for field."""
+    _fields_ = [('num_columns', _i), ('max_workgroups', _i), ('n', _i * SORT_MAX_COLUMNS), ('x', _vp * SORT_MAX_COLUMNS),
+                ('keys_sorted', _vp * SORT_MAX_COLUMNS), ('perm', _vp * SORT_MAX_COLUMNS), ('workspace', _vp), ('workspace_bytes', _sz)]
+
+
+class Rank(C.Structure):
+    """``rovit_rank`` of include/rovit_hip.h, field for field."""
+    _fields_ = [('num_columns', _i), ('method', _i), ('max_workgroups', _i), ('reserved', _i), ('n', _i * SORT_MAX_COLUMNS),
+                ('x', _vp * SORT_MAX_COLUMNS), ('less', _vp * SORT_MAX_COLUMNS), ('eq', _vp * SORT_MAX_COLUMNS),
+                ('before', _vp * SORT_MAX_COLUMNS), ('perm', _vp * SORT_MAX_COLUMNS), ('workspace', _vp), ('workspace_bytes', _sz)]
+
+
+def rank_method(method, n: int, what: str = 'rank') -> int:
+    """``'auto'`` / ``'count'`` / ``'sort'`` as ROVIT_RANK_COUNT or ROVIT_RANK_SORT for n rows (ROVIT_RANK_AUTO resolved as the library does)."""
+    if method not in RANK_METHODS:
+        raise RovitHipError(f"{what}: the rank method must be one of {sorted(RANK_METHODS)}, got {method!r}")
+    m = RANK_METHODS[method]
+    return (RANK_SORT if n >= RANK_SORT_ROWS else RANK_COUNT) if m == RANK_AUTO else m
 
 
 def density_chunk_rows(n: int) -> int:
