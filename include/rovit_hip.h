@@ -1614,6 +1614,91 @@ int rovit_shap_coalitions(const rovit_shap_coalition_args* p, rovit_stream_t str
 int rovit_shap_gram(const rovit_shap_gram_args* p, rovit_stream_t stream);
 int rovit_shap_solve(const rovit_shap_solve_args* p, rovit_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Exact t-SNE of feature rows (tsne.hip; van der Maaten & Hinton 2008): the dense affinities P and the gradient descent on a 2-D map.
+ * Rows x_i are fp32 (n, embed) row-major; all state is fp32; u = 2^-24.
+ *
+ * rovit_tsne_affinities, in stream order (P holds D, then the conditional rows, then P):
+ *   rows        a row is valid when every feature and its squared norm (an fp32 fma chain) are finite and, with ROVIT_KNN_COSINE, the
+ *               squared norm is positive.  With _COSINE the kernels below run on the unit rows x / sqrt(|x|^2), formed element by
+ *               element as rovit_knn_build forms them.  Every later step treats a row that is not valid as absent.
+ *   distances   D_ij = sum_k (x_ik - x_jk)^2 as ONE fp32 chain acc = fma(x_ik - x_jk, x_ik - x_jk, acc), k ascending from 0: every term
+ *               is non-negative, |D - exact| <= (embed + 2) u D, D_ii = 0 and D_ij = D_ji bit for bit; 0 where i or j is not valid.
+ *               distances_only != 0 stops here (P = D; beta, entropy and status are not written).
+ *   perplexity  a workgroup per valid row i over its candidates (the valid j != i): d_j = D_ij - min_j D_ij, beta = 1, then exactly 64
+ *               steps: H(beta) = log S + beta sum_j d_j w_j / S with w_j = exp(-(beta d_j)) and S = sum_j w_j; H > log(perplexity): beta
+ *               becomes the lower bracket and doubles (or moves half way to the upper one when there is one); otherwise it becomes the
+ *               upper bracket and halves (or moves half way to the lower one).  beta is kept in fp64 and used rounded to fp32; w in fp32
+ *               (expf); the sums as described below.  After the loop p_j|i = w_j / S (an fp64 division rounded once), 0 on the diagonal
+ *               and at rows that are not valid; beta[i] and entropy[i] = H at the final beta.  A row with fewer than two brackets after
+ *               the loop is counted as unconverged: it has at least `perplexity` exact duplicates, its beta ends at 2^64 and its row is
+ *               uniform over the duplicates.  beta d is formed so that d = 0 gives 0: no NaN arises.  A row that is not valid gets a zero
+ *               row, beta 0 and entropy 0.
+ *   symmetrise  (symmetrize != 0) P_ij = max((p_j|i + p_i|j) / (2 n_valid), 1e-12) for valid i != j (one fp32 add, one IEEE division),
+ *               0 on the diagonal and in rows and columns that are not valid; in place by tile pairs, symmetric bit for bit.
+ *   status      ROVIT_TSNE_WORDS int64 words: [_N] [_N_VALID] [_BAD_ROWS] [_UNCONVERGED] and the fp32 bit patterns of the smallest and
+ *               largest beta of a valid row [_MIN_BETA] [_MAX_BETA].
+ *
+ * rovit_tsne_run: n_iter iterations on the caller's stream, two launches each, nothing waits for the host.  A map row with a NaN
+ * coordinate is absent (the caller marks the rows that are not valid this way; P is 0 there): it keeps its NaN and adds to nothing.
+ *   forces      for row i over the present j != i, w_ij = 1 / (1 + |y_i - y_j|^2): a_i = sum_j P_ij w_ij (y_i - y_j),
+ *               r_i = sum_j w_ij^2 (y_i - y_j), z_i = sum_j w_ij; on the iterations t with t % kl_every == 0, and on the last one (kl_every
+ *               0: never), A_i = sum_j P_ij (log P_ij - log w_ij) over P_ij > 0 and B_i = sum_j P_ij.
+ *   update      Z = sum_i z_i (every workgroup folds it itself); g = 4 (alpha a - r / Z); gain = (v g < 0) ? gain + 0.2 : gain 0.8, then
+ *               max(gain, 0.01); v = m v - eta gain g; y += v: sklearn's _gradient_descent.  KL_t = sum A + log Z sum B goes to the next
+ *               free slot of trace.  alpha = early_exaggeration and m = momentum_early for t < exaggeration_iter, then 1 and momentum_late.
+ *               learning_rate <= 0 stands for sklearn's 'auto', max(n_present / early_exaggeration / 4, 50), resolved on the device:
+ *               the host does not know n_present without a copy.  grad_out (n, 2) and z_out (1), when given, receive g and Z of the last
+ *               iteration.
+ *   center != 0 subtracts the mean of the present rows once, after the last iteration.
+ *   status      [_N] [_N_VALID] (present rows) [_BAD_ROWS] [_RUN_ITERATIONS] [_RUN_TRACE] (slots written) [_RUN_NONFINITE] (present rows
+ *               with an infinite coordinate, before centring).
+ * Sums (S, the forces, Z, the KL parts, the mean): a lane or thread adds its own elements in ascending index in fp32 (element j belongs
+ * to lane j % 64 of its row's wave, or to thread j % 256), the wave folds by a fixed butterfly in fp32, the four waves fold in wave
+ * order in fp64.  No atomic, no cooperative launch, no kernel that waits on another workgroup; work items are walked with a stride of
+ * the grid: every output is bit-identical from run to run and for every max_workgroups (> 0 caps every grid).
+ * rovit_tsne_random_init: Y[e] = 1e-4 sqrt(-2 ln u1) cos(2 pi u2), e in [0, 2 n), u1 = ((x >> 8) + 1) 2^-24 and u2 = (y >> 8) 2^-24 from
+ * words x, y of Philox4x32-10 with key = seed and counter (e, 0, ROVIT_TSNE_STREAM, 0).
+ * workspace: rovit_tsne_workspace_bytes(n, embed) bytes, 16-byte aligned (0 outside the limits); the same block serves both entries.
+ * Limits: embed a multiple of 32 in 32..256 with 16-byte aligned rows, 4 <= n <= ROVIT_TSNE_MAX_ROWS (dense P is 1 GiB there),
+ * 1 < perplexity < n - 1 (n_valid is known on the device only: fewer valid rows than the perplexity allows show in status, as
+ * unconverged rows), 1 <= n_iter <= ROVIT_TSNE_MAX_ITER, Y 8-byte aligned.  A bad descriptor returns ROVIT_ERR_SHAPE (_NULL, _ALIGN)
+ * before any launch.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define ROVIT_TSNE_MAX_ROWS 16384
+#define ROVIT_TSNE_MAX_ITER 100000
+#define ROVIT_TSNE_STREAM 0x54534E45u          /* "TSNE": counter word 2, apart from the other Philox streams */
+enum { ROVIT_TSNE_N = 0, ROVIT_TSNE_N_VALID = 1, ROVIT_TSNE_BAD_ROWS = 2, ROVIT_TSNE_UNCONVERGED = 3, ROVIT_TSNE_MIN_BETA = 4,
+       ROVIT_TSNE_MAX_BETA = 5, ROVIT_TSNE_WORDS = 8 };
+enum { ROVIT_TSNE_RUN_ITERATIONS = 3, ROVIT_TSNE_RUN_TRACE = 4, ROVIT_TSNE_RUN_NONFINITE = 5 };
+typedef struct rovit_tsne_affinity {
+  int n, embed, metric, symmetrize, distances_only, max_workgroups;
+  double perplexity;
+  const float* features;             /* (n, embed) */
+  void* workspace;
+  size_t workspace_bytes;
+  float* P;                          /* (n, n) */
+  float* beta; float* entropy;       /* (n) each */
+  void* status;                      /* ROVIT_TSNE_WORDS 8-byte words */
+} rovit_tsne_affinity;
+typedef struct rovit_tsne_descent {
+  int n, n_iter, exaggeration_iter, kl_every, center, max_workgroups, trace_capacity, reserved;
+  float early_exaggeration, momentum_early, momentum_late, learning_rate;
+  const float* P;                    /* (n, n) */
+  float* Y;                          /* (n, 2): the initial map on entry, the map on exit */
+  float* V; float* G;                /* (n, 2) each: the velocities and the gains, carried from call to call */
+  void* workspace;
+  size_t workspace_bytes;
+  float* trace;                      /* trace_capacity values; NULL with kl_every 0 */
+  void* status;                      /* ROVIT_TSNE_WORDS 8-byte words */
+  float* grad_out;                   /* (n, 2) or NULL */
+  float* z_out;                      /* (1) or NULL */
+} rovit_tsne_descent;
+size_t rovit_tsne_workspace_bytes(int n, int embed);
+int rovit_tsne_affinities(const rovit_tsne_affinity* p, rovit_stream_t stream);
+int rovit_tsne_run(const rovit_tsne_descent* p, rovit_stream_t stream);
+int rovit_tsne_random_init(unsigned long long seed, float* Y, int n, rovit_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -53,6 +53,8 @@ void rovit_set_error(const char* fmt, ...) {
 // (rovit_sort_workspace_bytes, rovit_sort_f32, rovit_rank_workspace_bytes, rovit_rank_f32 and the three score cards' _ex forms with their
 // *_rank_workspace_bytes were added at 440 the same way: the device radix sort and the ranks behind it, sort_rank.hip.  rovit_eval_finalize,
 // rovit_eval_selective and rovit_ood_metrics keep their argument lists and their launches.)
+// (rovit_tsne_workspace_bytes, rovit_tsne_affinities, rovit_tsne_run and rovit_tsne_random_init were added at 440 the same way: exact t-SNE
+// of the feature space, tsne.hip.)
 extern "C" int rovit_version(void) { return 440; }
 extern "C" const char* rovit_last_error_string(void) { return g_err; }
 

@@ -330,6 +330,16 @@ class RoViTKAN(nn.Module):
         from rovit_hip import neighbors
         return neighbors.fit_model_index(self, x_or_loader, labels, severity, metric, chunk)
 
+    def feature_map(self, x_or_loader, chunk: int = 256, **tsne_kwargs) -> Dict:
+        """Extension (not in the reference): the exact t-SNE map of this model's backbone features over images (a (B,3,224,224) tensor or
+        an iterable of batches, gathered as ``fit_feature_index`` gathers them: eval mode, ``chunk`` images at a time, no ``.grad``
+        written).  ``tsne_kwargs`` go to ``rovit_hip.embedding.TSNE``.  Returns ``map`` (n, 2), ``features`` (n, E) and
+        ``kl_divergence`` (a 0-d device tensor: nothing is copied to the host)."""
+        from rovit_hip import embedding, neighbors
+        feats = neighbors.fit_model_index(self, x_or_loader, metric='l2', chunk=chunk).rows().clone()
+        tsne = embedding.TSNE(**tsne_kwargs)
+        return {'map': tsne.fit_transform(feats), 'features': feats, 'kl_divergence': tsne.kl_trace_[-1]}
+
     def nearest_examples(self, x: torch.Tensor, index, k: int = 5) -> Dict[str, torch.Tensor]:
         """Extension (not in the reference): explanation by example.  One forward, then ``index.search(features, k)``: the ``k`` nearest
         recorded rows of every image with their labels and severities, the neighbours' vote, and beside it the heads' own ``class``

@@ -180,6 +180,10 @@ SIGNATURES = {
     'rovit_influence_embed': (_i, [_vp, _vp]),
     'rovit_influence_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'rovit_influence_search': (_i, [_vp, _vp]),
+    'rovit_tsne_workspace_bytes': (_sz, [_i, _i]),
+    'rovit_tsne_affinities': (_i, [_vp, _vp]),
+    'rovit_tsne_run': (_i, [_vp, _vp]),
+    'rovit_tsne_random_init': (_i, [C.c_ulonglong, _vp, _i, _vp]),
 }
 
 
@@ -449,6 +453,27 @@ class KnnQuery(C.Structure):
                 ('exclude', _vp), ('ref_labels', _vp), ('ref_severity', _vp), ('workspace', _vp), ('workspace_bytes', _sz),
                 ('distances', _vp), ('indices', _vp), ('labels', _vp), ('severities', _vp), ('class_probs', _vp), ('cls', _vp),
                 ('severity', _vp), ('kth_distance', _vp), ('mean_distance', _vp)]
+
+
+# rovit_tsne_affinities / rovit_tsne_run: limits, the Philox stream word and the status blocks (the ROVIT_TSNE_* names of include/rovit_hip.h)
+TSNE_MAX_ROWS, TSNE_MAX_ITER, TSNE_STREAM = 16384, 100000, 0x54534E45
+TSNE_N, TSNE_N_VALID, TSNE_BAD_ROWS, TSNE_UNCONVERGED, TSNE_MIN_BETA, TSNE_MAX_BETA, TSNE_WORDS = 0, 1, 2, 3, 4, 5, 8
+TSNE_RUN_ITERATIONS, TSNE_RUN_TRACE, TSNE_RUN_NONFINITE = 3, 4, 5
+
+
+class TsneAffinity(C.Structure):
+    """``rovit_tsne_affinity`` of include/rovit_hip.h, field for field."""
+    _fields_ = [('n', _i), ('embed', _i), ('metric', _i), ('symmetrize', _i), ('distances_only', _i), ('max_workgroups', _i),
+                ('perplexity', C.c_double), ('features', _vp), ('workspace', _vp), ('workspace_bytes', _sz), ('P', _vp), ('beta', _vp),
+                ('entropy', _vp), ('status', _vp)]
+
+
+class TsneDescent(C.Structure):
+    """``rovit_tsne_descent`` of include/rovit_hip.h, field for field."""
+    _fields_ = [('n', _i), ('n_iter', _i), ('exaggeration_iter', _i), ('kl_every', _i), ('center', _i), ('max_workgroups', _i),
+                ('trace_capacity', _i), ('reserved', _i), ('early_exaggeration', _f), ('momentum_early', _f), ('momentum_late', _f),
+                ('learning_rate', _f), ('P', _vp), ('Y', _vp), ('V', _vp), ('G', _vp), ('workspace', _vp), ('workspace_bytes', _sz),
+                ('trace', _vp), ('status', _vp), ('grad_out', _vp), ('z_out', _vp)]
 
 
 # rovit_eval_conformal / rovit_eval_conformal_apply: limits, score kinds, the Philox stream word and the result blocks' layouts (the
