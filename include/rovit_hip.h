@@ -504,7 +504,14 @@ int rovit_wgrad_multi_ex(const void* const* dY, const int* ldy, const void* cons
 int rovit_wgrad_reduce(const float* ws, int splits, int N, int K, const float* gamma, const float* beta, const float* W,
                        float* dW, float* db, float* dgamma, float* dbeta, float* g_scratch, rovit_stream_t stream);
 /* softmax(q k^T * scale) v per (image, head); qkv bf16 (B*T, 3*H*64) = [q|k|v]; out bf16 (B*T, H*64);
- * lse2 (B,H,T) = log2 sum exp(scale q.k) */
+ * lse2 (B,H,T) = log2 sum exp(scale q.k); tokens 1 .. 208, head_dim 64.
+ * THE SCALE RULE of every attention entry: a call whose scale the kernel would not honour exactly is refused with ROVIT_ERR_SHAPE and a
+ * message naming the value, before anything is launched.
+ *   - the forwards (rovit_attention_fwd, _cls_fwd, _fwd_ragged, _cls_fwd_ragged) and rovit_attention_cls_bwd take any finite scale > 0
+ *     (they take the row maximum and mask padded keys on the unscaled scores: a maximum and a mask only for scale > 0);
+ *   - rovit_attention_bwd takes scale == 0.125f only: its kernel folds head_dim^-1/2 = 2^-3 into the exponent offset and the dV store
+ *     (exact in binary floating point), and with another value dQ and dK would come out multiplied by 0.125 / scale.
+ * The engine passes 0.125f everywhere; rovit_attention_relevance_step and the rollout kernels take no scale and use 1/8. */
 int rovit_attention_fwd(const void* qkv, void* out, float* lse2, int batch, int tokens, int heads, int head_dim, float scale,
                         rovit_stream_t stream);
 /* softmax(scale q k^T) as fp32 (B,H,T,T) from a saved qkv tensor -- explainability only */

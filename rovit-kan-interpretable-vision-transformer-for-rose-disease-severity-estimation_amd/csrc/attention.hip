@@ -911,6 +911,20 @@ int check_attn(int batch, int tokens, int heads, int head_dim) {
   return ROVIT_OK;
 }
 
+// The scale rule (include/rovit_hip.h).  Every forward takes the row maximum of the UNSCALED scores and masks padded keys with -inf
+// before the multiply by scale * log2(e): a maximum, and a mask, only for a finite scale > 0.
+int check_attn_scale(const char* what, float scale) {
+  ROVIT_CHECK_ARG(scale > 0.f && scale < INFINITY, ROVIT_ERR_SHAPE, "%s: scale must be finite and > 0 (got %g)", what, (double)scale);
+  return ROVIT_OK;
+}
+// attn_bwd_kernel folds scale = head_dim^-1/2 = 2^-3 into the exponent offset (lse + 3) and the x 8 of the dV store: with any other value
+// dQ and dK would come out multiplied by 0.125 / scale.
+int check_attn_scale_folded(const char* what, float scale) {
+  ROVIT_CHECK_ARG(scale == 0.125f, ROVIT_ERR_SHAPE, "%s: scale must be 0.125 = 64^-1/2, which the kernel folds in as 2^-3 (got %g)", what,
+                  (double)scale);
+  return ROVIT_OK;
+}
+
 // Explainability only (not on the training path): the softmax probabilities themselves, fp32 (B,H,T,T), from a saved
 // qkv tensor.  One wave per query row; lanes stride over the keys.
 __global__ __launch_bounds__(256) void attn_probs_kernel(const bf16* __restrict__ qkv, float* __restrict__ probs, int B, int T, int H,
@@ -1105,6 +1119,7 @@ extern "C" int rovit_attention_cls_fwd(const void* qkv, void* out, float* lse2, 
                                        rovit_stream_t stream) {
   ROVIT_CHECK_ARG(qkv && out, ROVIT_ERR_NULL, "attention_cls_fwd: null pointer");
   ROVIT_CHECK_ARG(batch > 0 && tokens > 0 && tokens <= TP && head_dim == HD && heads > 0, ROVIT_ERR_SHAPE, "attention_cls_fwd: unsupported shape");
+  if (int rc = check_attn_scale("attention_cls_fwd", scale)) return rc;
   ROVIT_CHECK_ARG(rovit_aligned16(qkv) && rovit_aligned16(out), ROVIT_ERR_ALIGN, "attention_cls_fwd: alignment");
   AttnArgs a{};
   a.qkv = (const bf16*)qkv; a.out = (bf16*)out; a.lse2 = lse2; a.T = tokens; a.H = heads; a.scale = scale;
@@ -1117,6 +1132,7 @@ extern "C" int rovit_attention_cls_bwd(const void* qkv, const void* out, const f
                                        int heads, int head_dim, float scale, rovit_stream_t stream) {
   ROVIT_CHECK_ARG(qkv && out && lse2 && dout && dqkv, ROVIT_ERR_NULL, "attention_cls_bwd: null pointer");
   ROVIT_CHECK_ARG(batch > 0 && tokens > 0 && tokens <= TP && head_dim == HD && heads > 0, ROVIT_ERR_SHAPE, "attention_cls_bwd: unsupported shape");
+  if (int rc = check_attn_scale("attention_cls_bwd", scale)) return rc;      // the rank-one kernel honours any such scale
   ROVIT_CHECK_ARG(rovit_aligned16(qkv) && rovit_aligned16(out) && rovit_aligned16(dout) && rovit_aligned16(dqkv), ROVIT_ERR_ALIGN,
                   "attention_cls_bwd: alignment");
   AttnArgs a{};
@@ -1133,6 +1149,7 @@ extern "C" int rovit_attention_fwd(const void* qkv, void* out, float* lse2, int 
   ROVIT_CHECK_ARG(qkv && out, ROVIT_ERR_NULL, "attention_fwd: null pointer");
   int rc = check_attn(batch, tokens, heads, head_dim);
   if (rc) return rc;
+  if ((rc = check_attn_scale("attention_fwd", scale))) return rc;
   ROVIT_CHECK_ARG(rovit_aligned16(qkv) && rovit_aligned16(out), ROVIT_ERR_ALIGN, "attention_fwd: alignment");
   AttnArgs a{};
   a.qkv = (const bf16*)qkv; a.out = (bf16*)out; a.lse2 = lse2; a.T = tokens; a.H = heads; a.scale = scale;
@@ -1172,6 +1189,7 @@ int rovit_attention_bwd_rows(const void* qkv, const void* out, const float* lse2
   ROVIT_CHECK_ARG(qkv && out && lse2 && dout && dqkv, ROVIT_ERR_NULL, "attention_bwd: null pointer");
   int rc = check_attn(batch, tokens, heads, head_dim);
   if (rc) return rc;
+  if ((rc = check_attn_scale_folded("attention_bwd", scale))) return rc;
   ROVIT_CHECK_ARG(rovit_aligned16(qkv) && rovit_aligned16(out) && rovit_aligned16(dout) && rovit_aligned16(dqkv), ROVIT_ERR_ALIGN,
                   "attention_bwd: alignment");
   AttnArgs a{};
@@ -1475,7 +1493,7 @@ int rovit_attention_cls_fwd_ragged_range(const void* qkv, void* out, float* lse2
 
 namespace {
 int check_ragged_attn(const char* what, const void* qkv, const void* out, const int* off_dev, const int* off_host, int n_seq, int heads,
-                      int head_dim, int* total_rows) {
+                      int head_dim, float scale, int* total_rows) {
   ROVIT_CHECK_ARG(qkv, ROVIT_ERR_NULL, "%s: null qkv", what);
   ROVIT_CHECK_ARG(out, ROVIT_ERR_NULL, "%s: null out", what);
   ROVIT_CHECK_ARG(off_dev, ROVIT_ERR_NULL, "%s: null seq_offsets_dev", what);
@@ -1483,6 +1501,7 @@ int check_ragged_attn(const char* what, const void* qkv, const void* out, const 
   if (rc) return rc;
   ROVIT_CHECK_ARG(heads > 0 && head_dim == HD && (long)n_seq * heads < (1L << 31), ROVIT_ERR_SHAPE,
                   "%s: unsupported heads %d / head_dim %d (head_dim must be %d)", what, heads, head_dim, HD);
+  ROVIT_CHECK_ARG(scale > 0.f && scale < INFINITY, ROVIT_ERR_SHAPE, "%s: scale must be finite and > 0 (got %g)", what, (double)scale);
   ROVIT_CHECK_ARG(rovit_aligned16(qkv) && rovit_aligned16(out), ROVIT_ERR_ALIGN, "%s: qkv and out must be 16-byte aligned", what);
   return ROVIT_OK;
 }
@@ -1492,7 +1511,7 @@ int check_ragged_attn(const char* what, const void* qkv, const void* out, const 
 extern "C" int rovit_attention_fwd_ragged(const void* qkv, void* out, float* lse2, const int* seq_offsets_dev, const int* seq_offsets_host,
                                           int n_seq, int heads, int head_dim, float scale, rovit_stream_t stream) {
   int total = 0;
-  int rc = check_ragged_attn("attention_fwd_ragged", qkv, out, seq_offsets_dev, seq_offsets_host, n_seq, heads, head_dim, &total);
+  int rc = check_ragged_attn("attention_fwd_ragged", qkv, out, seq_offsets_dev, seq_offsets_host, n_seq, heads, head_dim, scale, &total);
   if (rc) return rc;
   return rovit_attention_fwd_ragged_range(qkv, out, lse2, seq_offsets_dev, 0, n_seq, total, heads, scale, stream);
 }
@@ -1501,7 +1520,7 @@ extern "C" int rovit_attention_cls_fwd_ragged(const void* qkv, void* out, float*
                                               const int* seq_offsets_dev, const int* seq_offsets_host, int n_seq, int heads, int head_dim,
                                               float scale, rovit_stream_t stream) {
   int total = 0;
-  int rc = check_ragged_attn("attention_cls_fwd_ragged", qkv, out, seq_offsets_dev, seq_offsets_host, n_seq, heads, head_dim, &total);
+  int rc = check_ragged_attn("attention_cls_fwd_ragged", qkv, out, seq_offsets_dev, seq_offsets_host, n_seq, heads, head_dim, scale, &total);
   if (rc) return rc;
   ROVIT_CHECK_ARG(!x_rows == !x_cls, ROVIT_ERR_NULL, "attention_cls_fwd_ragged: x_rows and x_cls go together (both or neither)");
   return rovit_attention_cls_fwd_ragged_range(qkv, out, lse2, x_rows, x_cls, seq_offsets_dev, 0, n_seq, total, heads, scale, stream);

@@ -181,32 +181,43 @@ def attention_bwd_truth(qkv, dO_full, B):
     return q.grad
 
 
+def attention_bwd_heads(q, k, v, g, delta, lse, scale=0.125):
+    """attn_bwd on (..., T, 64) heads of any T: dQ, dK, dV from delta and lse (..., T), P / 8 and dS / 8 rounded to bf16 as MFMA operands.
+    The kernel's factor is 2^-3, folded into the exponent offset and the dV store; `scale` enters the exponent alone, as the kernel's
+    argument does (rovit_attention_bwd refuses any value but 1/8: dQ and dK would be 0.125 / scale times the truth)."""
+    ps = torch.exp2((q @ k.transpose(-2, -1)) * (scale * LOG2E) - (lse + 3.0).unsqueeze(-1)).float().double()     # an fp32 number: it underflows
+    dss = ps * (g @ v.transpose(-2, -1) - delta.unsqueeze(-1))
+    psb, dsb = bf(ps), bf(dss)
+    return dsb @ k, dsb.transpose(-2, -1) @ q, 8.0 * (psb.transpose(-2, -1) @ g)
+
+
 def attention_bwd_emulated(qkv, o, lse, dO_full, B):
     """attn_bwd: statistics from the forward's saved o and lse, P / 8 and dS / 8 rounded to bf16 as MFMA operands."""
     q, k, v = heads_of(qkv, B)
     g = dO_full.view(B, ROWS, HEADS, HD).transpose(1, 2)                                # (B,3,197,64)
     delta = (dO_full * o).view(B, ROWS, HEADS, HD).sum(-1).transpose(1, 2)              # (B,3,197)
-    ps = torch.exp2((q @ k.transpose(-2, -1)) * (0.125 * LOG2E) - (lse + 3.0).unsqueeze(-1))
-    dss = ps * (g @ v.transpose(-2, -1) - delta.unsqueeze(-1))
-    psb, dsb = bf(ps), bf(dss)
-    dv = 8.0 * (psb.transpose(-2, -1) @ g)
-    dk = dsb.transpose(-2, -1) @ q
-    dq = dsb @ k
+    dq, dk, dv = attention_bwd_heads(q, k, v, g, delta, lse)
     return torch.cat([rows_of(dq, B), rows_of(dk, B), rows_of(dv, B)], dim=1)
+
+
+def attention_cls_bwd_heads(q0, k, v, g, delta, lse, scale=0.125):
+    """attn_cls_bwd_kernel on (..., T, 64) keys and values of any T: q0, g (..., 64) the class token's query and output gradient, delta and
+    lse (...).  Nothing is rounded before the outputs; the kernel honours its scale argument."""
+    p = torch.exp2((k @ q0.unsqueeze(-1)).squeeze(-1) * (scale * LOG2E) - lse.unsqueeze(-1))          # (..., T)
+    ds = p * ((v @ g.unsqueeze(-1)).squeeze(-1) - delta.unsqueeze(-1))
+    dk = scale * ds.unsqueeze(-1) * q0.unsqueeze(-2)
+    dv = p.unsqueeze(-1) * g.unsqueeze(-2)
+    dq = torch.zeros_like(k)
+    dq[..., 0, :] = scale * (ds.unsqueeze(-1) * k).sum(-2)
+    return dq, dk, dv
 
 
 def attention_cls_bwd_emulated(qkv, o_cls, lse_cls, dO_cls, B):
     """attn_cls_bwd_kernel: the class token's query alone, fp32 probabilities; dQ of every other query is zero."""
     q, k, v = heads_of(qkv, B)
-    q0 = q[:, :, 0]                                                                      # (B,3,64)
     g = dO_cls.view(B, HEADS, HD)
     delta = (dO_cls * o_cls).view(B, HEADS, HD).sum(-1)                                  # (B,3)
-    p = torch.exp2((k @ q0.unsqueeze(-1)).squeeze(-1) * (0.125 * LOG2E) - lse_cls.view(B, HEADS, 1))   # (B,3,197)
-    ds = p * ((v @ g.unsqueeze(-1)).squeeze(-1) - delta.unsqueeze(-1))
-    dk = 0.125 * ds.unsqueeze(-1) * q0.unsqueeze(2)
-    dv = p.unsqueeze(-1) * g.unsqueeze(2)
-    dq = torch.zeros_like(k)
-    dq[:, :, 0] = 0.125 * (ds.unsqueeze(-1) * k).sum(2)
+    dq, dk, dv = attention_cls_bwd_heads(q[:, :, 0], k, v, g, delta, lse_cls.view(B, HEADS))
     return torch.cat([rows_of(dq, B), rows_of(dk, B), rows_of(dv, B)], dim=1)
 
 
