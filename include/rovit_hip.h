@@ -1706,6 +1706,80 @@ int rovit_tsne_affinities(const rovit_tsne_affinity* p, rovit_stream_t stream);
 int rovit_tsne_run(const rovit_tsne_descent* p, rovit_stream_t stream);
 int rovit_tsne_random_init(unsigned long long seed, float* Y, int n, rovit_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * k-means of the feature space (kmeans.hip): k-means++ seeding, Lloyd iterations with the exact stopping rule, the per-cluster score
+ * card and the cluster x class contingency table.  Rows are fp32 (n, embed) row-major, embed a multiple of 32 in 32..256,
+ * 1 <= n <= ROVIT_KMEANS_MAX_ROWS, 1 <= k <= ROVIT_KMEANS_MAX_K.
+ * Rows.  Validity is rovit_knn_build's: a row with a non-finite feature or squared norm (with ROVIT_KNN_COSINE also a zero row) is
+ * absent: label -1, distance and second distance +inf, silhouette 0, counted in [_BAD_ROWS], and it enters no sum and no pick.  With
+ * _COSINE every kernel works on the unit rows x^ = x / sqrt(|x|^2) (element by element, as rovit_knn_build forms them; `normalized`).
+ * Distance of a row x to a centroid c: the neighbours' definition.  _L2: max(0, (|x|^2 + |c|^2) - 2 x.c); _COSINE: max(0, 1 - x^.c) with
+ * c of unit length (spherical k-means).  Every term fp32, x.c and the squared norms fma chains in ascending feature index from 0: on the
+ * vector units in the seeding kernel, on v_mfma_f32_32x32x2_f32 in the assignment kernel, the same bits.
+ * Order.  A row belongs to the centroid with the smallest key (bits(d) << 32) | c, an unsigned 64-bit integer: ties go to the lower
+ * cluster index, only integer compares decide.  The second smallest key gives second_distance (+inf with k = 1).
+ * Seeding (Arthur & Vassilvitskii 2007, one trial per seed), exact in integers.  Seed j of restart r draws r64 = (w.x << 32) | w.y from
+ * Philox4x32-10(key = seed, counter = (j, r, ROVIT_KMEANS_STREAM, 0)).  Seed 0 is the floor(r64 * n_valid / 2^64)-th valid row in
+ * ascending index.  Seed j > 0: d_i = the smallest distance of row i to the seeds chosen so far (fp32), dmax = max_i d_i = m * 2^e with
+ * m in [1/2, 1), w_i = floor(d_i * 2^(40 - e)) (exact, below 2^40), W = sum w_i, t = floor(r64 * W / 2^64), and the seed is the smallest i
+ * with sum_{i' <= i} w_i' > t.  W = 0 (every valid row coincides with a seed): w_i = 1 for every valid row, counted in [_W0_EVENTS].
+ * More seeds than valid rows: [_SHORT] = 1 (and -1 seeds when there is no valid row at all).  The chosen index is read from device
+ * memory by the next launch; three launches per seed (distances and maximum; weights and block sums; the pick), two for seed 0.
+ * tap (m, n) or NULL: row j >= 1 receives the d_i that seed j was drawn from.
+ * Lloyd iteration it = 1 .. max_iter: assign (labels, both distances, the integer count of rows whose label changed); when no label
+ * changed [_DONE] = 1, [_N_ITER] = it and every later launch of the run returns at once; otherwise update: the rows are brought into
+ * (cluster, ascending row index) order by a two-level counting sort (per 256-row block counts, a scan per cluster, a scatter; integers
+ * only), every cluster's members are cut into segments of ROVIT_KMEANS_SEGMENT, a segment is summed in fp64 in member order, the
+ * segments are added in ascending order, the sum is divided by the count and rounded once to fp32.  With _COSINE the fp64 mean of the
+ * unit rows is divided by its fp64 length (sum of squares in ascending feature index) and rounded once.  The order is a function of
+ * (n, labels) alone.  An empty cluster keeps its centroid ([_EMPTY_EVENTS] counts them over the run), and so does a _COSINE cluster
+ * whose mean has zero length ([_ZERO_MEANS]); nothing is relocated.  No tolerance: the stopping rule is the exact one.  Without
+ * convergence [_N_ITER] = max_iter.  All launches are enqueued at once; nothing waits for the host.
+ * Final pass: one more assign against the final centroids, the same sort, and per cluster c into the status block:
+ *   counts; medoids: the member with the smallest key (bits(d) << 32) | row (-1 for an empty cluster); inertia: the fp64 sum of the
+ *   members' fp32 distances (per 1024-member segment: member s of the segment belongs to thread s % 256, which adds its members in
+ *   ascending order; the threads are added by the fixed tree of common.h; segments in ascending order); silhouette sums likewise;
+ *   radii: the largest member distance.  [_EMPTY] = the number of empty clusters.
+ * Silhouette (simplified) of a row: (b - a) / max(a, b) in fp32 with a, b = sqrtf of the two distances with _L2, the distances with
+ * _COSINE; 0 when k = 1, when max(a, b) = 0 and for an absent row.
+ * status: ROVIT_KMEANS_WORDS + 5 k 8-byte words: the words below, then k int64 counts, k int64 medoids, k fp64 inertias, k fp64
+ * silhouette sums, k fp64 radii (each the fp32 value).  rovit_kmeans_seed fills only the first ROVIT_KMEANS_WORDS.
+ * rovit_kmeans_seed: m seeds (1 <= m <= ROVIT_KMEANS_MAX_K) into seeds (m) and their rows (unit rows with _COSINE) into centroids (m, embed).
+ * rovit_kmeans_run: centroids (k, embed) hold the initial centroids on entry (unit length with _COSINE) and the final ones on exit.
+ * rovit_kmeans_assign: the assignment alone of n rows against k given centroids (out-of-sample rows).
+ * rovit_kmeans_contingency: table (k * num_classes + 1 int64): table[c * num_classes + y] counts the rows with cluster c and class y by
+ * integer atomics; a row whose cluster is outside [0, k) or whose class is outside [0, num_classes) is counted in the last word.
+ * No floating-point atomic anywhere; work items are walked with a stride of the grid: every output is bit-identical from run to run
+ * and for every max_workgroups.  workspace: rovit_kmeans_workspace_bytes(n, embed, k) bytes (0 outside the limits), 16-byte aligned.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define ROVIT_KMEANS_MAX_ROWS (1 << 20)
+#define ROVIT_KMEANS_MAX_K 256
+#define ROVIT_KMEANS_MAX_ITER 100000
+#define ROVIT_KMEANS_SEGMENT 1024
+#define ROVIT_KMEANS_STREAM 0x4B4D6E73u   /* "KMns" */
+enum { ROVIT_KMEANS_N = 0, ROVIT_KMEANS_N_VALID = 1, ROVIT_KMEANS_BAD_ROWS = 2, ROVIT_KMEANS_N_ITER = 3, ROVIT_KMEANS_DONE = 4,
+       ROVIT_KMEANS_EMPTY = 5, ROVIT_KMEANS_EMPTY_EVENTS = 6, ROVIT_KMEANS_ZERO_MEANS = 7, ROVIT_KMEANS_W0_EVENTS = 8,
+       ROVIT_KMEANS_SHORT = 9, ROVIT_KMEANS_CHANGED = 10 /* two words */, ROVIT_KMEANS_WORDS = 16 };
+typedef struct rovit_kmeans_problem {
+  int n, embed, k, metric, max_iter, max_workgroups, restart, m;
+  unsigned long long seed;
+  const float* features;             /* (n, embed) */
+  float* normalized;                 /* (n, embed) scratch with ROVIT_KNN_COSINE, else NULL */
+  float* centroids;                  /* (k, embed); rovit_kmeans_seed: (m, embed) */
+  int* seeds;                        /* (m); rovit_kmeans_seed only */
+  float* tap;                        /* (m, n) or NULL; rovit_kmeans_seed only */
+  int* labels;                       /* (n) */
+  float* distance; float* second_distance; float* silhouette;   /* (n) each */
+  void* workspace;
+  size_t workspace_bytes;
+  void* status;
+} rovit_kmeans_problem;
+size_t rovit_kmeans_workspace_bytes(int n, int embed, int k);
+int rovit_kmeans_seed(const rovit_kmeans_problem* p, rovit_stream_t stream);
+int rovit_kmeans_run(const rovit_kmeans_problem* p, rovit_stream_t stream);
+int rovit_kmeans_assign(const rovit_kmeans_problem* p, rovit_stream_t stream);
+int rovit_kmeans_contingency(const int* clusters, const int* classes, int n, int k, int num_classes, long long* table, rovit_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -55,6 +55,8 @@ void rovit_set_error(const char* fmt, ...) {
 // rovit_eval_selective and rovit_ood_metrics keep their argument lists and their launches.)
 // (rovit_tsne_workspace_bytes, rovit_tsne_affinities, rovit_tsne_run and rovit_tsne_random_init were added at 440 the same way: exact t-SNE
 // of the feature space, tsne.hip.)
+// (rovit_kmeans_workspace_bytes, rovit_kmeans_seed, rovit_kmeans_run, rovit_kmeans_assign and rovit_kmeans_contingency were added at 440
+// the same way: k-means of the feature space, kmeans.hip.)
 extern "C" int rovit_version(void) { return 440; }
 extern "C" const char* rovit_last_error_string(void) { return g_err; }
 

@@ -340,6 +340,14 @@ class RoViTKAN(nn.Module):
         tsne = embedding.TSNE(**tsne_kwargs)
         return {'map': tsne.fit_transform(feats), 'features': feats, 'kl_divergence': tsne.kl_trace_[-1]}
 
+    def cluster_features(self, x_or_loader, n_clusters: int, labels=None, chunk: int = 256, **kw) -> Dict:
+        """Extension (not in the reference): k-means (k-means++ seeding) of this model's backbone features over images, gathered as
+        ``fit_feature_index`` gathers them.  ``kw`` go to ``rovit_hip.clustering.KMeans``.  Returns the fitted object under ``kmeans``,
+        ``features``, ``labels``, ``distances``, ``cluster_centers``, ``medoids``, ``counts``, ``silhouette``, and with class ``labels``
+        the cluster-by-class ``score_card`` (purity, NMI, ARI: a label audit that needs no trained head)."""
+        from rovit_hip import clustering
+        return clustering.cluster_model_features(self, x_or_loader, n_clusters, labels, chunk, **kw)
+
     def nearest_examples(self, x: torch.Tensor, index, k: int = 5) -> Dict[str, torch.Tensor]:
         """Extension (not in the reference): explanation by example.  One forward, then ``index.search(features, k)``: the ``k`` nearest
         recorded rows of every image with their labels and severities, the neighbours' vote, and beside it the heads' own ``class``

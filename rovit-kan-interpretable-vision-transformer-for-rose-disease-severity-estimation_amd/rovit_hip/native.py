@@ -184,6 +184,11 @@ SIGNATURES = {
     'rovit_tsne_affinities': (_i, [_vp, _vp]),
     'rovit_tsne_run': (_i, [_vp, _vp]),
     'rovit_tsne_random_init': (_i, [C.c_ulonglong, _vp, _i, _vp]),
+    'rovit_kmeans_workspace_bytes': (_sz, [_i, _i, _i]),
+    'rovit_kmeans_seed': (_i, [_vp, _vp]),
+    'rovit_kmeans_run': (_i, [_vp, _vp]),
+    'rovit_kmeans_assign': (_i, [_vp, _vp]),
+    'rovit_kmeans_contingency': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
 }
 
 
@@ -474,6 +479,20 @@ class TsneDescent(C.Structure):
                 ('trace_capacity', _i), ('reserved', _i), ('early_exaggeration', _f), ('momentum_early', _f), ('momentum_late', _f),
                 ('learning_rate', _f), ('P', _vp), ('Y', _vp), ('V', _vp), ('G', _vp), ('workspace', _vp), ('workspace_bytes', _sz),
                 ('trace', _vp), ('status', _vp), ('grad_out', _vp), ('z_out', _vp)]
+
+
+# rovit_kmeans_*: limits, the Philox stream word ("KMns") and the status block (the ROVIT_KMEANS_* names of include/rovit_hip.h)
+KMEANS_MAX_ROWS, KMEANS_MAX_K, KMEANS_MAX_ITER, KMEANS_SEGMENT, KMEANS_STREAM = 1 << 20, 256, 100000, 1024, 0x4B4D6E73
+(KMEANS_N, KMEANS_N_VALID, KMEANS_BAD_ROWS, KMEANS_N_ITER, KMEANS_DONE, KMEANS_EMPTY, KMEANS_EMPTY_EVENTS, KMEANS_ZERO_MEANS, KMEANS_W0_EVENTS,
+ KMEANS_SHORT, KMEANS_CHANGED, KMEANS_WORDS) = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 16
+
+
+class KMeansProblem(C.Structure):
+    """``rovit_kmeans_problem`` of include/rovit_hip.h, field for field."""
+    _fields_ = [('n', _i), ('embed', _i), ('k', _i), ('metric', _i), ('max_iter', _i), ('max_workgroups', _i), ('restart', _i), ('m', _i),
+                ('seed', C.c_ulonglong), ('features', _vp), ('normalized', _vp), ('centroids', _vp), ('seeds', _vp), ('tap', _vp),
+                ('labels', _vp), ('distance', _vp), ('second_distance', _vp), ('silhouette', _vp), ('workspace', _vp),
+                ('workspace_bytes', _sz), ('status', _vp)]
 
 
 # rovit_eval_conformal / rovit_eval_conformal_apply: limits, score kinds, the Philox stream word and the result blocks' layouts (the
