@@ -41,6 +41,13 @@ bool rovit_set_max_lds(const void* fn, size_t bytes);
 static inline bool rovit_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static inline bool rovit_aligned(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }   // a: a power of two
 constexpr size_t rovit_up16(size_t v) { return (v + 15) & ~(size_t)15; }          // workspace sections start on 16 bytes
+// the grid of a kernel that walks `items` work items with a stride of the grid: a workgroup per item, at most max_workgroups of them
+// when that is positive (a descriptor's 0 means no cap), and never an empty grid
+static inline dim3 rovit_grid(long long items, int max_workgroups) {
+  const long long cap = max_workgroups > 0 ? max_workgroups : (1ll << 30);
+  const long long g = items < cap ? items : cap;
+  return dim3((unsigned)(g < 1 ? 1 : g));
+}
 
 
 // ---- developer knobs (A/B timing, ablations) ------------------------------------------------------------

@@ -3,8 +3,9 @@
 // two score populations (rovit_ood_metrics).  Lee et al., NeurIPS 2018; Ren et al., 2021.  The reference has no counterpart: its heads
 // read outputs['features'] and nothing asks how far a feature row lies from the training features.
 //
-// Everything matrix-shaped runs on the exact-fp32 matrix instruction (v_mfma_f32_32x32x2_f32: a k-ordered fp32 fma chain, as vit_f32.hip
-// uses it): the whitening of a near-singular covariance amplifies operand error by sqrt(cond), so bf16 operands are out.
+// Everything matrix-shaped runs on the exact-fp32 matrix instruction (v_mfma_f32_32x32x2_f32: a k-ordered fp32 fma chain; the tiles
+// are those of feature_tiles.h, which laplace.hip shares): the whitening of a near-singular covariance amplifies operand error by
+// sqrt(cond), so bf16 operands are out.
 //
 // rovit_density_moments, four kernels on the caller's stream; a chunk is R = density_chunk_rows(n) consecutive rows (a function of n alone):
 //   dens_sums_kernel     per chunk: each row's class (-1 bad label, -2 non-finite feature) into the workspace, the per-class column sums
@@ -23,12 +24,13 @@
 //   are sorted (sort_rank.hip) and the four counts of every row come from binary searches in the two sorted key arrays.
 // Work items are walked with a stride of the grid, and no item's result depends on which workgroup computes it.  No floating-point atomics.
 #include "common.h"
+#include "feature_tiles.h"
 #include "rank_count.h"
 #include "sort_device.h"
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
 namespace {
+
+using namespace ftile;                  // tile_dot, acc_row, upper_tiles, wave_tiles, gram_slab, store_acc_tile, fold_element
 
 constexpr int NT = 256;                 // threads per workgroup
 constexpr int SLAB = 32;                // rows of one centred LDS slab of the scatter pass
@@ -39,7 +41,6 @@ static_assert(SCORE_ROWS == 64, "two row tiles of 32 per workgroup");
 static_assert(NT == RANK_NT, "rank_stage_tile strides by RANK_NT");
 
 inline int density_chunk_rows(int n) { return ROVIT_DENSITY_CHUNK_ROWS * ((n + ROVIT_DENSITY_CHUNK_ROWS * MAX_CHUNKS - 1) / (ROVIT_DENSITY_CHUNK_ROWS * MAX_CHUNKS)); }
-inline int upper_tiles(int E) { const int T = E / 32; return T * (T + 1) / 2; }
 
 // ---- moments -------------------------------------------------------------------------------------------------------------------------
 
@@ -52,7 +53,7 @@ inline MomLayout mom_layout(int n, int E, int C) {
   l.ccnt = l.csum + rovit_up16(chunks * C * E * 8);
   l.mean32 = l.ccnt + rovit_up16(chunks * (C + 2) * 8);
   l.part = l.mean32 + rovit_up16((size_t)C * E * 4);
-  l.total = l.part + rovit_up16(chunks * upper_tiles(E) * 1024 * 4);
+  l.total = l.part + rovit_up16(chunks * upper_tiles(E / 32) * 1024 * 4);
   return l;
 }
 
@@ -147,25 +148,19 @@ __global__ __launch_bounds__(NT) void dens_means_kernel(const MomArgs a) {
   }
 }
 
-// tile q of the upper triangle, row-major: (i, j), i <= j < T
-__device__ __forceinline__ void upper_tile(int q, int T, int& i, int& j) {
-  i = 0;
-  while (q >= T - i) { q -= T - i; ++i; }
-  j = i + q;
-}
+struct PlainRow {               // gram_slab's B operand: the row itself, whichever row
+  __device__ __forceinline__ PlainRow operator()(int) const { return *this; }
+  __device__ __forceinline__ float operator()(float x) const { return x; }
+};
 
 template <int T>
 __global__ __launch_bounds__(NT) void dens_scatter_kernel(const MomArgs a) {
-  constexpr int E = 32 * T, TILES = T * (T + 1) / 2, NQ = (TILES + 3) / 4;
+  constexpr int E = 32 * T, TILES = upper_tiles(T), NQ = (TILES + 3) / 4;
   __shared__ __attribute__((aligned(16))) float Xs[SLAB * E];
-  const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, lh = lane >> 5, n = a.n;
+  const int tid = threadIdx.x, n = a.n;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   int ti[NQ], tj[NQ];
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) {
-    ti[q] = tj[q] = 0;
-    if (wv + 4 * q < TILES) upper_tile(wv + 4 * q, T, ti[q], tj[q]);
-  }
+  wave_tiles<T>(wv, ti, tj);
   for (int w = blockIdx.x; w < a.chunks; w += gridDim.x) {
     f32x16 acc[NQ];
 #pragma unroll
@@ -190,36 +185,23 @@ __global__ __launch_bounds__(NT) void dens_scatter_kernel(const MomArgs a) {
         *reinterpret_cast<float4*>(Xs + row * E + 4 * c4) = v;
       }
       __syncthreads();
-#pragma unroll 4
-      for (int k2 = 0; k2 < SLAB / 2; ++k2) {
-        const float* xr = Xs + (2 * k2 + lh) * E + l31;         // row k, column l31 of a tile: conflict-free
-#pragma unroll
-        for (int q = 0; q < NQ; ++q)
-          if (wv + 4 * q < TILES) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(xr[32 * ti[q]], xr[32 * tj[q]], acc[q], 0, 0, 0);
-      }
+      gram_slab<T>(acc, Xs, wv, ti, tj, PlainRow());            // k = the rows of the chunk in order
     }
-    // accumulator tile: column = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
 #pragma unroll
     for (int q = 0; q < NQ; ++q)
-      if (wv + 4 * q < TILES) {
-        float* out = a.part + ((size_t)w * TILES + (wv + 4 * q)) * 1024;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) out[((r & 3) + 8 * (r >> 2) + 4 * lh) * 32 + l31] = acc[q][r];
-      }
+      if (wv + 4 * q < TILES) store_acc_tile(a.part + ((size_t)w * TILES + (wv + 4 * q)) * 1024, acc[q]);
   }
 }
 
 __global__ __launch_bounds__(NT) void dens_fold_kernel(const MomArgs a) {
-  const int E = a.E, T = E / 32, tiles = T * (T + 1) / 2, items = tiles * 4;
+  const int E = a.E, T = E / 32, tiles = upper_tiles(T), items = tiles * 4;
   double* S = (double*)a.result + ROVIT_DENSITY_HEADER + (size_t)(a.C + 1) * E;
   for (int w = blockIdx.x; w < items; w += gridDim.x) {
-    const int q = w >> 2, el = (w & 3) * NT + threadIdx.x, m = el >> 5, nn = el & 31;
-    int i, j;
-    upper_tile(q, T, i, j);
-    if (i == j && m > nn) continue;                             // the diagonal tiles' lower half is the mirror of their upper half
+    const int q = w >> 2, el = (w & 3) * NT + threadIdx.x;
+    int ra, rb;
+    if (fold_element(q, el, T, ra, rb)) continue;               // the diagonal tiles' lower half is the mirror of their upper half
     double s = 0.0;
     for (int c = 0; c < a.chunks; ++c) s += (double)a.part[((size_t)c * tiles + q) * 1024 + el];
-    const int ra = 32 * i + m, rb = 32 * j + nn;
     S[(size_t)ra * E + rb] = s;
     S[(size_t)rb * E + ra] = s;
   }
@@ -265,20 +247,13 @@ __global__ __launch_bounds__(NT) void dens_score_kernel(const rovit_density_scor
       f32x16 acc;
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-      const float* wrow = Ws + (mat * 32 + l31) * ST + 4 * lh;   // A[m = a][k]: lane half h holds k = kk + 4h + s in step s
+      const float* wrow = Ws + (mat * 32 + l31) * ST + 4 * lh;   // A[m = a][k]: plain rows, lane half h holds k = kk + 4h + s in step s
       const float* frow = Fs + (rt * 32 + l31) * ST + 4 * lh;    // B[k][n = row]
-      for (int kk = 0; kk < kend; kk += 8) {
-        const float4 w4 = *reinterpret_cast<const float4*>(wrow + kk);
-        const float4 f4 = *reinterpret_cast<const float4*>(frow + kk);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w4.x, f4.x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w4.y, f4.y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w4.z, f4.z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w4.w, f4.w, acc, 0, 0, 0);
-      }
-      // lane (l31, h) holds z[row l31][a0 + (r & 3) + 8 (r >> 2) + 4 h]
+      acc = tile_dot(acc, wrow, frow, kend);                       // a run-time bound: the columns up to the diagonal tile
+      // lane (l31, h) holds z[row l31][a0 + acc_row(r, h)]
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int ai = a0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        const int ai = a0 + acc_row(r, lh);
         const float z = acc[r];
 #pragma unroll
         for (int c = 0; c < MAXC; ++c)
@@ -481,8 +456,7 @@ extern "C" int rovit_density_moments(const rovit_density_fit* p, rovit_stream_t 
   a.part = (float*)(ws + l.part);
   a.result = p->result;
   hipStream_t s = (hipStream_t)stream;
-  const long long cap = p->max_workgroups > 0 ? p->max_workgroups : (1ll << 30);
-  auto grid = [&](long long items) { return dim3((unsigned)(items < cap ? items : cap)); };
+  auto grid = [&](long long items) { return rovit_grid(items, p->max_workgroups); };
   hipLaunchKernelGGL(dens_sums_kernel, grid(a.chunks), dim3(NT), 0, s, a);
   ROVIT_CHECK_LAUNCH("dens_sums_kernel");
   hipLaunchKernelGGL(dens_means_kernel, dim3(1), dim3(NT), 0, s, a);
@@ -498,7 +472,7 @@ extern "C" int rovit_density_moments(const rovit_density_fit* p, rovit_stream_t 
     default: launch_scatter<8>(grid(a.chunks), s, a); break;
   }
   ROVIT_CHECK_LAUNCH("dens_scatter_kernel");
-  hipLaunchKernelGGL(dens_fold_kernel, grid(4ll * upper_tiles(E)), dim3(NT), 0, s, a);
+  hipLaunchKernelGGL(dens_fold_kernel, grid(4ll * upper_tiles(E / 32)), dim3(NT), 0, s, a);
   ROVIT_CHECK_LAUNCH("dens_fold_kernel");
   return ROVIT_OK;
 }
@@ -526,8 +500,7 @@ extern "C" int rovit_density_score(const rovit_density_scores* p, rovit_stream_t
   const size_t lds = score_lds_bytes(p->embed, p->num_classes);
   ROVIT_CHECK_ARG(rovit_set_max_lds((const void*)dens_score_kernel, lds), ROVIT_ERR_LAUNCH, "%s: cannot raise the LDS limit", who);
   const long long tiles = ((long long)p->batch + SCORE_ROWS - 1) / SCORE_ROWS;
-  const long long cap = p->max_workgroups > 0 ? p->max_workgroups : (1ll << 30);
-  hipLaunchKernelGGL(dens_score_kernel, dim3((unsigned)(tiles < cap ? tiles : cap)), dim3(NT), lds, (hipStream_t)stream, *p);
+  hipLaunchKernelGGL(dens_score_kernel, rovit_grid(tiles, p->max_workgroups), dim3(NT), lds, (hipStream_t)stream, *p);
   ROVIT_CHECK_LAUNCH("dens_score_kernel");
   return ROVIT_OK;
 }
@@ -600,8 +573,7 @@ extern "C" int rovit_ood_metrics_ex(const rovit_ood* p, int method, void* rank_w
     rovit_set_error("%s: hipMemsetAsync failed", who);
     return ROVIT_ERR_LAUNCH;
   }
-  const long long cap = p->max_workgroups > 0 ? p->max_workgroups : (1ll << 30);
-  auto grid = [&](long long items) { return dim3((unsigned)(items < cap ? items : cap)); };
+  auto grid = [&](long long items) { return rovit_grid(items, p->max_workgroups); };
   const int ntiles = (a.n_in + RANK_RT - 1) / RANK_RT + (a.n_out + RANK_RT - 1) / RANK_RT;
   // split the j range until about 1024 workgroups exist; the counts are integers, so the split changes nothing
   int splits = (1024 + a.chunks - 1) / a.chunks;

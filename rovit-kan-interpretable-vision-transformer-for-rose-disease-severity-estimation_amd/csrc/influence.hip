@@ -16,12 +16,12 @@
 //                      below the one rounding to fp32.)  A non-finite entry of u makes the norm non-finite: the row is then zeroed again.
 //   inf_search_kernel  a work item = (query tile of 64 rows, reference split).  A 64 x 640 fp32 query tile is the whole LDS of a CU, so the
 //                      dim is walked in slabs of 64 columns: the query slab and the slab of one 64-row reference tile sit in LDS in the
-//                      (f0 f2 f4 f6 | f1 f3 f5 f7) order of neighbors.hip, the next slab's loads are in flight in registers while this
+//                      (f0 f2 f4 f6 | f1 f3 f5 f7) order of store_unit (feature_tiles.h), the next slab's loads are in flight in registers while this
 //                      slab's products run, and wave (qt, rt) keeps ONE accumulator tile over all slabs of a reference tile: a k-ordered
 //                      fp32 fma chain per (query, row), the queries on the lane index.  BOTH ends are kept in one pass: a lane has two
 //                      ascending key lists of KB keys in registers, proponents under the key (~o << 32) | j and opponents under
 //                      (o << 32) | j, o the orderable bits of the score with -0 made +0.  The four lists of a query and end meet in LDS,
-//                      are ranked as in knn_search_kernel, and the KB smallest go to the workspace (B, 2, splits, KB).
+//                      are ranked by merge_four (topk_device.h), and the KB smallest go to the workspace (B, 2, splits, KB).
 //   inf_merge_kernel   a wave per (query, end): the splits' lists to LDS, every key with a position below k ranked by binary searches
 //                      in the other lists, the k smallest decoded; labels and severities gathered.
 // Resource usage (hipcc -Rpass-analysis=kernel-resource-usage, gfx950), VGPRs + AGPRs: inf_search_kernel<32> 231 + 16 with both ends in
@@ -29,15 +29,15 @@
 // Work items are walked with a stride of the grid; no floating-point atomic; no result depends on which workgroup computes it, on the
 // number of reference splits, or on how the rows were split into embed calls (a row's outputs are a function of that row alone).
 #include "common.h"
+#include "feature_tiles.h"
 #include "laplace_device.h"
 #include "topk_device.h"
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
 namespace {
 
+using namespace ftile;                           // tile_dot, acc_row, store_unit
 using namespace laplace;                         // NT, MAXC, ROWS, lap_hidden, lap_stage_features
-using namespace topk;                            // u64, EMPTY, keys_below, list_insert, store_unit
+using namespace topk;                            // u64, EMPTY, key_of, keys_below, list_insert, merge_four, Plan, plan_of
 
 // ---- embed -----------------------------------------------------------------------------------------------------------------------------
 
@@ -141,7 +141,7 @@ __global__ __launch_bounds__(NT) void inf_embed_kernel(const rovit_influence_row
     double nrm = 0.0;
     const int row = r0 + rt * 32 + l31;                         // this lane's row
     const float* frow = As + (rt * 32 + l31) * SA + 4 * lh;     // B[k][n = row]
-    const float* wrow = Ws + (th * 32 + l31) * SA + 4 * lh;     // A[m = t][k]
+    const float* wrow = Ws + (th * 32 + l31) * SA + 4 * lh;     // A[m = t][k]: plain rows, lane half h holds k = kk + 4 h + s in step s
     for (int cb = 0; cb < C; ++cb) {
       for (int at0 = 0; at0 < TP; at0 += 2) {
         const int at = at0 + th;                                // this wave's tile of class block cb
@@ -165,17 +165,10 @@ __global__ __launch_bounds__(NT) void inf_embed_kernel(const rovit_influence_row
             __syncthreads();
             if (live) {
               const int kend = c == cb ? 32 * at + 32 : P;
-              for (int kk = 0; kk < kend; kk += 8) {
-                const float4 w4 = *reinterpret_cast<const float4*>(wrow + kk);
-                const float4 f4 = *reinterpret_cast<const float4*>(frow + kk);
-                acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(w4.x, f4.x, acc[c], 0, 0, 0);
-                acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(w4.y, f4.y, acc[c], 0, 0, 0);
-                acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(w4.z, f4.z, acc[c], 0, 0, 0);
-                acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(w4.w, f4.w, acc[c], 0, 0, 0);
-              }
+              acc[c] = tile_dot(acc[c], wrow, frow, kend);
             }
           }
-        // lane (l31, h) holds z_c[row l31][t = 32 at + (r & 3) + 8 (r >> 2) + 4 h] of every c <= cb
+        // lane (l31, h) holds z_c[row l31][t = 32 at + acc_row(r, h)] of every c <= cb
         if (live) {
           float u[16];
 #pragma unroll
@@ -238,28 +231,8 @@ constexpr int RT = 64;                           // reference rows of an LDS til
 constexpr int KS = 64;                           // columns of a slab
 constexpr int SST = KS + 4;                      // row stride of a slab in LDS
 constexpr int MAXK = ROVIT_INFLUENCE_MAX_K;
-constexpr int MAX_SPLITS = 64;
-constexpr int TARGET_ITEMS = 512;                // two work items per CU: the splits are chosen to reach it
 constexpr int UNITS = (QT + RT) * (KS / 8) / NT; // units of 8 columns a thread moves per slab
-static_assert(QT == 64 && RT == 64 && UNITS == 4, "2 x 2 sub-tiles of 32 per workgroup, one per wave");
-
-inline int bucket_of(int k) { return k <= 8 ? 8 : (k <= 16 ? 16 : 32); }
-
-struct Plan { int qtiles, rtiles, splits, tps, kb; };
-inline Plan plan_of(int B, int n, int k, int max_splits) {
-  Plan p;
-  p.qtiles = (B + QT - 1) / QT;
-  p.rtiles = (n + RT - 1) / RT;
-  p.kb = bucket_of(k);
-  long long s = (TARGET_ITEMS + p.qtiles - 1) / p.qtiles;
-  s = s < 1 ? 1 : s;
-  s = s > MAX_SPLITS ? MAX_SPLITS : s;
-  s = (max_splits > 0 && s > max_splits) ? max_splits : s;
-  s = s > p.rtiles ? p.rtiles : s;
-  p.tps = (p.rtiles + (int)s - 1) / (int)s;
-  p.splits = (p.rtiles + p.tps - 1) / p.tps;      // never more than without the cap: the default workspace serves every cap
-  return p;
-}
+static_assert(QT == 64 && RT == 64 && UNITS == 4, "2 x 2 sub-tiles of 32 per workgroup, one per wave; plan_of's tiles");
 
 inline bool search_limits_ok(int B, int n, int dim, int k) {
   return B >= 1 && n >= 1 && n <= ROVIT_KAN_STATS_MAX_ROWS && dim >= 32 && dim <= ROVIT_INFLUENCE_MAX_DIM && dim % 32 == 0 && k >= 1 && k <= MAXK;
@@ -281,38 +254,6 @@ struct SearchArgs {
 inline size_t search_lds_bytes(int kb) {
   const size_t stage = ((size_t)(QT + RT) * SST + 2 * RT) * 4, merge = (size_t)QT * 4 * kb * 8;
   return stage > merge ? stage : merge;
-}
-
-// the four lists of every query of the tile (two lane halves, two waves) meet in Ms; every key's rank among them is its index in its own
-// list plus a binary search in the three others, and the KB smallest go to out (B, 2, splits, KB)
-template <int KB>
-__device__ __forceinline__ void merge_four(const u64 (&lst)[KB], u64* Ms, u64* keys, int end, int q0, int B, int splits, int sp, int slot) {
-  const int tid = threadIdx.x;
-  __syncthreads();                                               // Ms lies over the staging buffers and the other end's lists
-  {
-    u64* mine = Ms + slot * KB;
-#pragma unroll
-    for (int i = 0; i < KB; ++i) mine[i] = lst[i];
-  }
-  __syncthreads();
-  const int ql = tid >> 2, li = tid & 3, g = q0 + ql;
-  if (g < B) {
-    const u64* base = Ms + ql * 4 * KB;
-    u64* out = keys + (((size_t)g * 2 + end) * splits + sp) * KB;
-    for (int i = 0; i < KB; ++i) {
-      const u64 c = base[li * KB + i];
-      if (c == EMPTY) break;
-      int rank = i;
-      for (int o = 0; o < 4; ++o)
-        if (o != li) rank += keys_below(base + o * KB, KB, c);
-      if (rank < KB) out[rank] = c;
-    }
-    if (li == 0) {
-      int real = 0;
-      for (int o = 0; o < 4; ++o) real += keys_below(base + o * KB, KB, EMPTY);
-      for (int s = real; s < KB; ++s) out[s] = EMPTY;
-    }
-  }
 }
 
 template <int KB>
@@ -390,26 +331,18 @@ __global__ __launch_bounds__(NT) void inf_search_kernel(const SearchArgs a) {
       }
       const float* rrow = Rs + (rtw * 32 + l31) * SST + 4 * lh;  // A[m = reference][k]: lane half h holds column 8 b + 2 s + h in step s
       const float* qrw = Qs + (qtw * 32 + l31) * SST + 4 * lh;   // B[k][n = query]
-#pragma unroll
-      for (int kk = 0; kk < KS; kk += 8) {
-        const float4 r4 = *reinterpret_cast<const float4*>(rrow + kk);
-        const float4 q4 = *reinterpret_cast<const float4*>(qrw + kk);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(r4.x, q4.x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(r4.y, q4.y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(r4.z, q4.z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(r4.w, q4.w, acc, 0, 0, 0);
-      }
+      acc = tile_dot(acc, rrow, qrw, KS);                             // a compile-time bound: unrolled
       if (sn == 0) {
-        // lane (l31, h) holds q.r of query l31 against the sub-tile's rows (r & 3) + 8 (r >> 2) + 4 h
+        // lane (l31, h) holds q.r of query l31 against the sub-tile's rows acc_row(r, h)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int i = rtw * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+          const int i = rtw * 32 + acc_row(r, lh);
           const int j = s_rj[i];
           const float sc = (a.relative ? acc[r] / s_rl[i] : acc[r]) + 0.f;       // -0 becomes +0
           const bool cand = qgood && j >= 0 && j != excl && isfinite(sc);
           const unsigned b = __float_as_uint(sc), o = b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);   // ascending as unsigned
-          const u64 kp = cand ? (((u64)(~o) << 32) | (u64)(unsigned)j) : EMPTY;
-          const u64 ko = cand ? (((u64)o << 32) | (u64)(unsigned)j) : EMPTY;
+          const u64 kp = cand ? key_of(~o, j) : EMPTY;
+          const u64 ko = cand ? key_of(o, j) : EMPTY;
           if (__ballot(kp < pro[KB - 1]) != 0ull) list_insert<KB>(pro, kp);
           if (__ballot(ko < opp[KB - 1]) != 0ull) list_insert<KB>(opp, ko);
         }
@@ -417,9 +350,10 @@ __global__ __launch_bounds__(NT) void inf_search_kernel(const SearchArgs a) {
       s = sn;
       t = tn;
     }
-    const int slot = (qtw * 32 + l31) * 4 + rtw * 2 + lh;
-    merge_four<KB>(pro, Ms, a.keys, 0, q0, a.B, a.splits, sp, slot);
-    merge_four<KB>(opp, Ms, a.keys, 1, q0, a.B, a.splits, sp, slot);
+    const int slot = (qtw * 32 + l31) * 4 + rtw * 2 + lh, g = q0 + (tid >> 2);   // g: the query whose lists this thread helps to merge
+    u64* out = g < a.B ? a.keys + ((size_t)g * 2 * a.splits + sp) * KB : nullptr;  // (B, 2, splits, KB): the proponents' words
+    merge_four<KB>(pro, Ms, slot, out);
+    merge_four<KB>(opp, Ms, slot, out ? out + (size_t)a.splits * KB : nullptr);
   }
 }
 
@@ -452,8 +386,8 @@ __global__ __launch_bounds__(64) void inf_merge_kernel(const rovit_influence_que
     if (lane < k) {
       const u64 c = top[lane];
       const bool real = c != EMPTY;
-      const int j = real ? (int)(unsigned)(c & 0xffffffffull) : -1;
-      const unsigned hi = (unsigned)(c >> 32), o = end == 0 ? ~hi : hi, b = o ^ ((o >> 31) ? 0x80000000u : 0xffffffffu);
+      const int j = real ? key_index(c) : -1;
+      const unsigned hi = key_bits(c), o = end == 0 ? ~hi : hi, b = o ^ ((o >> 31) ? 0x80000000u : 0xffffffffu);
       const float sc = real ? __uint_as_float(b) : __builtin_nanf("");
       const size_t at = (size_t)q * k + lane;
       (end == 0 ? a.pro_scores : a.opp_scores)[at] = sc;
@@ -500,9 +434,7 @@ extern "C" int rovit_influence_embed(const rovit_influence_rows* p, rovit_stream
                   ROVIT_ERR_ALIGN, "%s: an array is not aligned to its element size", who);
   const size_t lds = embed_lds_bytes(p->embed, p->hid);
   ROVIT_CHECK_ARG(rovit_set_max_lds((const void*)inf_embed_kernel, lds), ROVIT_ERR_LAUNCH, "%s: cannot raise the LDS limit", who);
-  const long long tiles = ((long long)p->n + ROWS - 1) / ROWS;
-  const long long cap = p->max_workgroups > 0 ? p->max_workgroups : (1ll << 30);
-  hipLaunchKernelGGL(inf_embed_kernel, dim3((unsigned)(tiles < cap ? tiles : cap)), dim3(NT), lds, (hipStream_t)stream, *p);
+  hipLaunchKernelGGL(inf_embed_kernel, rovit_grid(((long long)p->n + ROWS - 1) / ROWS, p->max_workgroups), dim3(NT), lds, (hipStream_t)stream, *p);
   ROVIT_CHECK_LAUNCH("inf_embed_kernel");
   return ROVIT_OK;
 }
@@ -541,8 +473,7 @@ extern "C" int rovit_influence_search(const rovit_influence_query* p, rovit_stre
   const size_t need = keys_bytes(B, pl);
   ROVIT_CHECK_ARG(p->workspace_bytes >= need, ROVIT_ERR_SHAPE, "%s: the workspace holds %zu bytes, %zu are needed", who, p->workspace_bytes, need);
   hipStream_t s = (hipStream_t)stream;
-  const long long cap = p->max_workgroups > 0 ? p->max_workgroups : (1ll << 30);
-  auto grid = [&](long long items) { return dim3((unsigned)(items < cap ? items : cap)); };
+  auto grid = [&](long long items) { return rovit_grid(items, p->max_workgroups); };
   SearchArgs a;
   a.B = B; a.n = n; a.dim = p->dim; a.relative = p->relative;
   a.qtiles = pl.qtiles; a.rtiles = pl.rtiles; a.splits = pl.splits; a.tps = pl.tps;

@@ -3,8 +3,8 @@
 // `index_add_` materialises an (n, k) matrix, has no tie rule and sums its centroids with atomics; here no such matrix exists, the
 // order is total, and every output is the same bits for every grid.
 //
-// Distance: the neighbours' (neighbors.hip): l2 = max(0, (|x|^2 + |c|^2) - 2 x.c), cosine = max(0, 1 - x^.c); every term fp32, x.c and
-// the norms fma chains in ascending feature index.  The seeding kernel forms x.c with fmaf on the vector units, the assignment kernel on
+// Distance: the neighbours' (dist_of, feature_tiles.h): l2 = max(0, (|x|^2 + |c|^2) - 2 x.c), cosine = max(0, 1 - x^.c); every term fp32,
+// x.c and the norms fma chains in ascending feature index.  The seeding kernel forms x.c with fmaf on the vector units, the assignment kernel on
 // v_mfma_f32_32x32x2_f32, whose result is that chain: the same bits.  Order: the key (bits(d) << 32) | c, smallest first.
 //
 //   km_rows_kernel          a thread per row: squared norm, validity flag, with cosine the unit row; the counts (integer atomics).
@@ -28,14 +28,14 @@
 //   km_contingency_kernel   integer atomics into the (k, C) table.
 // A run enqueues max_iter iterations at once; every kernel of an iteration returns at once when the flag is set.
 #include "common.h"
+#include "feature_tiles.h"
 #include "philox.h"
 #include "topk_device.h"
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
 namespace {
 
-using namespace topk;                            // u64, EMPTY, store_unit
+using namespace ftile;                           // row_scan, count_rows, store_unit, tile_dot, acc_row, dist_of
+using namespace topk;                            // u64, EMPTY, key_of, key_bits, key_index
 
 constexpr int NT = 256;                          // threads per workgroup = rows of a sort block
 constexpr int QT = 64, CT = 64;                  // rows / centroids of an LDS tile
@@ -76,12 +76,6 @@ inline bool limits_ok(int n, int E, int k) {
   return n >= 1 && n <= ROVIT_KMEANS_MAX_ROWS && E >= 32 && E <= 256 && E % 32 == 0 && k >= 1 && k <= MAXK;
 }
 
-__device__ __forceinline__ float dist_of(bool cosine, float xn, float cn, float dot, bool* finite) {
-  const float raw = cosine ? 1.f - dot : (xn + cn) - 2.f * dot;
-  *finite = isfinite(raw);
-  return raw > 0.f ? raw : 0.f;
-}
-
 // ---- rows: norms, flags, the unit rows ----------------------------------------------------------------------------------------------------
 
 struct RowArgs {
@@ -94,40 +88,12 @@ struct RowArgs {
 };
 
 __global__ __launch_bounds__(NT) void km_rows_kernel(const RowArgs a) {
-  const int chunks = (a.n + NT - 1) / NT, E4 = a.E / 4;
+  const int chunks = (a.n + NT - 1) / NT;
   for (int w = blockIdx.x; w < chunks; w += gridDim.x) {
     const int row = w * NT + threadIdx.x;
     bool good = false;
-    if (row < a.n) {
-      const float4* src = reinterpret_cast<const float4*>(a.x + (size_t)row * a.E);
-      float s = 0.f;
-      bool fin = true;
-      for (int c = 0; c < E4; ++c) {
-        const float4 v = src[c];
-        fin &= isfinite(v.x) && isfinite(v.y) && isfinite(v.z) && isfinite(v.w);
-        s = fmaf(v.x, v.x, s);
-        s = fmaf(v.y, v.y, s);
-        s = fmaf(v.z, v.z, s);
-        s = fmaf(v.w, v.w, s);
-      }
-      good = fin && isfinite(s) && (!a.cosine || s > 0.f);
-      a.norm[row] = s;
-      a.ok[row] = good ? 1 : 0;
-      if (a.xhat) {
-        float4* dst = reinterpret_cast<float4*>(a.xhat + (size_t)row * a.E);
-        const float len = sqrtf(s);
-        for (int c = 0; c < E4; ++c) {
-          const float4 v = src[c];
-          dst[c] = good ? make_float4(v.x / len, v.y / len, v.z / len, v.w / len) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-      }
-    }
-    const u64 m_good = __ballot(good), m_bad = __ballot(row < a.n && !good);
-    if ((threadIdx.x & 63) == 0) {
-      if (m_good) atomicAdd(&a.status[ROVIT_KMEANS_N_VALID], (u64)__popcll(m_good));
-      if (m_bad) atomicAdd(&a.status[ROVIT_KMEANS_BAD_ROWS], (u64)__popcll(m_bad));
-    }
-    if (w == 0 && threadIdx.x == 0) a.status[ROVIT_KMEANS_N] = (u64)a.n;
+    if (row < a.n) good = row_scan(a.x, a.norm, a.ok, a.xhat, row, a.E, a.cosine);
+    count_rows(a.status, good, row, a.n, ROVIT_KMEANS_N, ROVIT_KMEANS_N_VALID, ROVIT_KMEANS_BAD_ROWS);
   }
 }
 
@@ -341,7 +307,7 @@ __global__ __launch_bounds__(NT) void km_assign_kernel(const AssignArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, lh = lane >> 5;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), qtw = wv >> 1, ctw = wv & 1;
   const int tiles = (a.n + QT - 1) / QT, ctiles = (a.k + CT - 1) / CT;
-  auto stage_centroids = [&](int ct) {
+  auto stage_centroids = [&](int ct) {                           // store_unit's order: k ascending in feature index, as for the rows below
 #pragma unroll
     for (int i = 0; i < MAX_T; ++i)
       if (i < T) {
@@ -405,21 +371,14 @@ __global__ __launch_bounds__(NT) void km_assign_kernel(const AssignArgs a) {
       for (int r = 0; r < 16; ++r) acc[r] = 0.f;
       const float* crow = Cs + (ctw * 32 + l31) * ST + 4 * lh;   // A[m = centroid][k]: lane half h holds feature 8 b + 2 s + h in step s
       const float* qrw = Qs + (qtw * 32 + l31) * ST + 4 * lh;    // B[k][n = row]
-      for (int kk = 0; kk < E; kk += 8) {
-        const float4 c4 = *reinterpret_cast<const float4*>(crow + kk);
-        const float4 q4 = *reinterpret_cast<const float4*>(qrw + kk);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(c4.x, q4.x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(c4.y, q4.y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(c4.z, q4.z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(c4.w, q4.w, acc, 0, 0, 0);
-      }
-      // lane (l31, h) holds x.c of row l31 against the sub-tile's centroids (r & 3) + 8 (r >> 2) + 4 h
+      acc = tile_dot(acc, crow, qrw, E);
+      // lane (l31, h) holds x.c of row l31 against the sub-tile's centroids acc_row(r, h)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int i = ctw * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh, cc = ct * CT + i;
+        const int i = ctw * 32 + acc_row(r, lh), cc = ct * CT + i;
         bool fin;
         const float d = dist_of(a.cosine, qn, s_cn[i], acc[r], &fin);
-        const u64 key = (qgood && cc < a.k && fin) ? (((u64)__float_as_uint(d) << 32) | (u64)(unsigned)cc) : EMPTY;
+        const u64 key = (qgood && cc < a.k && fin) ? key_of(__float_as_uint(d), cc) : EMPTY;
         two_insert(k1, k2, key);
       }
     }
@@ -437,9 +396,9 @@ __global__ __launch_bounds__(NT) void km_assign_kernel(const AssignArgs a) {
         u64 b1 = EMPTY, b2 = EMPTY;
 #pragma unroll
         for (int i = 0; i < 8; ++i) two_insert(b1, b2, base[i]);
-        const int label = b1 != EMPTY ? (int)(unsigned)(b1 & 0xffffffffull) : -1;
-        const float d1 = b1 != EMPTY ? __uint_as_float((unsigned)(b1 >> 32)) : __builtin_inff();
-        const float d2 = b2 != EMPTY ? __uint_as_float((unsigned)(b2 >> 32)) : __builtin_inff();
+        const int label = b1 != EMPTY ? key_index(b1) : -1;
+        const float d1 = b1 != EMPTY ? __uint_as_float(key_bits(b1)) : __builtin_inff();
+        const float d2 = b2 != EMPTY ? __uint_as_float(key_bits(b2)) : __builtin_inff();
         float sil = 0.f;
         if (b2 != EMPTY) {
           const float sa = a.cosine ? d1 : sqrtf(d1), sb = a.cosine ? d2 : sqrtf(d2), mx = sa > sb ? sa : sb;
@@ -608,7 +567,7 @@ __global__ __launch_bounds__(NT) void km_partial_kernel(const UpdArgs a) {
       const unsigned bits = __float_as_uint(d);
       in += (double)d;
       sl += (double)a.sil[r];
-      const u64 kk = ((u64)bits << 32) | (u64)(unsigned)r;
+      const u64 kk = key_of(bits, r);
       key = kk < key ? kk : key;
       rad = bits > rad ? bits : rad;
     }
@@ -766,10 +725,9 @@ struct Ctx {
   Layout l;
   char* ws;
   hipStream_t s;
-  long long cap;
   bool cosine;
   const float* rows;
-  dim3 grid(long long items) const { return dim3((unsigned)(items < 1 ? 1 : (items < cap ? items : cap))); }
+  dim3 grid(long long items) const { return rovit_grid(items, p->max_workgroups); }
 };
 
 inline Ctx ctx_of(const rovit_kmeans_problem* p, int k, rovit_stream_t stream) {
@@ -778,7 +736,6 @@ inline Ctx ctx_of(const rovit_kmeans_problem* p, int k, rovit_stream_t stream) {
   c.l = layout_of(p->n, p->embed, k);
   c.ws = (char*)p->workspace;
   c.s = (hipStream_t)stream;
-  c.cap = p->max_workgroups > 0 ? p->max_workgroups : (1ll << 30);
   c.cosine = p->metric == ROVIT_KNN_COSINE;
   c.rows = c.cosine ? p->normalized : p->features;
   return c;

@@ -5,8 +5,8 @@
 //
 // A head is fc1 (hid, E) + bias, ReLU, last layer.  a = [relu(fc1 f + b1); 1; 0 ...] is the augmented hidden row, padded from D = hid + 1
 // to P = hid + 32 columns with exact zeros (a row that is left out is zero in every column, the 1 included: exact zero products).
-// The Grams and the whitening run on the exact-fp32 matrix instruction (v_mfma_f32_32x32x2_f32), as in density.hip, whose structure the
-// two matrix kernels follow; the small fc1 product in front of them is accumulated in fp64 (lap_hidden says why).
+// The Grams and the whitening run on the exact-fp32 matrix instruction (v_mfma_f32_32x32x2_f32) on the tiles of feature_tiles.h, which
+// density.hip's two matrix kernels share; the small fc1 product in front of them is accumulated in fp64 (lap_hidden says why).
 //
 // rovit_laplace_gram, three kernels on the caller's stream; a chunk is R = lap_chunk_rows(n) consecutive rows (a function of n alone):
 //   lap_rows_kernel   per 64-row tile: the feature rows into LDS, is any feature or weight of a row non-finite, the hidden rows
@@ -20,19 +20,18 @@
 //   the diagonal tile for c = t) and z_c on the matrix instruction, one query row per lane; then S[c][d] += z_c z_d in-lane.
 // Work items are walked with a stride of the grid, and no item's result depends on which workgroup computes it.  No floating-point atomics.
 #include "common.h"
+#include "feature_tiles.h"
 #include "laplace_device.h"
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 namespace {
 
+using namespace ftile;                  // tile_dot, upper_tiles, wave_tiles, gram_slab, store_acc_tile, fold_element
 using namespace laplace;                // NT, MAXC, ROWS, lap_hidden, lap_stage_features: shared with influence.hip
 constexpr int SLAB = 32;                // rows of one LDS slab of the gram pass
 constexpr int MAXK = ROVIT_LAPLACE_MAX_WEIGHTS;
 static_assert(MAXK == MAXC * (MAXC + 1) / 2, "one weight per pair of classes");
 
 inline int lap_chunk_rows(int n) { return 256 * ((n + 256 * ROVIT_LAPLACE_MAX_CHUNKS - 1) / (256 * ROVIT_LAPLACE_MAX_CHUNKS)); }
-inline int upper_tiles(int TP) { return TP * (TP + 1) / 2; }
 
 // ---- weights -------------------------------------------------------------------------------------------------------------------------
 
@@ -158,26 +157,24 @@ __global__ __launch_bounds__(NT) void lap_rows_kernel(const GramArgs a) {
   }
 }
 
-// tile q of the upper triangle, row-major: (i, j), i <= j < T
-__device__ __forceinline__ void upper_tile(int q, int T, int& i, int& j) {
-  i = 0;
-  while (q >= T - i) { q -= T - i; ++i; }
-  j = i + q;
-}
+struct Scaled {                 // gram_slab's B operand: w_k of the slab row times the row
+  float wk;
+  __device__ __forceinline__ float operator()(float x) const { return wk * x; }
+};
+struct WeightedRows {
+  const float* w;              // [SLAB]
+  __device__ __forceinline__ Scaled operator()(int row) const { return Scaled{w[row]}; }
+};
 
 template <int TP>
 __global__ __launch_bounds__(NT) void lap_gram_kernel(const GramArgs a) {
-  constexpr int P = 32 * TP, TILES = TP * (TP + 1) / 2, NQ = (TILES + 3) / 4;
+  constexpr int P = 32 * TP, TILES = upper_tiles(TP), NQ = (TILES + 3) / 4;
   __shared__ __attribute__((aligned(16))) float Xs[SLAB * P];
   __shared__ float s_w[SLAB];
-  const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, lh = lane >> 5, n = a.n, K = a.K;
+  const int tid = threadIdx.x, n = a.n, K = a.K;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   int ti[NQ], tj[NQ];
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) {
-    ti[q] = tj[q] = 0;
-    if (wv + 4 * q < TILES) upper_tile(wv + 4 * q, TP, ti[q], tj[q]);
-  }
+  wave_tiles<TP>(wv, ti, tj);
   const int items = a.chunks * K;
   for (int w = blockIdx.x; w < items; w += gridDim.x) {
     const int chunk = w / K, k = w - chunk * K;
@@ -202,29 +199,17 @@ __global__ __launch_bounds__(NT) void lap_gram_kernel(const GramArgs a) {
         s_w[tid] = (gr < n && a.flag[gr] != 0) ? a.w[(size_t)gr * K + k] : 0.f;   // a row that is left out: 0, whatever its weight
       }
       __syncthreads();
-#pragma unroll 4
-      for (int k2 = 0; k2 < SLAB / 2; ++k2) {
-        const float* xr = Xs + (2 * k2 + lh) * P + l31;         // row k, column l31 of a tile: conflict-free
-        const float wk = s_w[2 * k2 + lh];
-#pragma unroll
-        for (int q = 0; q < NQ; ++q)
-          if (wv + 4 * q < TILES) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(xr[32 * ti[q]], wk * xr[32 * tj[q]], acc[q], 0, 0, 0);
-      }
+      gram_slab<TP>(acc, Xs, wv, ti, tj, WeightedRows{s_w});     // k = the rows of the chunk in order
     }
-    // accumulator tile: column = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
 #pragma unroll
     for (int q = 0; q < NQ; ++q)
-      if (wv + 4 * q < TILES) {
-        float* out = a.part + ((size_t)w * TILES + (wv + 4 * q)) * 1024;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) out[((r & 3) + 8 * (r >> 2) + 4 * lh) * 32 + l31] = acc[q][r];
-      }
+      if (wv + 4 * q < TILES) store_acc_tile(a.part + ((size_t)w * TILES + (wv + 4 * q)) * 1024, acc[q]);
   }
 }
 
 __global__ __launch_bounds__(NT) void lap_fold_kernel(const GramArgs a) {
   __shared__ unsigned long long s_u[4];
-  const int D = a.hid + 1, TP = (a.hid + 32) / 32, tiles = TP * (TP + 1) / 2, K = a.K, items = K * tiles * 4;
+  const int D = a.hid + 1, TP = (a.hid + 32) / 32, tiles = upper_tiles(TP), K = a.K, items = K * tiles * 4;
   if (blockIdx.x == 0) {
     unsigned long long bad = 0;
     const int row_tiles = (a.n + ROWS - 1) / ROWS;
@@ -241,11 +226,9 @@ __global__ __launch_bounds__(NT) void lap_fold_kernel(const GramArgs a) {
   double* G = (double*)a.result + ROVIT_LAPLACE_HEADER;
   for (int w = blockIdx.x; w < items; w += gridDim.x) {
     const int k = w / (tiles * 4), rem = w - k * tiles * 4;
-    const int q = rem >> 2, el = (rem & 3) * NT + threadIdx.x, m = el >> 5, nn = el & 31;
-    int i, j;
-    upper_tile(q, TP, i, j);
-    const int ra = 32 * i + m, rb = 32 * j + nn;
-    if ((i == j && m > nn) || ra >= D || rb >= D) continue;     // the mirror fills the lower half; the padding is not part of G
+    const int q = rem >> 2, el = (rem & 3) * NT + threadIdx.x;
+    int ra, rb;
+    if (fold_element(q, el, TP, ra, rb) || ra >= D || rb >= D) continue;   // the mirror fills the lower half; the padding is not part of G
     double s = 0.0;
     for (int c = 0; c < a.chunks; ++c) s += (double)a.part[(((size_t)c * K + k) * tiles + q) * 1024 + el];
     double* Gk = G + (size_t)k * D * D;
@@ -284,7 +267,7 @@ __global__ __launch_bounds__(NT) void lap_predict_kernel(const rovit_laplace_que
 #pragma unroll
     for (int q = 0; q < MAXK; ++q) S[q] = 0.f;
     const float* frow = As + (rt * 32 + l31) * SA + 4 * lh;     // B[k][n = row]
-    const float* wrow = Ws + (th * 32 + l31) * SA + 4 * lh;     // A[m = t][k]
+    const float* wrow = Ws + (th * 32 + l31) * SA + 4 * lh;     // A[m = t][k]: plain rows, lane half h holds k = kk + 4 h + s in step s
     for (int cb = 0; cb < C; ++cb) {
       for (int at0 = 0; at0 < TP; at0 += 2) {
         const int at = at0 + th;                                // this wave's tile of class block cb
@@ -308,17 +291,10 @@ __global__ __launch_bounds__(NT) void lap_predict_kernel(const rovit_laplace_que
             __syncthreads();
             if (live) {
               const int kend = c == cb ? 32 * at + 32 : P;
-              for (int kk = 0; kk < kend; kk += 8) {
-                const float4 w4 = *reinterpret_cast<const float4*>(wrow + kk);
-                const float4 f4 = *reinterpret_cast<const float4*>(frow + kk);
-                acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(w4.x, f4.x, acc[c], 0, 0, 0);
-                acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(w4.y, f4.y, acc[c], 0, 0, 0);
-                acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(w4.z, f4.z, acc[c], 0, 0, 0);
-                acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(w4.w, f4.w, acc[c], 0, 0, 0);
-              }
+              acc[c] = tile_dot(acc[c], wrow, frow, kend);
             }
           }
-        // lane (l31, h) holds z_c[row l31][t = 32 at + (r & 3) + 8 (r >> 2) + 4 h] of every c <= cb
+        // lane (l31, h) holds z_c[row l31][t = 32 at + acc_row(r, h)] of every c <= cb
         if (live) {
           int q = 0;
 #pragma unroll
@@ -421,8 +397,7 @@ extern "C" int rovit_laplace_weights(const rovit_laplace_weight_args* p, rovit_s
     rovit_set_error("%s: hipMemsetAsync failed", who);
     return ROVIT_ERR_LAUNCH;
   }
-  const long long blocks = ((long long)p->n + NT - 1) / NT, cap = p->max_workgroups > 0 ? p->max_workgroups : (1ll << 30);
-  hipLaunchKernelGGL(lap_weights_kernel, dim3((unsigned)(blocks < cap ? blocks : cap)), dim3(NT), 0, s, *p);
+  hipLaunchKernelGGL(lap_weights_kernel, rovit_grid(((long long)p->n + NT - 1) / NT, p->max_workgroups), dim3(NT), 0, s, *p);
   ROVIT_CHECK_LAUNCH("lap_weights_kernel");
   return ROVIT_OK;
 }
@@ -460,8 +435,7 @@ extern "C" int rovit_laplace_gram(const rovit_laplace_fit* p, rovit_stream_t str
   a.part = (float*)(ws + l.part);
   a.result = p->result;
   hipStream_t s = (hipStream_t)stream;
-  const long long cap = p->max_workgroups > 0 ? p->max_workgroups : (1ll << 30);
-  auto grid = [&](long long items) { return dim3((unsigned)(items < cap ? items : cap)); };
+  auto grid = [&](long long items) { return rovit_grid(items, p->max_workgroups); };
   const int TP = (hid + 32) / 32;
   hipLaunchKernelGGL(lap_rows_kernel, grid(((long long)n + ROWS - 1) / ROWS), dim3(NT), lds, s, a);
   ROVIT_CHECK_LAUNCH("lap_rows_kernel");
@@ -505,8 +479,7 @@ extern "C" int rovit_laplace_predict(const rovit_laplace_query* p, rovit_stream_
   const size_t lds = predict_lds_bytes(p->embed, p->hid);
   ROVIT_CHECK_ARG(rovit_set_max_lds((const void*)lap_predict_kernel, lds), ROVIT_ERR_LAUNCH, "%s: cannot raise the LDS limit", who);
   const long long tiles = ((long long)p->batch + ROWS - 1) / ROWS;
-  const long long cap = p->max_workgroups > 0 ? p->max_workgroups : (1ll << 30);
-  hipLaunchKernelGGL(lap_predict_kernel, dim3((unsigned)(tiles < cap ? tiles : cap)), dim3(NT), lds, (hipStream_t)stream, *p);
+  hipLaunchKernelGGL(lap_predict_kernel, rovit_grid(tiles, p->max_workgroups), dim3(NT), lds, (hipStream_t)stream, *p);
   ROVIT_CHECK_LAUNCH("lap_predict_kernel");
   return ROVIT_OK;
 }

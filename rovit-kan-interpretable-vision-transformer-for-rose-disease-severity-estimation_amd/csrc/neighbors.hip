@@ -4,11 +4,11 @@
 //
 // Distance (include/rovit_hip.h): l2 = max(0, (|q|^2 + |r|^2) - 2 q.r), cosine = max(0, 1 - q^.r^); every term fp32, q.r and the norms
 // fma chains in ascending feature index.  q.r runs on the exact-fp32 matrix instruction (v_mfma_f32_32x32x2_f32: a k-ordered fp32 fma
-// chain, as density.hip uses it), so a distance is a function of its two rows alone.  Order: the key (bits(d) << 32) | j as an unsigned
+// chain; feature_tiles.h), so a distance is a function of its two rows alone.  Order: the key (bits(d) << 32) | j as an unsigned
 // 64-bit integer; the k smallest keys, ascending.  Only integer compares decide membership.
 //
-//   knn_rows_kernel    a thread per row: the squared norm (one fma chain), the validity flag; for the recorded rows with cosine also the
-//                      normalised copy, and the integer counts (integer atomics).
+//   knn_rows_kernel    a thread per row: the row scan of feature_tiles.h (squared norm, validity flag; for the recorded rows with cosine
+//                      also the normalised copy) and the integer counts (integer atomics).
 //   knn_search_kernel  a work item = (query tile of 64 rows, reference split).  The 64 query rows sit in LDS (normalised on the way in with
 //                      cosine); 64-row reference tiles stream through a second LDS buffer, the next tile's loads in flight in registers while
 //                      this tile's products run.  Both buffers hold each group of 8 features as (f0 f2 f4 f6 | f1 f3 f5 f7): a lane half
@@ -24,39 +24,20 @@
 //                      smallest unpacked; then the vote in fp64 in slot order by one lane.
 // Work items are walked with a stride of the grid; no floating-point atomic; no result depends on which workgroup computes it.
 #include "common.h"
+#include "feature_tiles.h"
 #include "topk_device.h"
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 namespace {
 
-using namespace topk;                            // u64, EMPTY, keys_below, list_insert, store_unit: shared with influence.hip
+using namespace ftile;                           // row_scan, count_rows, store_unit, tile_dot, acc_row, dist_of
+using namespace topk;                            // u64, EMPTY, key_of, keys_below, list_insert, merge_four, Plan, plan_of
 
 constexpr int NT = 256;                        // threads per workgroup
 constexpr int QT = ROVIT_KNN_QUERY_TILE;         // query rows of a work item
 constexpr int RT = 64;                           // reference rows of an LDS tile
 constexpr int MAXK = ROVIT_KNN_MAX_K;
-constexpr int MAX_SPLITS = 64;
-constexpr int TARGET_ITEMS = 512;                // two work items per CU: the splits are chosen to reach it
 constexpr int MAX_T = 8;                         // embed / 32
-static_assert(QT == 64 && RT == 64, "2 x 2 sub-tiles of 32 per workgroup, one per wave");
-
-inline int bucket_of(int k) { return k <= 8 ? 8 : (k <= 16 ? 16 : 32); }
-
-struct Plan { int qtiles, rtiles, splits, tps, kb; };
-inline Plan plan_of(int B, int N, int k) {
-  Plan p;
-  p.qtiles = (B + QT - 1) / QT;
-  p.rtiles = (N + RT - 1) / RT;
-  p.kb = bucket_of(k);
-  long long s = (TARGET_ITEMS + p.qtiles - 1) / p.qtiles;
-  s = s < 1 ? 1 : s;
-  s = s > MAX_SPLITS ? MAX_SPLITS : s;
-  s = s > p.rtiles ? p.rtiles : s;
-  p.tps = (p.rtiles + (int)s - 1) / (int)s;
-  p.splits = (p.rtiles + p.tps - 1) / p.tps;
-  return p;
-}
+static_assert(QT == 64 && RT == 64, "2 x 2 sub-tiles of 32 per workgroup, one per wave; plan_of's tiles");
 
 struct Layout { size_t qnorm, qok, keys, total; };
 inline Layout layout_of(int B, const Plan& p) {
@@ -84,42 +65,12 @@ struct RowArgs {
 };
 
 __global__ __launch_bounds__(NT) void knn_rows_kernel(const RowArgs a) {
-  const int chunks = (a.n + NT - 1) / NT, E4 = a.E / 4;
+  const int chunks = (a.n + NT - 1) / NT;
   for (int w = blockIdx.x; w < chunks; w += gridDim.x) {
     const int row = w * NT + threadIdx.x;
     bool good = false;
-    if (row < a.n) {
-      const float4* src = reinterpret_cast<const float4*>(a.x + (size_t)row * a.E);
-      float s = 0.f;
-      bool fin = true;
-      for (int c = 0; c < E4; ++c) {
-        const float4 v = src[c];
-        fin &= isfinite(v.x) && isfinite(v.y) && isfinite(v.z) && isfinite(v.w);
-        s = fmaf(v.x, v.x, s);
-        s = fmaf(v.y, v.y, s);
-        s = fmaf(v.z, v.z, s);
-        s = fmaf(v.w, v.w, s);
-      }
-      good = fin && isfinite(s) && (!a.cosine || s > 0.f);
-      a.norm[row] = s;
-      a.ok[row] = good ? 1 : 0;
-      if (a.xhat) {
-        float4* dst = reinterpret_cast<float4*>(a.xhat + (size_t)row * a.E);
-        const float len = sqrtf(s);
-        for (int c = 0; c < E4; ++c) {
-          const float4 v = src[c];
-          dst[c] = good ? make_float4(v.x / len, v.y / len, v.z / len, v.w / len) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-      }
-    }
-    if (a.counts) {
-      const u64 m_good = __ballot(good), m_bad = __ballot(row < a.n && !good);
-      if ((threadIdx.x & 63) == 0) {
-        if (m_good) atomicAdd(&a.counts[ROVIT_KNN_N_VALID], (u64)__popcll(m_good));
-        if (m_bad) atomicAdd(&a.counts[ROVIT_KNN_BAD_ROWS], (u64)__popcll(m_bad));
-      }
-      if (w == 0 && threadIdx.x == 0) a.counts[ROVIT_KNN_N] = (u64)a.n;
-    }
+    if (row < a.n) good = row_scan(a.x, a.norm, a.ok, a.xhat, row, a.E, a.cosine);
+    if (a.counts) count_rows(a.counts, good, row, a.n, ROVIT_KNN_N, ROVIT_KNN_N_VALID, ROVIT_KNN_BAD_ROWS);
   }
 }
 
@@ -172,7 +123,7 @@ __global__ __launch_bounds__(NT) void knn_search_kernel(const SearchArgs a) {
             v = make_float4(v.x / len, v.y / len, v.z / len, v.w / len);
           }
         }
-        store_unit(Qs + row * ST + 8 * c8, u, v);
+        store_unit(Qs + row * ST + 8 * c8, u, v);               // k ascending in feature index, as for the reference tiles below
       }
     const int qrow = q0 + qtw * 32 + l31;
     const bool qgood = qrow < a.B && a.qok[qrow] != 0;
@@ -226,54 +177,21 @@ __global__ __launch_bounds__(NT) void knn_search_kernel(const SearchArgs a) {
       for (int r = 0; r < 16; ++r) acc[r] = 0.f;
       const float* rrow = Rs + (rtw * 32 + l31) * ST + 4 * lh;   // A[m = reference][k]: lane half h holds feature 8 b + 2 s + h in step s
       const float* qrw = Qs + (qtw * 32 + l31) * ST + 4 * lh;    // B[k][n = query]
-      for (int kk = 0; kk < E; kk += 8) {
-        const float4 r4 = *reinterpret_cast<const float4*>(rrow + kk);
-        const float4 q4 = *reinterpret_cast<const float4*>(qrw + kk);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(r4.x, q4.x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(r4.y, q4.y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(r4.z, q4.z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(r4.w, q4.w, acc, 0, 0, 0);
-      }
-      // lane (l31, h) holds q.r of query l31 against the sub-tile's rows (r & 3) + 8 (r >> 2) + 4 h
+      acc = tile_dot(acc, rrow, qrw, E);
+      // lane (l31, h) holds q.r of query l31 against the sub-tile's rows acc_row(r, h)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int i = rtw * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        const int i = rtw * 32 + acc_row(r, lh);
         const int j = s_rj[i];
-        const float raw = a.cosine ? 1.f - acc[r] : (qn + s_rn[i]) - 2.f * acc[r];
-        const float d = raw > 0.f ? raw : 0.f;
-        // norms near the top of the fp32 range can overflow the sum or the product: such a pair has no fp32 distance and is no candidate
-        const bool cand = qgood && j >= 0 && j != excl && isfinite(raw);
-        const u64 key = cand ? (((u64)__float_as_uint(d) << 32) | (u64)(unsigned)j) : EMPTY;
+        bool fin;
+        const float d = dist_of(a.cosine, qn, s_rn[i], acc[r], &fin);
+        const bool cand = qgood && j >= 0 && j != excl && fin;
+        const u64 key = cand ? key_of(__float_as_uint(d), j) : EMPTY;
         if (__ballot(key < lst[KB - 1]) != 0ull) list_insert<KB>(lst, key);
       }
     }
-    __syncthreads();                                             // every wave is done with the staging buffers
-    {
-      u64* mine = Ms + ((qtw * 32 + l31) * 4 + rtw * 2 + lh) * KB;
-#pragma unroll
-      for (int i = 0; i < KB; ++i) mine[i] = lst[i];
-    }
-    __syncthreads();
-    {
-      const int ql = tid >> 2, li = tid & 3, g = q0 + ql;
-      if (g < a.B) {
-        const u64* base = Ms + ql * 4 * KB;
-        u64* out = a.keys + ((size_t)g * a.splits + sp) * KB;
-        for (int i = 0; i < KB; ++i) {
-          const u64 c = base[li * KB + i];
-          if (c == EMPTY) break;
-          int rank = i;
-          for (int o = 0; o < 4; ++o)
-            if (o != li) rank += keys_below(base + o * KB, KB, c);
-          if (rank < KB) out[rank] = c;
-        }
-        if (li == 0) {
-          int real = 0;
-          for (int o = 0; o < 4; ++o) real += keys_below(base + o * KB, KB, EMPTY);
-          for (int s = real; s < KB; ++s) out[s] = EMPTY;
-        }
-      }
-    }
+    const int g = q0 + (tid >> 2);                               // the query whose four lists this thread helps to merge
+    merge_four<KB>(lst, Ms, (qtw * 32 + l31) * 4 + rtw * 2 + lh, g < a.B ? a.keys + ((size_t)g * a.splits + sp) * KB : nullptr);
   }
 }
 
@@ -337,9 +255,9 @@ __global__ __launch_bounds__(64) void knn_merge_kernel(const rovit_knn_query a, 
     if (lane < k) {
       const u64 c = top[lane];
       const bool real = c != EMPTY;
-      const int j = real ? (int)(unsigned)(c & 0xffffffffull) : -1;
+      const int j = real ? key_index(c) : -1;
       const size_t o = (size_t)q * k + lane;
-      a.distances[o] = real ? __uint_as_float((unsigned)(c >> 32)) : __builtin_inff();
+      a.distances[o] = real ? __uint_as_float(key_bits(c)) : __builtin_inff();
       a.indices[o] = j;
       if (a.labels) a.labels[o] = real ? a.ref_labels[j] : -1;
       if (a.severities) a.severities[o] = real ? a.ref_severity[j] : __builtin_nanf("");
@@ -348,11 +266,11 @@ __global__ __launch_bounds__(64) void knn_merge_kernel(const rovit_knn_query a, 
       int nv = 0;
       while (nv < k && top[nv] != EMPTY) ++nv;
       double sw = 0.0, ss = 0.0, sd = 0.0, dk = 0.0;
-      const double d1 = nv ? (double)__uint_as_float((unsigned)(top[0] >> 32)) : 0.0;
+      const double d1 = nv ? (double)__uint_as_float(key_bits(top[0])) : 0.0;
       for (int s = 0; s < nv; ++s) {
         const u64 c = top[s];
-        const int j = (int)(unsigned)(c & 0xffffffffull);
-        dk = (double)__uint_as_float((unsigned)(c >> 32));
+        const int j = key_index(c);
+        dk = (double)__uint_as_float(key_bits(c));
         const double w = exp(-(dk - d1) / a.temperature);
         sw += w;
         sd += dk;
@@ -388,7 +306,7 @@ bool launch_search(dim3 grid, size_t lds, hipStream_t s, const SearchArgs& a) {
 }  // namespace
 
 extern "C" size_t rovit_knn_workspace_bytes(int batch, int n, int embed, int k) {
-  return limits_ok(batch, n, embed, k) ? layout_of(batch, plan_of(batch, n, k)).total : 0;
+  return limits_ok(batch, n, embed, k) ? layout_of(batch, plan_of(batch, n, k, 0)).total : 0;
 }
 
 extern "C" int rovit_knn_build(const rovit_knn_index* p, rovit_stream_t stream) {
@@ -413,8 +331,7 @@ extern "C" int rovit_knn_build(const rovit_knn_index* p, rovit_stream_t stream) 
   RowArgs a;
   a.n = p->n; a.E = p->embed; a.cosine = p->metric == ROVIT_KNN_COSINE;
   a.x = p->features; a.norm = p->norms; a.ok = p->valid; a.xhat = p->normalized; a.counts = (u64*)p->result;
-  const long long chunks = ((long long)p->n + NT - 1) / NT, cap = p->max_workgroups > 0 ? p->max_workgroups : (1ll << 30);
-  hipLaunchKernelGGL(knn_rows_kernel, dim3((unsigned)(chunks < cap ? chunks : cap)), dim3(NT), 0, s, a);
+  hipLaunchKernelGGL(knn_rows_kernel, rovit_grid(((long long)p->n + NT - 1) / NT, p->max_workgroups), dim3(NT), 0, s, a);
   ROVIT_CHECK_LAUNCH("knn_rows_kernel");
   return ROVIT_OK;
 }
@@ -447,14 +364,13 @@ extern "C" int rovit_knn_search(const rovit_knn_query* p, rovit_stream_t stream)
                       rovit_aligned(p->kth_distance, 4) && rovit_aligned(p->mean_distance, 4),
                   ROVIT_ERR_ALIGN, "%s: an array is not aligned to its element size", who);
   const int B = p->batch, N = p->n, E = p->embed;
-  const Plan pl = plan_of(B, N, p->k);
+  const Plan pl = plan_of(B, N, p->k, 0);
   const Layout l = layout_of(B, pl);
   ROVIT_CHECK_ARG(p->workspace_bytes >= l.total, ROVIT_ERR_SHAPE, "%s: the workspace holds %zu bytes, %zu are needed", who, p->workspace_bytes,
                   l.total);
   char* ws = (char*)p->workspace;
   hipStream_t s = (hipStream_t)stream;
-  const long long cap = p->max_workgroups > 0 ? p->max_workgroups : (1ll << 30);
-  auto grid = [&](long long items) { return dim3((unsigned)(items < cap ? items : cap)); };
+  auto grid = [&](long long items) { return rovit_grid(items, p->max_workgroups); };
   const bool cosine = p->metric == ROVIT_KNN_COSINE;
   RowArgs ra;
   ra.n = B; ra.E = E; ra.cosine = cosine;

@@ -4,7 +4,7 @@
 // optimisation.  Definitions and limits: include/rovit_hip.h.
 //
 //   tsne_rows_kernel      a thread per row: the validity flag (every feature and the squared norm finite; with cosine the norm positive) and
-//                         with cosine the unit row, formed as neighbors.hip forms it.
+//                         with cosine the unit row: the row scan of feature_tiles.h, the one neighbors.hip and kmeans.hip run.
 //   tsne_dist_kernel      a 64 x 64 tile of D per work item; the two row tiles stream through LDS 32 features at a time; a thread owns a
 //                         4 x 4 block and runs, per pair, ONE fp32 chain  acc = fma(x_ik - x_jk, x_ik - x_jk, acc), k ascending from 0: every
 //                         term is non-negative, D_ii is 0 and D_ij = D_ji bit for bit.  Vector units, no matrix instruction: the difference
@@ -23,6 +23,7 @@
 // output is the same bits for every max_workgroups.  No atomic of any kind; no kernel waits on another workgroup; two plain launches per
 // iteration.
 #include "common.h"
+#include "feature_tiles.h"
 #include "philox.h"
 
 namespace {
@@ -94,31 +95,11 @@ struct RowArgs {
 };
 
 __global__ __launch_bounds__(NT) void tsne_rows_kernel(const RowArgs a) {
-  const int chunks = (a.n + NT - 1) / NT, E4 = a.E / 4;
+  const int chunks = (a.n + NT - 1) / NT;
   for (int w = blockIdx.x; w < chunks; w += gridDim.x) {
     const int row = w * NT + threadIdx.x;
     if (row >= a.n) continue;
-    const float4* src = reinterpret_cast<const float4*>(a.x + (size_t)row * a.E);
-    float s = 0.f;
-    bool fin = true;
-    for (int c = 0; c < E4; ++c) {
-      const float4 v = src[c];
-      fin &= isfinite(v.x) && isfinite(v.y) && isfinite(v.z) && isfinite(v.w);
-      s = fmaf(v.x, v.x, s);
-      s = fmaf(v.y, v.y, s);
-      s = fmaf(v.z, v.z, s);
-      s = fmaf(v.w, v.w, s);
-    }
-    const bool good = fin && isfinite(s) && (!a.cosine || s > 0.f);
-    a.ok[row] = good ? 1 : 0;
-    if (a.xhat) {
-      float4* dst = reinterpret_cast<float4*>(a.xhat + (size_t)row * a.E);
-      const float len = sqrtf(s);
-      for (int c = 0; c < E4; ++c) {
-        const float4 v = src[c];
-        dst[c] = good ? make_float4(v.x / len, v.y / len, v.z / len, v.w / len) : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-    }
+    ftile::row_scan(a.x, nullptr, a.ok, a.xhat, row, a.E, a.cosine);   // the norm is not kept: the distances are of the difference form
   }
 }
 
@@ -549,12 +530,6 @@ __global__ __launch_bounds__(NT) void tsne_random_kernel(unsigned long long seed
   }
 }
 
-inline dim3 grid_of(long long items, int max_workgroups) {
-  const long long cap = max_workgroups > 0 ? max_workgroups : (1ll << 20);
-  const long long g = items < cap ? items : cap;
-  return dim3((unsigned)(g < 1 ? 1 : g));
-}
-
 }  // namespace
 
 extern "C" size_t rovit_tsne_workspace_bytes(int n, int embed) { return limits_ok(n, embed) ? layout_of(n, embed).total : 0; }
@@ -589,26 +564,26 @@ extern "C" int rovit_tsne_affinities(const rovit_tsne_affinity* p, rovit_stream_
 
   RowArgs ra;
   ra.n = n; ra.E = E; ra.cosine = cosine; ra.x = p->features; ra.ok = ok; ra.xhat = cosine ? (float*)(ws + l.xhat) : nullptr;
-  hipLaunchKernelGGL(tsne_rows_kernel, grid_of((n + NT - 1) / NT, mw), dim3(NT), 0, s, ra);
+  hipLaunchKernelGGL(tsne_rows_kernel, rovit_grid((n + NT - 1) / NT, mw), dim3(NT), 0, s, ra);
   ROVIT_CHECK_LAUNCH("tsne_rows_kernel");
   hipLaunchKernelGGL(tsne_count_kernel, dim3(1), dim3(NT), 0, s, n, (const int*)ok, counts);
   ROVIT_CHECK_LAUNCH("tsne_count_kernel");
 
   DistArgs da;
   da.n = n; da.E = E; da.tiles = (n + DT - 1) / DT; da.x = cosine ? ra.xhat : p->features; da.ok = ok; da.D = p->P;
-  hipLaunchKernelGGL(tsne_dist_kernel, grid_of((long long)da.tiles * da.tiles, mw), dim3(NT), 0, s, da);
+  hipLaunchKernelGGL(tsne_dist_kernel, rovit_grid((long long)da.tiles * da.tiles, mw), dim3(NT), 0, s, da);
   ROVIT_CHECK_LAUNCH("tsne_dist_kernel");
   if (p->distances_only) return ROVIT_OK;
 
   PerpArgs pa;
   pa.n = n; pa.log_perplexity = log(p->perplexity); pa.P = p->P; pa.ok = ok; pa.beta = p->beta; pa.entropy = p->entropy; pa.unconv = unconv;
-  hipLaunchKernelGGL(tsne_perp_kernel, grid_of(n, mw), dim3(NT), perp_lds, s, pa);
+  hipLaunchKernelGGL(tsne_perp_kernel, rovit_grid(n, mw), dim3(NT), perp_lds, s, pa);
   ROVIT_CHECK_LAUNCH("tsne_perp_kernel");
 
   if (p->symmetrize) {
     SymArgs sa;
     sa.n = n; sa.tiles = (n + ST - 1) / ST; sa.P = p->P; sa.ok = ok; sa.counts = counts;
-    hipLaunchKernelGGL(tsne_sym_kernel, grid_of((long long)sa.tiles * sa.tiles, mw), dim3(NT), 0, s, sa);
+    hipLaunchKernelGGL(tsne_sym_kernel, rovit_grid((long long)sa.tiles * sa.tiles, mw), dim3(NT), 0, s, sa);
     ROVIT_CHECK_LAUNCH("tsne_sym_kernel");
   }
   hipLaunchKernelGGL(tsne_affinity_status_kernel, dim3(1), dim3(NT), 0, s, n, (const int*)ok, (const int*)unconv, (const float*)p->beta,
@@ -652,7 +627,7 @@ extern "C" int rovit_tsne_run(const rovit_tsne_descent* p, rovit_stream_t stream
   UpdateArgs ua;
   ua.n = n; ua.eta = p->learning_rate; ua.auto_alpha = p->early_exaggeration; ua.part = fa.part;
   ua.Y = p->Y; ua.V = p->V; ua.G = p->G; ua.trace = p->trace; ua.grad_out = p->grad_out; ua.z_out = p->z_out;
-  const dim3 fgrid = grid_of((n + FR - 1) / FR, mw), ugrid = grid_of((2ll * n + NT - 1) / NT, mw);
+  const dim3 fgrid = rovit_grid((n + FR - 1) / FR, mw), ugrid = rovit_grid((2ll * n + NT - 1) / NT, mw);
   int slot = 0;
   for (int t = 0; t < p->n_iter; ++t) {
     const bool early = t < p->exaggeration_iter;
@@ -682,7 +657,7 @@ extern "C" int rovit_tsne_random_init(unsigned long long seed, float* Y, int n, 
   ROVIT_CHECK_ARG(n >= 1 && n <= ROVIT_TSNE_MAX_ROWS, ROVIT_ERR_SHAPE, "%s: %d rows (1..%d)", who, n, ROVIT_TSNE_MAX_ROWS);
   ROVIT_CHECK_ARG(Y, ROVIT_ERR_NULL, "%s: a null pointer", who);
   ROVIT_CHECK_ARG(rovit_aligned(Y, 4), ROVIT_ERR_ALIGN, "%s: the map is not aligned to its words", who);
-  hipLaunchKernelGGL(tsne_random_kernel, grid_of((2ll * n + NT - 1) / NT, 0), dim3(NT), 0, (hipStream_t)stream, seed, 2 * n, Y);
+  hipLaunchKernelGGL(tsne_random_kernel, rovit_grid((2ll * n + NT - 1) / NT, 0), dim3(NT), 0, (hipStream_t)stream, seed, 2 * n, Y);
   ROVIT_CHECK_LAUNCH("tsne_random_kernel");
   return ROVIT_OK;
 }
