@@ -232,6 +232,32 @@ int rovit_vit_forward_rollout(const float* images, const float* const* params, c
  * clamped: cv2.resize INTER_LINEAR / F.interpolate align_corners=False) to 224x224, then (m - min) / (max - min + 1e-8) per
  * image.  map224 fp32 (B,224,224). */
 int rovit_rollout_map(const float* rollout, float* map224, int batch, rovit_stream_t stream);
+/* forward + per-head attention statistics (no counterpart in the reference; Dosovitskiy et al. 2021 fig. 11, Raghu et al. 2021).  For
+ * image b, block l, head h with softmax probabilities P (197 x 197), class token 0, patch t >= 1 at (r, c) = divmod(t - 1, 14),
+ * dist(i, j) = 16 sqrt((r_i - r_j)^2 + (c_i - c_j)^2) pixels and 0 ln 0 = 0, per query row i:
+ *   H_i = -sum_j P_ij ln P_ij (nats);  D_i = sum_{j>=1} P_ij dist(i, j) / sum_{j>=1} P_ij for i >= 1 (0 for i = 0, and where the patches'
+ *   mass is 0);  C_i = P_i0;  M_i = max_j P_ij.
+ * summary fp32 (B, depth, 3, 8): [0] mean H_i over the 197 queries, [1] mean D_i over the 196 patch queries, [2] mean C_i over the patch
+ * queries, [3] mean P_ii over the 197 queries, [4] H_0, [5] P_00, [6] mean M_i over the 197 queries, [7] mean over the patch queries of
+ * sum P_ij over the patch keys j within Chebyshev grid distance 1 of i (self included, not renormalised).
+ * cls_attention fp32 (B, depth, 3, 196): P_0j, j = 1..196.  per_token (NULL, or fp32 (B, depth, 3, 197, 4), 16-byte aligned): H, D, C, M of
+ * every query row.  The probabilities are the bits rovit_attention_probs writes and are never stored; every sum has a fixed order (csrc/
+ * head_stats.hip), so a call is bit-identical run to run at a given batch.  Inference workspace, bf16 engine, one stream, every query row
+ * of the last block: `features` are the bits rovit_vit_forward_taps gives at the same batch. */
+int rovit_vit_forward_head_stats(const float* images, const float* const* params, const void* prep, void* workspace, float* features,
+                                 float* summary, float* cls_attention, float* per_token, int batch, int depth, rovit_stream_t stream);
+/* one block's step of the above on its saved qkv (bf16 (B*197, 576), scale 1/8): writes slice `block` of summary, cls_attention and
+ * per_token (NULL or as above).  partial: fp32 scratch of batch x 13 x 24 floats.  Two launches. */
+int rovit_attention_head_stats_step(const void* qkv, float* summary, float* cls_attention, float* per_token, float* partial, int batch,
+                                    int block, int depth, rovit_stream_t stream);
+/* Data-set reduction of n recorded rows: summary fp32 (n, depth*heads*8), cls_attention fp32 (n, depth*heads*196), labels int32 (n) or
+ * NULL with classes = 0.  block receives rovit_head_stats_block_words(depth, heads, classes) doubles: for group 0 (every row) and groups
+ * 1 + c (rows labelled c; labels outside 0..classes-1 count in group 0 only), [count, mean (R), unbiased variance (R), mean cls_attention
+ * (Q)] with R = depth*heads*8 and Q = depth*heads*196.  fp64, the rows walked in storage order; a group of no rows gives zeros, of one row
+ * variance 0. */
+size_t rovit_head_stats_block_words(int depth, int heads, int classes);
+int rovit_head_stats_finalize(const float* summary, const float* cls_attention, const int* labels, double* block, int n, int depth,
+                              int heads, int classes, rovit_stream_t stream);
 /* Grad-CAM++ at blocks[depth-1].norm1 (explainability/gradcam.py:34-104, GradCAMPlusPlus.compute), batched, bf16 engine, eval
  * semantics (no dropout).  Workspace: rovit_vit_gradcam_workspace_bytes(batch, depth) bytes (the inference workspace plus the last
  * block's class-token backward temporaries; 0 for a bad batch / depth).  rovit_vit_forward_gradcam = the inference forward, keeping

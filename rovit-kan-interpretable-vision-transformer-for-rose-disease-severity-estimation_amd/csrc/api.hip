@@ -57,6 +57,8 @@ void rovit_set_error(const char* fmt, ...) {
 // of the feature space, tsne.hip.)
 // (rovit_kmeans_workspace_bytes, rovit_kmeans_seed, rovit_kmeans_run, rovit_kmeans_assign and rovit_kmeans_contingency were added at 440
 // the same way: k-means of the feature space, kmeans.hip.)
+// (rovit_vit_forward_head_stats, rovit_attention_head_stats_step, rovit_head_stats_finalize and rovit_head_stats_block_words were added at
+// 440 the same way: per-head attention statistics, head_stats.hip / vit.hip.)
 extern "C" int rovit_version(void) { return 440; }
 extern "C" const char* rovit_last_error_string(void) { return g_err; }
 

@@ -316,6 +316,13 @@ struct RaggedSeqs {
   const int* host;
 };
 
+// rovit_vit_forward_head_stats: where the per-head attention statistics of every block go (head_stats.hip)
+struct HeadStatsOut {
+  float* summary;
+  float* cls_attention;
+  float* per_token;      // may be null
+};
+
 // prepare: 0 = the weights in `prep` are current; 1 = prepare them from `params` first; 2 = ... and write the constant tables too.
 // tokens: the sequence length (197 but for rovit_vit_forward_tokens / _train_tokens); rows: gather X from token tables instead of
 // embedding `images` (both given: embed `images` into rows->img first, then gather -- the training forward on kept tokens).
@@ -325,7 +332,7 @@ struct RaggedSeqs {
 int vit_forward_impl(const float* images, const float* const* params, const void* prep, void* workspace, float* features,
                      void* const* attn_taps, float* const* prob_taps, int batch, int depth, int training, int mlp_path,
                      rovit_stream_t stream, int prepare = 0, float* rollout = nullptr, int head_fusion = 0, bool gradcam = false,
-                     int tokens = T, const TokenRows* rows = nullptr, const RaggedSeqs* rg = nullptr) {
+                     int tokens = T, const TokenRows* rows = nullptr, const RaggedSeqs* rg = nullptr, const HeadStatsOut* head_stats = nullptr) {
   ROVIT_CHECK_ARG((images || rows) && features, ROVIT_ERR_NULL, "vit_forward: null images/features");
   RUN(check_common(params, prep, workspace, batch, depth, mlp_path));
   const Prep P(depth);
@@ -336,8 +343,9 @@ int vit_forward_impl(const float* images, const float* const* params, const void
   const int M = (int)L.M;
   const float eps = 1e-6f;
   // explainability outputs want every token of every block: one stream, no class-token shortcuts in the last block
-  const bool taps = attn_taps || prob_taps || rollout;
-  // (the rollout's partial sums, batch x 13 x 197 floats, sit in the dact slot: 52 bytes per token row of its 1536)
+  const bool taps = attn_taps || prob_taps || rollout || head_stats;
+  // (the rollout's partial sums, batch x 13 x 197 floats, sit in the dact slot: 52 bytes per token row of its 1536; the head statistics'
+  // batch x 13 x 24 floats take 7 bytes per token row of the same slot -- a call asks for one of the two)
   // Weight preparation inside the forward (rovit_vit_forward_prepare): four launches, 41 us per training step when they stand in front
   // of the forward.  Only the patch-embedding weight is needed at once; the blocks' weights are prepared on the side stream BESIDE the
   // patch embedding (59 us, bound by the fp32 pixels it reads), and the caller's stream waits for them in front of block 0.
@@ -446,6 +454,10 @@ int vit_forward_impl(const float* images, const float* const* params, const void
     // ... and the attention rollout (rollout.hip), folded into a running (B,197) vector behind every block's attention (before the
     // block tail overwrites qkv with the next block's); its partial sums use the dact slot, which an inference forward never writes
     if (rollout) RUN(rovit_rollout_step(s + L.qkv, rollout, (float*)(s + L.dact), head_fusion, batch, i == 0, stream));
+    // ... and the per-head attention statistics (head_stats.hip), at the same place for the same reason
+    if (head_stats)
+      RUN(rovit_attention_head_stats_step(s + L.qkv, head_stats->summary, head_stats->cls_attention, head_stats->per_token,
+                                          (float*)(s + L.dact), batch, i, depth, stream));
     // The last block: its post-attention half AND the final norm on the class-token rows in ONE launch (cls_tail.hip; six launches before).
     // (Taps want the attention module's output for every token: the launch-by-launch path below.)
     if (cls_only && cls_fused) {
@@ -639,6 +651,21 @@ extern "C" int rovit_vit_forward_rollout(const float* images, const float* const
                   head_fusion);
   return vit_forward_impl(images, params, prep, workspace, features, nullptr, nullptr, batch, depth, 0, ROVIT_MLP_AUTO, stream, 0, rollout,
                           head_fusion);
+}
+
+// Same forward (inference workspace), additionally reducing every block's attention to per-head statistics (head_stats.hip): summary fp32
+// (B, depth, 3, 8), cls_attention fp32 (B, depth, 3, 196) and, when given, per_token fp32 (B, depth, 3, 197, 4).  Like the taps, one stream
+// and every query row of the last block, so the features are the bits rovit_vit_forward_taps gives at the same batch.  The step's
+// partial sums (batch x 13 x 24 floats) sit in the workspace's dact slot (batch x 197 x 1536 bytes).
+extern "C" int rovit_vit_forward_head_stats(const float* images, const float* const* params, const void* prep, void* workspace,
+                                            float* features, float* summary, float* cls_attention, float* per_token, int batch, int depth,
+                                            rovit_stream_t stream) {
+  ROVIT_CHECK_ARG(summary && cls_attention, ROVIT_ERR_NULL, "vit_forward_head_stats: null summary / cls_attention");
+  ROVIT_CHECK_ARG(!per_token || rovit_aligned16(per_token), ROVIT_ERR_ALIGN, "vit_forward_head_stats: per_token must be 16-byte aligned");
+  static_assert((size_t)T * MLP * 2 >= 13 * 24 * sizeof(float), "the head statistics' partial sums must fit an image's share of the dact slot");
+  const HeadStatsOut hs{summary, cls_attention, per_token};
+  return vit_forward_impl(images, params, prep, workspace, features, nullptr, nullptr, batch, depth, 0, ROVIT_MLP_AUTO, stream, 0, nullptr,
+                          0, false, T, nullptr, nullptr, &hs);
 }
 
 // Same forward as rovit_vit_forward's inference mode (blocks 0..depth-2 and the last block's attention identical; workspace of

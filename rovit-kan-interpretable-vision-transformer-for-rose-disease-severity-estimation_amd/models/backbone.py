@@ -292,6 +292,13 @@ class DeiTTinyBackbone(nn.Module):
         from rovit_hip import rollout
         return rollout.attention_rollout(self.model, x, head_fusion, upsample)
 
+    def attention_head_stats(self, x: torch.Tensor, per_token: bool = False):
+        """Extension (not in the reference): per-head attention statistics of every image and block on the GPU -- entropy, mean attention
+        distance, class-token mass, self mass, row maximum, locality, and the class token's attention row -- from one fused forward
+        (rovit_hip.head_stats.attention_head_stats)."""
+        from rovit_hip import head_stats
+        return head_stats.attention_head_stats(self.model, x, per_token)
+
 
 def freeze_backbone(model: nn.Module, freeze: bool = True):
     if not hasattr(model, 'backbone'):

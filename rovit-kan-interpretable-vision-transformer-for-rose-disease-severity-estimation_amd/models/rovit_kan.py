@@ -220,6 +220,13 @@ class RoViTKAN(nn.Module):
         """Extension (not in the reference): DeiTTinyBackbone.attention_rollout of the backbone."""
         return self.backbone.attention_rollout(x, head_fusion, upsample)
 
+    def attention_head_stats(self, x_or_loader, per_token: bool = False, chunk: int = 256):
+        """Extension (not in the reference): per-head attention statistics (rovit_hip.head_stats).  A (B,3,224,224) tensor gives the
+        per-image dict of DeiTTinyBackbone.attention_head_stats; an iterable of (images, class_labels, severity_labels) batches gives
+        their mean and variance over the data set, for all images and per class label (``per_token`` is refused there)."""
+        from rovit_hip import head_stats
+        return head_stats.model_head_stats(self, x_or_loader, per_token, chunk)
+
     def grad_cam_pp(self, x: torch.Tensor, class_idx=None, upsample: bool = True, return_taps: bool = False, target='class'):
         """Extension (not in the reference): Grad-CAM++ at blocks[-1].norm1 for every image of the batch on the GPU, of cls_logits or,
         with ``target=``, of ordinal_severity / mu / log_var / kan_severity, or of several of them from one forward

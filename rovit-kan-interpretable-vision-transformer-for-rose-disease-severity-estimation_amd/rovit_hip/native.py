@@ -58,6 +58,10 @@ SIGNATURES = {
     'rovit_vit_forward_taps': (_i, [_vp] * 7 + [_i, _i, _vp]),
     'rovit_vit_forward_rollout': (_i, [_vp] * 6 + [_i, _i, _i, _vp]),
     'rovit_rollout_map': (_i, [_vp, _vp, _i, _vp]),
+    'rovit_vit_forward_head_stats': (_i, [_vp] * 8 + [_i, _i, _vp]),
+    'rovit_attention_head_stats_step': (_i, [_vp] * 5 + [_i, _i, _i, _vp]),
+    'rovit_head_stats_block_words': (_sz, [_i, _i, _i]),
+    'rovit_head_stats_finalize': (_i, [_vp] * 4 + [_i, _i, _i, _i, _vp]),
     'rovit_vit_gradcam_workspace_bytes': (_sz, [_i, _i]),
     'rovit_vit_forward_gradcam': (_i, [_vp] * 5 + [_i, _i, _vp]),
     'rovit_vit_gradcam': (_i, [_vp] * 8 + [_i, _i] + [_vp] * 6 + [_i, _i, _vp]),
