@@ -16,6 +16,7 @@
 // fp32 throughout, VALU FMAs (4 of the num_basis products per (sample, feature, output) are non-zero; a dense MFMA
 // form would multiply the structural zeros as well).
 #include "common.h"
+#include "kan_device.h"
 
 namespace {
 
@@ -53,13 +54,18 @@ __device__ __forceinline__ B4 ks_basis(float xn, const float* knots, int nk, flo
   while (j < nk - 1 && xc >= knots[j + 1]) ++j;
   if (j >= nb) { r.j = -1; r.v[0] = r.v[1] = r.v[2] = r.v[3] = 0.f; return r; }   // truncation: SURVEY.md 0.2
   const float tj = knots[j];
-  const float u = (xc - tj) / (knots[j + 1] - tj);
-  const float u2 = u * u, u3 = u2 * u, om = 1.f - u;
+  const float h = knots[j + 1] - tj;
   r.j = j;
-  r.v[0] = u3 * (1.f / 6.f);
-  r.v[1] = (-3.f * u3 + 3.f * u2 + 3.f * u + 1.f) * (1.f / 6.f);
-  r.v[2] = (3.f * u3 - 6.f * u2 + 4.f) * (1.f / 6.f);
-  r.v[3] = om * om * om * (1.f / 6.f);
+  if (!kan_locally_uniform(knots, j, h)) {                     // knots that are not uniform around j: the recursion itself (kan_device.h)
+    kan_basis_general<false>(xc, knots, j, r.v, nullptr);
+  } else {
+    const float u = (xc - tj) / h;
+    const float u2 = u * u, u3 = u2 * u, om = 1.f - u;
+    r.v[0] = u3 * (1.f / 6.f);
+    r.v[1] = (-3.f * u3 + 3.f * u2 + 3.f * u + 1.f) * (1.f / 6.f);
+    r.v[2] = (3.f * u3 - 6.f * u2 + 4.f) * (1.f / 6.f);
+    r.v[3] = om * om * om * (1.f / 6.f);
+  }
 #pragma unroll
   for (int m = 0; m < 4; ++m)
     if (j - m < 0) r.v[m] = 0.f;                               // left edge loses terms

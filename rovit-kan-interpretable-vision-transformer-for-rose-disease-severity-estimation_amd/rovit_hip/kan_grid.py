@@ -40,7 +40,8 @@ _GL_W = np.array([0.3478548451374538, 0.6521451548625461, 0.6521451548625461, 0.
 
 def check_grid(knots, what: str = 'knots') -> np.ndarray:
     """The fp32 knots as a numpy array, or RovitHipError: 8..64 of them, finite, strictly increasing and uniform by the rule of
-    ``KANSeverityModule._uniform_knots`` (the kernels' closed-form basis is the uniform cubic)."""
+    ``KANSeverityModule._uniform_knots`` (the refit's moments and priors are those of the uniform cubic, the kernels' closed form; the
+    forward kernels themselves follow any stored knots: kan_device.h)."""
     if isinstance(knots, torch.Tensor):
         knots = (knots.detach().cpu() if knots.is_cuda else knots.detach()).numpy()          # a host tensor costs no copy
     k = np.asarray(knots, dtype=np.float32).reshape(-1)
@@ -50,7 +51,7 @@ def check_grid(knots, what: str = 'knots') -> np.ndarray:
         raise RovitHipError(f'{what}: the knots must be finite and strictly increasing')
     hstep = float(k[-1] - k[0]) / (k.size - 1)
     if not float(np.abs(np.diff(k) - np.float32(hstep)).max()) <= 1e-4 * abs(hstep):
-        raise RovitHipError(f'{what}: non-uniform knots (the kernels evaluate the uniform cubic basis)')
+        raise RovitHipError(f'{what}: non-uniform knots (the refit is defined for the uniform cubic basis)')
     return k
 
 
