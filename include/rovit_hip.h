@@ -1806,6 +1806,58 @@ int rovit_kmeans_run(const rovit_kmeans_problem* p, rovit_stream_t stream);
 int rovit_kmeans_assign(const rovit_kmeans_problem* p, rovit_stream_t stream);
 int rovit_kmeans_contingency(const int* clusters, const int* classes, int n, int k, int num_classes, long long* table, rovit_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Adversarial perturbations (attack.hip): the projected step and the random start of a PGD attack (Madry et al. 2018) on normalised
+ * images.  The specification of record, in numpy, is rovit_hip/attack.py (step_reference, init_reference).
+ * Tensors: x, g, delta, x_adv, best_delta fp32 (B, 3, H, W) contiguous, n = H W >= 1 (any H, W; the model passes 224 x 224); x the
+ * clean normalised images, g the objective's gradient at x_adv (ascent), delta the perturbation in normalised units (read and
+ * overwritten), x_adv written.  eps, alpha: (B) fp32 DEVICE arrays, radius and step length per image in pixel units (image in
+ * [0, 1]); they are not checked: a negative or NaN entry gives that image an undefined perturbation and touches no other image.
+ * Host arrays of 3: inv_s[c] = fl32(1 / std_c), s[c] = std_c (L2 only), lo[c], hi[c] = the normalised values of pixel 0 and 1, or
+ * -inf / +inf for no box.  Per image and channel r = fl32(eps_b inv_s_c), a = fl32(alpha_b inv_s_c).
+ * clamp(v, l, h) below is: l when v < l, h when v > h, else v itself (a zero keeps its sign, a NaN passes through).
+ * copy_mask (B) bytes with best_delta, or both NULL: where copy_mask[b] != 0, best_delta[b] <- the delta the call was entered with
+ * (the perturbation whose objective value the caller has just found to be its best), before anything else.
+ *
+ * rovit_attack_step_linf, one launch.  Per element, every operation rounded once to fp32 and none contracted:
+ *   sg = +1, -1, 0 for g > 0, g < 0, and g == 0 or NaN;  d1 = delta + sg a;  d2 = clamp(d1, -r, r);  y = clamp(x + d2, lo_c, hi_c);
+ *   delta' = clamp(y - x, -r, r);  x_adv = clamp(x + delta', lo_c, hi_c).
+ * |delta'| <= r and lo_c <= x_adv <= hi_c hold exactly; eps_b == 0 gives x_adv == x wherever x is inside the box.  x_adv - x may
+ * differ from delta' by the one rounding of x + delta' (half an ulp of x_adv: 2^-23 at |x_adv| in [2, 4) against r >= 0.017 at
+ * eps = 1/255).
+ *
+ * rovit_attack_step_l2, three launches.  The ball is in pixel units, u = delta s_c.  gh = g inv_s_c (0 where g is not finite),
+ * G = sqrt(sum gh^2) over the image; d1 = delta + (alpha_b gh / G) inv_s_c (no move when G == 0: d1 == delta); the box in delta space,
+ * db = fl32(clamp(d1, lo_c - x, hi_c - x)) (the move is bounded before it meets x, so no rounding of x enters delta); U = sqrt(sum
+ * (db s_c)^2); delta' = fl32(db min(1, eps_b / U)) (the box is convex and holds x, so the shrink stays inside);
+ * x_adv = clamp(fl32(x + delta'), lo_c, hi_c).  Everything before each fl32 is fp64.  Both sums are fp64 sums in a fixed order: a
+ * workgroup sums its slab (thread-major, then the fixed tree of block_sum_t), the slab partials go to scratch, and every workgroup of
+ * the image adds the image's partials in index order.  No atomic; the same bits from run to run.
+ * scratch: rovit_attack_scratch_doubles(B, H, W) doubles (0 for a shape the kernels refuse), 8-byte aligned.
+ *
+ * rovit_attack_init: the random start.  Element e (its index in the (3, H, W) image) of image b takes word e % 4 of
+ * Philox4x32-10(key = seed, counter = (e / 4, (unsigned)ids[b], ROVIT_ATTACK_STREAM, restart)): a draw depends on (seed, ids[b], e,
+ * restart) alone.  ROVIT_ATTACK_LINF (one launch): d1 = fl32((2 u01(w) - 1) r), u01(w) = (w >> 8) 2^-24, then d2 .. x_adv as in the
+ * step.  ROVIT_ATTACK_L2 (three launches): Box-Muller normals in fp64 -- words (x, y) of a call give z(4k) = R cos(T), z(4k + 1) =
+ * R sin(T) with R = sqrt(-2 ln(((x >> 8) + 1) 2^-24)), T = 2 pi (y >> 8) 2^-24, words (z, w) give z(4k + 2), z(4k + 3) the same way --
+ * rounded once to fp32; d1 = (eps_b z / |z|_2) inv_s_c; then db .. x_adv as in the L2 step.  eps_b == 0 gives delta == 0.
+ *
+ * Every entry checks on the host, before any launch: null pointers, B >= 1, H, W >= 1, norm, inv_s and s finite and positive, lo / hi
+ * finite or -inf / +inf with lo <= hi, 4-byte alignment, and that x, g, delta, x_adv and best_delta do not overlap.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define ROVIT_ATTACK_STREAM 0x41646176u          /* "Adav": counter word 2, apart from the other Philox streams */
+enum { ROVIT_ATTACK_LINF = 0, ROVIT_ATTACK_L2 = 1 };
+size_t rovit_attack_scratch_doubles(int B, int H, int W);
+int rovit_attack_step_linf(const float* x, const float* g, float* delta, float* x_adv, float* best_delta, const unsigned char* copy_mask,
+                           const float* eps, const float* alpha, const float* inv_s, const float* lo, const float* hi, int B, int H, int W,
+                           rovit_stream_t stream);
+int rovit_attack_step_l2(const float* x, const float* g, float* delta, float* x_adv, float* best_delta, const unsigned char* copy_mask,
+                         const float* eps, const float* alpha, const float* inv_s, const float* s, const float* lo, const float* hi,
+                         double* scratch, int B, int H, int W, rovit_stream_t stream);
+int rovit_attack_init(const float* x, float* delta, float* x_adv, const long long* ids, const float* eps, int norm, unsigned long long seed,
+                      unsigned restart, const float* inv_s, const float* s, const float* lo, const float* hi, double* scratch, int B, int H,
+                      int W, rovit_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

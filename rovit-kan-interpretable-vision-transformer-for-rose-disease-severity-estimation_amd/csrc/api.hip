@@ -59,6 +59,8 @@ void rovit_set_error(const char* fmt, ...) {
 // the same way: k-means of the feature space, kmeans.hip.)
 // (rovit_vit_forward_head_stats, rovit_attention_head_stats_step, rovit_head_stats_finalize and rovit_head_stats_block_words were added at
 // 440 the same way: per-head attention statistics, head_stats.hip / vit.hip.)
+// (rovit_attack_scratch_doubles, rovit_attack_step_linf, rovit_attack_step_l2 and rovit_attack_init were added at 440 the same way: the
+// projected step and the random start of a PGD attack, attack.hip.)
 extern "C" int rovit_version(void) { return 440; }
 extern "C" const char* rovit_last_error_string(void) { return g_err; }
 

@@ -12,6 +12,7 @@
 //   KernelSHAP coalitions      shap.hip            (player / 4, sampled pair r, ROVIT_SHAP_STREAM, 0)  word player % 4 is the player's key
 //   PatchDropout subsets       patch_dropout.hip   (sample b, ROVIT_PATCH_DROPOUT_STREAM + patch / 4, step lo, step hi)  word patch % 4 is the patch's key
 //   k-means++ seeding          kmeans.hip          (seed index j, restart r, ROVIT_KMEANS_STREAM, 0)  r64 = (x << 32) | y
+//   PGD random start           attack.hip          (element / 4, image id, ROVIT_ATTACK_STREAM, restart)  word element % 4 is the element's
 // A caller with a 64-bit offset splits it at the call: (unsigned)off, (unsigned)(off >> 32).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -20,6 +20,8 @@ card) and adds ``metrics['knn']``: how well the neighbour-weighted vote alone cl
 with the classification head; ``evaluate_ood(..., index=fi)`` adds the ``'knn'`` card.
 ``evaluate_corruptions(store_or_loader)`` is the corruption-robustness score card: the test images corrupted on the device from the uint8
 store (``rovit_hip.corrupt``), one card per (corruption, severity) cell, the corruption errors and, against a baseline, CE and mCE.
+``evaluate_adversarial(loader)`` is its worst-case counterpart: the test images attacked on the device inside a ball of each radius
+(``rovit_hip.attack``), one card per radius with the robust accuracy, the flip rate and how far the severity outputs can be pushed.
 ``fit_laplace(train_loader)`` fits the last-layer Laplace approximation of the heads (``rovit_hip.laplace.HeadLaplace``);
 ``evaluate(laplace=la)`` records each row's mean logit variance and, from stage 3, the total standard deviation of ``mu`` as the extra
 columns ``laplace_logit_var`` and ``laplace_mu_std`` (two more scores of the selective card) and adds ``metrics['laplace']``: the prior
@@ -441,6 +443,164 @@ class Evaluator:
                   f"{'Mean corruption error:':<28}{result['mean_corruption_error']:.2f}%"]
         if result.get('mce') is not None:
             lines.append(f"{'mCE against the baseline:':<28}{result['mce']:.3f}")
+        return lines + ['']
+
+    def _adversarial_batches(self, source):
+        """A function that yields (images, class_labels, severity_labels) on the device, in the same order at every call: a
+        ``DeviceImageStore`` (or a loader that carries one) is read through its plain normalisation, any other loader is iterated."""
+        from rovit_hip.augment import DeviceImageStore
+        source = self.test_loader if source is None else source
+        if source is None:
+            raise RovitHipError('evaluate_adversarial needs images: pass a loader of (images, class_labels, severity_labels) batches or a '
+                                'DeviceImageStore')
+        if isinstance(source, DeviceImageStore) or isinstance(getattr(source, 'store', None), DeviceImageStore):
+            store, indices, batch_size = self._corruption_source(source)
+            order = store.upload_indices(indices)
+
+            def batches():
+                for lo in range(0, order.numel(), batch_size):
+                    sel = order[lo:lo + batch_size]
+                    yield store.corrupt(sel, 'brightness', param=0.0), store.labels.index_select(0, sel), store.severities.index_select(0, sel)
+            return batches
+        if not hasattr(source, '__iter__') or iter(source) is source:
+            raise RovitHipError('evaluate_adversarial: the source is visited once per cell, so it must be a loader or a list of batches, '
+                                'not an iterator')
+
+        def batches():
+            for images, class_labels, severity_labels in source:
+                yield images.to(self.device), class_labels.to(self.device), severity_labels.to(self.device)
+        return batches
+
+    def _adversarial_cell(self, batches, eps, attack_kw: Dict, targets, clean_pred):
+        """One cell: one pass into a fresh ``EvalAccumulator`` over the images attacked against their true labels (``eps=None``: the
+        clean pass, no attack), its ``compute()`` and ONE more device-to-host copy: the flips against ``clean_pred``, the summed
+        confidence and sigma, and per severity target the summed and the largest move of a ``direction=+1`` and a ``direction=-1``
+        attack of the same budget.  Returns the card and the predictions (on the device)."""
+        from rovit_hip.attack import pgd_attack
+        acc = EvalAccumulator(len(self.config.data.class_names))
+        self.model.eval()
+        moves = {name: None for name in targets} if eps is not None else {}
+        row = 0
+        for images, class_labels, severity_labels in batches():
+            n = images.shape[0]
+            ids = torch.arange(row, row + n, device=images.device)          # the row in the data set: a start never depends on the split
+            row += n
+            if eps is not None:
+                x_adv = pgd_attack(self.model, images, class_labels, eps=eps, ids=ids, check_labels=False, **attack_kw)
+                for name in moves:
+                    part = []
+                    for direction in (1, -1):
+                        kw = dict(attack_kw, objective=name, direction=direction)
+                        _, info = pgd_attack(self.model, images, None, eps=eps, ids=ids, return_info=True, **kw)
+                        move = (info['value'] - info['value_clean']).double()          # both carry the direction: a gain is positive
+                        part += [move.sum(), move.max()]
+                    part = torch.stack(part)
+                    old = moves[name]
+                    moves[name] = part if old is None else torch.stack([old[0] + part[0], torch.maximum(old[1], part[1]),
+                                                                        old[2] + part[2], torch.maximum(old[3], part[3])])
+            else:
+                x_adv = images
+            with torch.no_grad():
+                acc.update(self.model(x_adv), class_labels, severity_labels)
+        m = acc.compute()
+        if acc.device.type == 'cuda':
+            rec = {k: acc._rec[k][:acc.n] for k in ('pred', 'probs', 'uncertainty')}
+        else:
+            rec = {k: torch.from_numpy(v) for k, v in acc._cpu_arrays().items() if k in ('pred', 'probs', 'uncertainty')}
+        pred = rec['pred']
+        flips = (pred != clean_pred).sum() if clean_pred is not None else torch.zeros((), dtype=torch.int64, device=pred.device)
+        sigma = rec['uncertainty'].double().sum() if acc._has_uncertainty else torch.zeros((), dtype=torch.float64, device=pred.device)
+        head = torch.stack([flips.double(), rec['probs'].max(dim=1).values.double().sum(), sigma])
+        numbers = torch.cat([head] + [moves[name].to(head.device) for name in moves]).cpu().tolist()          # the one copy
+        flips, conf, sigma = numbers[:3]
+        card = {k: m[k] for k in self.CORRUPTION_CARD}
+        card.update(n=m['n'], correct=m['correct'], mean_confidence=conf / m['n'], flip_rate=flips / m['n'])
+        if acc._has_uncertainty:
+            card['mean_sigma'] = sigma / m['n']
+        if eps is not None:
+            card['severity'] = {}
+            for i, name in enumerate(moves):
+                up_sum, up_max, down_sum, down_max = numbers[3 + 4 * i:7 + 4 * i]
+                card['severity'][name] = {'mean_up': up_sum / m['n'], 'max_up': up_max, 'mean_down': down_sum / m['n'], 'max_down': down_max}
+        return card, pred
+
+    def evaluate_adversarial(self, source=None, eps=(1 / 255, 2 / 255, 4 / 255, 8 / 255), norm: str = 'linf', steps: int = 10,
+                             objective: str = 'ce', severity_targets=('ordinal_severity',), seed: int = 0):
+        """Extension (not in the reference): the worst-case counterpart of ``evaluate_corruptions`` -- a clean card once, then one
+        card per radius ``eps`` (pixel units, image in [0, 1]) over the images attacked against their TRUE labels with
+        ``rovit_hip.attack.pgd_attack`` (``norm``, ``steps``, ``objective`` 'ce' or 'margin', a random start drawn from ``seed`` and the
+        image's row in the data set).
+
+        ``source``: a loader or a list of (images, class_labels, severity_labels) batches that yields the same rows in the same order
+        at every visit (default ``self.test_loader``), or a ``DeviceImageStore``.  Returned dict: ``'clean'``; ``'eps'``; ``'cells'``,
+        one card per radius in the order given, with ``accuracy`` (the robust accuracy), ``macro_f1``, ``mae``, ``brier_score``,
+        ``ece``, ``mean_confidence``, ``mean_sigma`` when the model returns ``log_var``, ``n``, ``correct``, ``flip_rate`` (the share
+        of predictions that differ from the clean pass's) and ``'severity'[name]`` for every name of ``severity_targets`` the model's
+        curriculum stage has: ``mean_up`` / ``max_up``, how far a ``direction=+1`` attack of the same budget on that output raises it
+        (mean and largest over the images), and ``mean_down`` / ``max_down`` for ``direction=-1`` (how far it is lowered, positive
+        numbers).  Every number is what THIS attack finds: robust accuracy is an upper bound on the true one, the moves lower bounds.
+        Each cell makes one device-to-host copy beyond the accumulator's own.  The table is printed and saved as
+        ``adversarial_results.txt`` and ``.json`` in ``config.paths.results_dir``."""
+        from rovit_hip.attack import CLASS_OBJECTIVES, PGD
+        from rovit_hip.gradcam import TARGETS
+        what = 'evaluate_adversarial'
+        try:
+            radii = [e for e in eps]
+        except TypeError:
+            raise RovitHipError(f'{what}: eps must be a sequence of radii, got {eps!r}') from None
+        if not radii:
+            raise RovitHipError(f'{what}: no radius to evaluate')
+        try:
+            for e in radii:
+                PGD(norm, e, steps, None, True, 1, seed)
+        except RovitHipError as err:
+            raise RovitHipError(f'{what}: {err}') from None
+        if any(isinstance(e, torch.Tensor) for e in radii):
+            raise RovitHipError(f'{what}: every radius must be a number')
+        if objective not in CLASS_OBJECTIVES:
+            raise RovitHipError(f'{what}: objective must be one of {list(CLASS_OBJECTIVES)}, got {objective!r}')
+        if isinstance(severity_targets, str) or not all(isinstance(n, str) and n in TARGETS and n != 'class' for n in severity_targets):
+            raise RovitHipError(f"{what}: severity_targets must be names out of {[n for n in TARGETS if n != 'class']}, got {severity_targets!r}")
+        batches = self._adversarial_batches(source)
+        targets = [n for n in dict.fromkeys(severity_targets) if TARGETS[n][1] <= self.model.curriculum_stage]
+        attack_kw = {'objective': objective, 'norm': norm, 'steps': steps, 'seed': seed}
+        clean, clean_pred = self._adversarial_cell(batches, None, attack_kw, targets, None)
+        result = {'clean': clean, 'norm': norm, 'steps': steps, 'objective': objective, 'eps': [float(e) for e in radii], 'cells': []}
+        for e in radii:
+            card, _ = self._adversarial_cell(batches, float(e), attack_kw, targets, clean_pred)
+            result['cells'].append(dict(card, eps=float(e)))
+        lines = self._adversarial_lines(result)
+        print('\n'.join(lines))
+        results_dir = getattr(getattr(self.config, 'paths', None), 'results_dir', None)
+        if results_dir is not None:
+            import json
+            results_dir = Path(results_dir)
+            results_dir.mkdir(parents=True, exist_ok=True)
+            (results_dir / 'adversarial_results.txt').write_text('\n'.join(lines) + '\n', encoding='utf-8')
+            (results_dir / 'adversarial_results.json').write_text(json.dumps(result, indent=1) + '\n', encoding='utf-8')
+            print(f"Results saved to {results_dir / 'adversarial_results.txt'}")
+        return result
+
+    @staticmethod
+    def _adversarial_lines(result: Dict):
+        """Rows are radii; columns robust accuracy, flip rate, MAE, ECE, mean sigma and, per severity target, mean (largest) move up and down."""
+        has_sigma = 'mean_sigma' in result['clean']
+        names = list(result['cells'][0].get('severity', {})) if result['cells'] else []
+        unit = '255 eps' if result['norm'] == 'linf' else 'eps'
+        head = f"{unit:<10}{'Accuracy':>10}{'Flips %':>9}{'MAE':>9}{'ECE':>9}" + (f"{'Sigma':>9}" if has_sigma else '')
+        head += ''.join(f"{n + ' up':>26}{n + ' down':>26}" for n in names)
+        lines = ['', f"Adversarial robustness ({result['norm']}, {result['steps']} steps, {result['objective']}):", head, '-' * len(head)]
+
+        def row(label, c):
+            text = f"{label:<10}{c['accuracy']:>10.2f}{100.0 * c['flip_rate']:>9.2f}{c['mae']:>9.4f}{c['ece']:>9.4f}"
+            text += f"{c['mean_sigma']:>9.4f}" if has_sigma else ''
+            for n in names:
+                s = c.get('severity', {}).get(n)
+                text += ''.join(f"{f'{s[a]:.4f} ({s[b]:.4f})':>26}" for a, b in (('mean_up', 'max_up'), ('mean_down', 'max_down'))) if s else ''
+            return text
+        lines.append(row('clean', result['clean']))
+        for c in result['cells']:
+            lines.append(row(f"{c['eps'] * 255:g}" if result['norm'] == 'linf' else f"{c['eps']:g}", c))
         return lines + ['']
 
     @staticmethod

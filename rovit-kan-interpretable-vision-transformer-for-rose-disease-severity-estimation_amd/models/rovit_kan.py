@@ -241,6 +241,19 @@ class RoViTKAN(nn.Module):
         from rovit_hip import input_grad
         return input_grad.input_gradients(self, x, target, class_idx, steps, baseline, chunk, return_values)
 
+    def adversarial_examples(self, x: torch.Tensor, labels=None, **kw):
+        """Extension (not in the reference): adversarial images of ``x`` inside an L-infinity or L2 ball by projected gradient ascent on
+        the GPU, against the class (cross-entropy or margin) or a severity output (rovit_hip.attack.pgd_attack, whose keywords apply)."""
+        from rovit_hip import attack
+        return attack.pgd_attack(self, x, labels, **kw)
+
+    def robustness_radius(self, x: torch.Tensor, labels, norm: str = 'linf', eps_max: float = 8 / 255, search_steps: int = 8, steps: int = 10,
+                          **kw):
+        """Extension (not in the reference): per image, the smallest radius at which the attack changes the class -- a bisection over
+        eps for the whole batch at once; an upper bound on the true radius (rovit_hip.attack.robustness_radius)."""
+        from rovit_hip import attack
+        return attack.robustness_radius(self, x, labels, norm, eps_max, search_steps, steps, **kw)
+
     def attention_relevance(self, x: torch.Tensor, target='class', class_idx=None, upsample: bool = True, chunk: int = 256,
                             return_values: bool = False):
         """Extension (not in the reference): gradient-weighted attention relevance (Chefer, Gur & Wolf 2021) of cls_logits,

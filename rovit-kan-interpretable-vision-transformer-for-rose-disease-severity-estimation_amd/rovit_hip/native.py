@@ -193,6 +193,10 @@ SIGNATURES = {
     'rovit_kmeans_run': (_i, [_vp, _vp]),
     'rovit_kmeans_assign': (_i, [_vp, _vp]),
     'rovit_kmeans_contingency': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    'rovit_attack_scratch_doubles': (_sz, [_i, _i, _i]),
+    'rovit_attack_step_linf': (_i, [_vp] * 11 + [_i, _i, _i, _vp]),
+    'rovit_attack_step_l2': (_i, [_vp] * 13 + [_i, _i, _i, _vp]),
+    'rovit_attack_init': (_i, [_vp] * 5 + [_i, C.c_ulonglong, C.c_uint] + [_vp] * 5 + [_i, _i, _i, _vp]),
 }
 
 
@@ -489,6 +493,9 @@ class TsneDescent(C.Structure):
 KMEANS_MAX_ROWS, KMEANS_MAX_K, KMEANS_MAX_ITER, KMEANS_SEGMENT, KMEANS_STREAM = 1 << 20, 256, 100000, 1024, 0x4B4D6E73
 (KMEANS_N, KMEANS_N_VALID, KMEANS_BAD_ROWS, KMEANS_N_ITER, KMEANS_DONE, KMEANS_EMPTY, KMEANS_EMPTY_EVENTS, KMEANS_ZERO_MEANS, KMEANS_W0_EVENTS,
  KMEANS_SHORT, KMEANS_CHANGED, KMEANS_WORDS) = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 16
+
+
+ATTACK_STREAM, ATTACK_LINF, ATTACK_L2 = 0x41646176, 0, 1          # ROVIT_ATTACK_STREAM ("Adav"), the norms of rovit_attack_init
 
 
 class KMeansProblem(C.Structure):
