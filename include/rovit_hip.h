@@ -623,13 +623,16 @@ int rovit_mix_images(const float* images, float* out, const long long* perm, int
  * or NULL; t = 1-based step count for the bias correction.
  * ------------------------------------------------------------------------------------------------------------ */
 int rovit_sq_norm_accum(const float* g, size_t n, float* out_sq, float* scratch, rovit_stream_t stream);
-/* clip_grad_norm_ coefficient on the device: *norm_out = sqrt(*sq) (optional), *coef = min(1, max_norm / (norm + 1e-6)) */
+/* clip_grad_norm_ coefficient on the device: *norm_out = sqrt(*sq) (optional), *coef = min(1, max_norm / (norm + 1e-6)).
+ * NON-FINITE NORMS, as torch's clamp gives them: a NaN squared norm (any NaN gradient) gives *norm_out = NaN and *coef = NaN, so that
+ * the step it scales is poisoned as a whole, not applied unscaled; a norm of +inf gives *coef = 0; a norm of 0 gives *coef = 1 exactly. */
 int rovit_clip_coef(const float* sq, float max_norm, float* coef, float* norm_out, rovit_stream_t stream);
 int rovit_adamw_flat(float* p, const float* g, float* m, float* v, size_t n, const float* grad_scale, float lr, float beta1,
                      float beta2, float eps, float weight_decay, int t, rovit_stream_t stream);
 /* The same two steps as ONE launch each (round 4).  rovit_sq_norm_clip: squared norm over up to four buffers (HOST arrays bufs /
  * counts; 16-byte aligned, counts multiples of 4), block partials added in block order by the block that finishes last, then the
- * coefficient; scratch >= 264 floats, zeroed ONCE by the caller (the kernel re-arms its ticket).
+ * coefficient, by the same rule as rovit_clip_coef (NaN norm -> NaN coefficient, +inf -> 0, 0 -> 1: the two are one device function);
+ * scratch >= 264 floats, zeroed ONCE by the caller (the kernel re-arms its ticket).
  * rovit_adamw_flat_multi: rovit_adamw_flat over up to four segments with their own lr and step count t (HOST arrays). */
 int rovit_sq_norm_clip(const float* const* bufs, const size_t* counts, int n_bufs, float max_norm, float* coef, float* norm_out,
                        float* scratch, size_t scratch_floats, rovit_stream_t stream);

@@ -85,11 +85,17 @@ __global__ __launch_bounds__(256) void adamw_flat_kernel(float* __restrict__ p, 
   }
 }
 
+// clip_grad_norm_'s coefficient min(1, max_norm / (norm + 1e-6)) as torch.clamp(max=1) computes it: a NaN norm gives a NaN coefficient
+// (fminf alone would drop the NaN and return 1, and a poisoned step would be applied unscaled).  The one function both kernels below use.
+__device__ __forceinline__ float clip_coefficient(float norm, float max_norm) {
+  return norm != norm ? norm : fminf(1.f, max_norm / (norm + 1e-6f));
+}
+
 // clip_grad_norm_ coefficient from the accumulated squared norm: norm = sqrt(sq), coef = min(1, max_norm / (norm + 1e-6))
 __global__ void clip_coef_kernel(const float* __restrict__ sq, float max_norm, float* __restrict__ coef, float* __restrict__ norm_out) {
   const float n = sqrtf(*sq);
   if (norm_out) *norm_out = n;
-  *coef = fminf(1.f, max_norm / (n + 1e-6f));
+  *coef = clip_coefficient(n, max_norm);
 }
 
 // ---- the whole clip_grad_norm_ in ONE launch (round 4): squared norm over up to four buffers, then the coefficient ----
@@ -153,7 +159,7 @@ __global__ __launch_bounds__(NORM_THREADS) void sq_norm_clip_kernel(const NormSe
       for (int w = 0; w < NORM_THREADS / 64; ++w) tt += s_part[w];
       const float n = sqrtf(tt);
       if (norm_out) *norm_out = n;
-      *coef = fminf(1.f, max_norm / (n + 1e-6f));
+      *coef = clip_coefficient(n, max_norm);
       *(unsigned*)scratch = 0u;                   // ready for the next call on this stream
     }
   }
